@@ -18,22 +18,36 @@ and no collective touches the data path; the only inter-rank traffic is the
 gloo barrier, the max-over-ranks of the elapsed time and the verification
 counts.
 
-The line validates what it timed before it prints a number:
-* the library's overflow word is sticky across asynchronous batches, so the
-  ``synchronize()`` after the timed loop fails if any warm-up or timed batch
-  truncated its records or bin lists (no line is printed);
+A plain run does what the headline figure needs and no more: it sets up,
+warms up, times the K steps, writes the last timed step's outputs if
+``--dump-outputs DIR`` is given, and prints the line.  The library's overflow
+word is sticky across asynchronous batches, so the ``synchronize()`` after
+the timed loop fails if any warm-up or timed batch truncated its records or
+bin lists (no line is printed).  ``roofline`` (BASELINE.md:44 / SURVEY §8(d):
+fps x B_frame / 8 TB/s, plus per-kernel entries priced against the average
+launch of each kernel) comes from the HIP events the library records on its
+stream during the timed steps, so it takes no run of its own.
+
+``--full`` adds the legs that take runs of their own, after the timed steps:
 * frames of the last timed step are rendered again by the CPU oracle and
   compared byte for byte with what the GPU wrote during the timed region
   (RGB, instance ids, keypoint uv bits and visibility); any difference
-  aborts the run.  On rank 0 at N=1 the same oracle runs are the CPU
-  baseline.
+  aborts the run.  On rank 0 at N=1 the same oracle runs are
+  ``cpu_baseline`` (oracle/csg_oracle.c, a port of the same arithmetic --
+  the reference has no CPU render path -- single-thread and on the box's CPU
+  share, median of 5 after a warm-up, wall clock without file I/O);
+* ``with_label_stats``: batches timed with label statistics, occlusion
+  coverage and the depth visualisation;
+* ``pcie_inclusive``: batches timed with host outputs.
+Without ``--full`` those fields are null and ``verified.frames`` is 0.
 
-Reported extras: ``roofline`` (BASELINE.md:44 / SURVEY §8(d): fps x B_frame
-/ 8 TB/s, plus per-kernel entries priced against the average launch of each
-kernel timed with HIP events on its stream) and ``cpu_baseline``
-(oracle/csg_oracle.c, a port of the same arithmetic -- the reference has no
-CPU render path -- single-thread and on the box's CPU share, median of 5
-after a warm-up, wall clock without file I/O).
+``--dump-outputs DIR`` writes what the last timed step left in the output
+buffers as ``DIR/<name>.npy``: the keypoint arrays of every frame of the
+step whole, and of each per-pixel output the same fixed, seeded sample of
+pixels (``dump_pixel_sample``), float32 (float64 for the int32 outputs, so
+every id is exact), at most 64 MB in all.  The schedule is a function of the
+arguments alone, so two builds run with the same arguments write arrays that
+can be compared element for element.
 """
 from __future__ import annotations
 
@@ -67,6 +81,10 @@ MAX_SETS = 65536   # transform sets per context (kMaxSets, csg_api.cpp)
 # Host-delivery batches at N > 1 (every rank at once): 480 frames of C3 are
 # ~7 GB of pinned host outputs per rank, ~56 GB for the 8 ranks of a node.
 PCIE_FRAMES_MULTI = 480
+# --dump-outputs: bytes of all files together, and the most pixels sampled
+DUMP_MAX_BYTES, DUMP_MAX_PIXELS, DUMP_SEED = 60 << 20, 1 << 20, 0x5EED
+# schedule preparation in worker processes: from this many epochs on, at most this many workers
+PREP_MIN_EPOCHS, PREP_WORKERS_MAX = 512, 16
 
 
 def default_frames_per_step(width: int, height: int) -> int:
@@ -100,6 +118,55 @@ def verify_sample_indices(frames_per_step: int, n: int) -> List[int]:
     if n == 1:
         return [frames_per_step - 1]
     return [int(round(k * (frames_per_step - 1) / (n - 1))) for k in range(n)]
+
+
+def dump_pixel_sample(n_pixels_total: int, bytes_per_pixel: int, budget: int) -> np.ndarray:
+    """Flat pixel indices (frame-major, row, column) of the ``--dump-outputs``
+    sample: sorted, distinct, drawn with a fixed seed, as many as ``budget``
+    bytes hold at ``bytes_per_pixel`` (at most DUMP_MAX_PIXELS, and every
+    pixel if the outputs are that small)."""
+    n = int(max(0, min(DUMP_MAX_PIXELS, budget // max(bytes_per_pixel, 1), n_pixels_total)))
+    if n == n_pixels_total:
+        return np.arange(n, dtype=np.int64)
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.unique(rng.integers(0, n_pixels_total, size=n, dtype=np.int64))
+    return idx
+
+
+def dump_outputs(out_dir: str, dev_out: dict) -> dict:
+    """Write the step's outputs (``dev_out``: name -> device tensor, frames
+    first) as ``out_dir/<name>.npy``.  Keypoint arrays whole; per-pixel
+    arrays at the pixels of ``dump_pixel_sample``.  Integer outputs as
+    float64 (exact for every int32), the others as float32."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+
+    def as_float(t):
+        return t.to(torch.float64 if t.dtype in (torch.int32, torch.int64) else torch.float32)
+
+    small = {k: t for k, t in dev_out.items() if k.startswith("keypoints")}
+    images = {k: t for k, t in dev_out.items() if k not in small}
+    written = {}
+    used = 0
+    for k, t in small.items():
+        a = as_float(t).cpu().numpy()
+        used += a.nbytes
+        written[k] = a
+    if used > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench: --dump-outputs: the keypoint arrays alone hold {used} bytes")
+    if images:
+        first = next(iter(images.values()))
+        npix = first.shape[0] * first.shape[1] * first.shape[2]
+        per_px = sum((8 if t.dtype in (torch.int32, torch.int64) else 4) * (t.shape[3] if t.dim() == 4 else 1)
+                     for t in images.values())
+        idx = dump_pixel_sample(npix, per_px, DUMP_MAX_BYTES - used)
+        ix = torch.from_numpy(idx).to(first.device)
+        for k, t in images.items():
+            flat = t.reshape(npix, -1) if t.dim() == 4 else t.reshape(npix)
+            written[k] = as_float(flat.index_select(0, ix)).cpu().numpy()
+    for k, a in written.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in written.items()}
 
 
 def aggregate_value(steps: int, frames_per_step: int, world: int, elapsed_max: float) -> float:
@@ -283,6 +350,81 @@ def profiler_preload(env: Dict[str, str]) -> Optional[str]:
     return None
 
 
+def prep_worker_count(requested: int, n_epochs: int, world: int, env: Dict[str, str]) -> int:
+    """Worker processes that compute the schedule's epochs and cameras.  ``requested`` >= 0 is taken as given; -1 = this rank's
+    share of the CPUs (OMP_NUM_THREADS where it is set, else the CPUs this
+    process may use; at most PREP_WORKERS_MAX) for schedules of at least
+    PREP_MIN_EPOCHS epochs, else none: a short schedule is computed in this
+    process sooner than workers start.  Never under a profiler, whose preloaded
+    library every child process would load too."""
+    if profiler_preload(env):
+        return 0
+    if requested >= 0:
+        return requested
+    if n_epochs < PREP_MIN_EPOCHS:
+        return 0
+    cpus = int(env.get("OMP_NUM_THREADS") or 0) or available_cpus()
+    n = min(PREP_WORKERS_MAX, cpus // max(world, 1))
+    return n if n >= 2 else 0
+
+
+def prep_chunks(fids: List[int], chunk: int = 320) -> List[List[int]]:
+    """The schedule's frames in runs of ``chunk``, one task each."""
+    return [fids[k:k + chunk] for k in range(0, len(fids), chunk)]
+
+
+_PREP_WL = None   # a worker process's own Workload
+
+
+def _prep_init(workload: str, seed: int, width: int, height: int) -> None:
+    """Worker initialiser (as prep_pool.init): the same scene, the same seed."""
+    global _PREP_WL
+    from constructionsceneposeestimation_amd.workload import Workload
+    _PREP_WL = Workload(workload, seed=seed, width=width, height=height)
+
+
+def _prep_chunk(wl, frames: List[int]):
+    """What the bench uploads for a run of frames: its epochs' states (instance
+    transforms, keypoints, DR; not the object frames and joints, which only
+    labels need) and its frames' view and projection matrices."""
+    import dataclasses
+    wl = wl or _PREP_WL
+    views, projs = wl.frame_params(frames)
+    states = {e: dataclasses.replace(wl.epoch(e), object_frames=[], joints={}) for e in sorted({f // 10 for f in frames})}
+    return states, views, projs
+
+
+class SchedulePrep:
+    """The schedule's epoch states and camera matrices.  With ``workers`` > 0
+    they are computed by worker processes (as prep_pool.py does for the
+    generator: each worker builds its own Workload from the same arguments,
+    so the same numbers), started by ``__init__`` -- call it before this
+    process touches the GPU -- and handed out by ``chunks``; with none,
+    ``chunks`` computes them here."""
+
+    def __init__(self, wl, workload: str, seed: int, fids: List[int], workers: int):
+        self.wl, self.todo, self.pool, self.futs = wl, prep_chunks(fids), None, []
+        if workers > 0:
+            import multiprocessing as mp
+            from concurrent.futures import ProcessPoolExecutor
+            self.pool = ProcessPoolExecutor(max_workers=workers, mp_context=mp.get_context("spawn"),
+                                            initializer=_prep_init, initargs=(workload, seed, wl.width, wl.height))
+            self.futs = [self.pool.submit(_prep_chunk, None, c) for c in self.todo]
+
+    def chunks(self):
+        """Per run of frames, in schedule order: (epoch -> EpochState of the
+        run's epochs, views, projs of its frames)."""
+        if self.pool is None:
+            for c in self.todo:
+                yield _prep_chunk(self.wl, c)
+            return
+        try:
+            for fut in self.futs:
+                yield fut.result()
+        finally:
+            self.pool.shutdown(wait=True, cancel_futures=True)
+
+
 def median_time(fn: Callable[[], None], runs: int = 5, warmup: int = 1, what: str = "") -> float:
     """Median wall time of ``runs`` calls after ``warmup`` untimed ones.
     A progress line per call (stderr): a long CPU baseline is not silent."""
@@ -437,14 +579,25 @@ def main():
     ap.add_argument("--contexts", type=int, default=1,
                     help="renderer contexts per GPU, each with its own stream, work buffers and output buffers; "
                          "steps alternate between them so one step's short kernels overlap the other's k_raster")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: the oracle check "
+                         "of the timed outputs with the CPU baseline, the label-statistics batches and the "
+                         "host-delivery batches (--verify-frames, --stats-steps and --pcie-steps size them)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs to DIR/<name>.npy (keypoints whole, per-pixel "
+                         "outputs at a fixed seeded sample of pixels; float32 / float64, at most 64 MB)")
     ap.add_argument("--verify-frames", type=int, default=32,
-                    help="frames of the last timed step re-rendered by the oracle and compared (rank 0 at N=1: "
-                         "also the all-cores CPU baseline sample); 0 skips the check and the CPU baseline")
+                    help="with --full: frames of the last timed step re-rendered by the oracle and compared (rank 0 "
+                         "at N=1: also the all-cores CPU baseline sample); 0 skips the check and the CPU baseline")
     ap.add_argument("--verify-frames-multi", type=int, default=4, help="frames each rank checks when N > 1")
     ap.add_argument("--cpu-single-frames", type=int, default=3, help="frames of the single-thread CPU baseline run")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the all-cores CPU run (0 = all available)")
-    ap.add_argument("--pcie-steps", type=int, default=3, help="batches timed with host outputs (0 = skip)")
-    ap.add_argument("--stats-steps", type=int, default=5, help="batches timed with label statistics (0 = skip)")
+    ap.add_argument("--pcie-steps", type=int, default=3, help="with --full: batches timed with host outputs (0 = skip)")
+    ap.add_argument("--stats-steps", type=int, default=5,
+                    help="with --full: batches timed with label statistics (0 = skip)")
+    ap.add_argument("--prep-workers", type=int, default=-1,
+                    help="processes that compute the schedule's epochs and cameras before the GPU is touched "
+                         "(-1: this rank's share of the CPUs for schedules of 512 epochs or more, else none)")
     ap.add_argument("--size-work", type=int, default=1,
                     help="1: size the work buffers by a sizing pass over the schedule (csg_size_work); "
                          "0: the library's full-scene caps")
@@ -471,6 +624,23 @@ def main():
     if world != args.gpus:
         log(f"note: WORLD_SIZE={world} but --gpus={args.gpus}; using WORLD_SIZE")
 
+    # ---- schedule for every step: its epochs and cameras are numpy work of
+    # ~2 ms per epoch, computed in worker processes that start here, before
+    # this process imports torch or touches the GPU, and collected below
+    from constructionsceneposeestimation_amd.workload import WORKLOADS, Workload
+    t0 = time.time()
+    K, W = args.steps, args.warmup
+    wl = Workload(args.workload, seed=args.seed)
+    H, Wd = wl.height, wl.width
+    F = args.frames_per_step or default_frames_per_step(Wd, H)
+    fids = rank_frames(rank, world, W + K, F)
+    epochs = sorted({f // 10 for f in fids})
+    if len(epochs) > MAX_SETS:
+        raise SystemExit(f"bench: {len(epochs)} randomisation epochs on rank {rank}, the library holds {MAX_SETS} "
+                         "transform sets: fewer --steps or --frames-per-step")
+    n_prep = prep_worker_count(args.prep_workers, len(epochs), world, os.environ)
+    prep = SchedulePrep(wl, args.workload, args.seed, fids, n_prep)
+
     import torch
     import torch.distributed as dist
     if world > 1:
@@ -489,7 +659,6 @@ def main():
             os.close(saved)
 
     from constructionsceneposeestimation_amd.renderer import FRAME_DTYPE, Renderer, make_frames
-    from constructionsceneposeestimation_amd.workload import WORKLOADS, Workload
 
     # one rank per GPU (the driver's 8-GPU node: local = device); on a box with
     # fewer GPUs than ranks (a rehearsal) ranks share devices round-robin
@@ -499,35 +668,32 @@ def main():
     dev = torch.device("cuda", local)
     device_info = {"rank": rank, "local_rank": int(os.environ.get("LOCAL_RANK", "0")), "device": local,
                    "device_count": ndev, "pci": device_pci(local)}
-    K, W = args.steps, args.warmup
-    wl = Workload(args.workload, seed=args.seed)
-    H, Wd = wl.height, wl.width
-    F = args.frames_per_step or default_frames_per_step(Wd, H)
     outs = set(WORKLOADS[args.workload]["outputs"])   # C5 adds depth, normals and world points
     want_kp = "keypoints" in outs
-    t0 = time.time()
 
-    # ---- schedule for every step, uploaded before timing -------------------
-    fids = rank_frames(rank, world, W + K, F)
-    epochs = sorted({f // 10 for f in fids})
-    if len(epochs) > MAX_SETS:
-        raise SystemExit(f"bench: {len(epochs)} randomisation epochs on rank {rank}, the library holds {MAX_SETS} "
-                         "transform sets: fewer --steps or --frames-per-step")
+    # ---- the schedule, uploaded before timing -------------------------------
     set_of = {e: i for i, e in enumerate(epochs)}
     NC = max(1, args.contexts)
     ctxs = [Renderer(wl.scene, Wd, H, max_frames=F, device=local, frames_per_launch=args.frames_per_launch)
             for _ in range(NC)]
     r = ctxs[0]
-    for e in epochs:
-        st = wl.epoch(e)
-        for c in ctxs:
-            c.set_instance_transforms(set_of[e], st.models)
-            if want_kp:
-                c.set_keypoints(set_of[e], st.keypoints)
-            if st.dr is not None:                      # C4: per-epoch lighting and texture DR
-                c.set_dr_light(set_of[e], st.dr.light)
-                c.set_dr_textures(set_of[e], st.dr.textures)
-    views, projs = wl.frame_params(fids)
+    views, projs, uploaded = [], [], set()
+    for states, v, p in prep.chunks():
+        views.append(v)
+        projs.append(p)
+        for e, st in states.items():
+            if e in uploaded:
+                continue
+            uploaded.add(e)
+            for c in ctxs:
+                c.set_instance_transforms(set_of[e], st.models)
+                if want_kp:
+                    c.set_keypoints(set_of[e], st.keypoints)
+                if st.dr is not None:                      # C4: per-epoch lighting and texture DR
+                    c.set_dr_light(set_of[e], st.dr.light)
+                    c.set_dr_textures(set_of[e], st.dr.textures)
+    views, projs = np.concatenate(views), np.concatenate(projs)
+    t_sched = time.time() - t0
     frames = make_frames(views, projs, [set_of[f // 10] for f in fids], fids)
     frames_dev = torch.from_numpy(frames.view(np.uint8).copy()).to(dev)
     fsz = FRAME_DTYPE.itemsize
@@ -540,11 +706,13 @@ def main():
     # it the library sizes every frame for every scene triangle (~100 GB at C3 x
     # 960 frames)
     winfo = None
+    t1 = time.time()
     if args.size_work:
         for c in ctxs:
             winfo = c.size_work(frames_dev.data_ptr(), len(fids), on_device=True, margin=args.work_margin)
     else:
         winfo = r.work_info()
+    t_size = time.time() - t1
 
     def out_set():
         d = {"rgb": torch.empty((F, H, Wd, 3), dtype=torch.uint8, device=dev),
@@ -573,7 +741,8 @@ def main():
     extra = extras[0]
     streams = [torch.cuda.current_stream(dev)] + [torch.cuda.Stream(dev) for _ in range(NC - 1)]
     stream = streams[0].cuda_stream
-    log(f"[rank {rank}] setup {time.time() - t0:.1f}s: {len(fids)} frames, {len(epochs)} epochs, "
+    log(f"[rank {rank}] setup {time.time() - t0:.1f}s (schedule {t_sched:.1f}s with {n_prep} workers, sizing pass "
+        f"{t_size:.1f}s): {len(fids)} frames, {len(epochs)} epochs, "
         f"{wl.scene.n_tris_per_frame} tris/frame, K={Kp} keypoints")
 
     def step(s, **kw):
@@ -617,8 +786,11 @@ def main():
     dev_out = out_sets[(W + K - 1) % NC]        # the context that rendered the last timed step
 
     # ---- the last timed step's outputs, copied before anything reuses them --
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, dev_out)
+        log(f"[rank {rank}] wrote the last timed step's outputs to {args.dump_outputs}: {dumped}")
     nver = args.verify_frames if world == 1 else min(args.verify_frames, args.verify_frames_multi)
-    vidx = verify_sample_indices(F, nver)
+    vidx = verify_sample_indices(F, nver if args.full else 0)
     last = fids[(W + K - 1) * F:(W + K) * F]
     sample_frames = [last[k] for k in vidx]
     gpu_sample = {}
@@ -732,7 +904,7 @@ def main():
 
     # ---- with label statistics (rank 0, N=1 only; never `value`) -------------
     with_stats = None
-    if rank == 0 and world == 1 and args.stats_steps > 0:
+    if args.full and rank == 0 and world == 1 and args.stats_steps > 0:
         try:
             st_buf = torch.empty((F, r.n_labels, 5), dtype=torch.int32, device=dev)
             step(0, stats=st_buf.data_ptr())
@@ -774,7 +946,7 @@ def main():
     # user of the node gets.  Instance ids cross PCIe narrowed (csg_host_id_bytes)
     # and are widened to int32 on host threads inside the timed region.
     pcie = None
-    if args.pcie_steps > 0:
+    if args.full and args.pcie_steps > 0:
         import ctypes as C
         from constructionsceneposeestimation_amd import _lib
         Fp = F if world == 1 else min(F, PCIE_FRAMES_MULTI)
@@ -835,7 +1007,7 @@ def main():
         line = {
             "metric": METRIC, "value": round(value, 2), "unit": "frames/s", "n_gpus": world, "steps": K,
             "warmup": W, "ms_per_step": round(elapsed_max / K * 1e3, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": bool(args.full),
             "config": {"workload": f"{args.workload}: " + WORKLOADS[args.workload]["title"]
                                    + f", {Wd}x{H}, RGB8 + int32 instance mask"
                                    + (f" + {Kp} 2D keypoints/frame" if want_kp else "")

@@ -34,7 +34,7 @@ def test_bench_two_ranks_under_torchrun(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--steps", str(steps), "--warmup", str(warmup), "--frames-per-step", str(F),
-           "--verify-frames-multi", "4"]
+           "--verify-frames-multi", "4", "--full"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     log = tmp_path / "bench2.err"
     with open(log, "w") as err:
@@ -65,7 +65,7 @@ def test_bench_two_ranks_plain_command(tmp_path):
     shards and the oracle check."""
     steps, warmup, F = 2, 1, 48
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", str(steps), "--warmup",
-           str(warmup), "--frames-per-step", str(F), "--verify-frames-multi", "4"]
+           str(warmup), "--frames-per-step", str(F), "--verify-frames-multi", "4", "--full"]
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     log = tmp_path / "bench2plain.err"
@@ -112,7 +112,7 @@ def test_bench_single_rank_every_leg_with_hinted_pools(tmp_path):
     steps, warmup, F, G = 2, 1, 96, 48
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup),
            "--frames-per-step", str(F), "--frames-per-launch", str(G), "--verify-frames", "4",
-           "--pcie-steps", "1", "--stats-steps", "1", "--cpu-single-frames", "1"]
+           "--pcie-steps", "1", "--stats-steps", "1", "--cpu-single-frames", "1", "--full"]
     log = tmp_path / "bench1.err"
     with open(log, "w") as err:
         r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=err, text=True, timeout=540)
@@ -126,3 +126,45 @@ def test_bench_single_rank_every_leg_with_hinted_pools(tmp_path):
     assert w["pool_records"] < G * w["records_per_frame_cap"]
     assert d["pcie_inclusive"] is not None and d["pcie_inclusive"]["value"] > 0
     assert d["with_label_stats"] is not None
+
+
+def _plain_dump(out_dir, steps, warmup, F):
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup",
+           str(warmup), "--frames-per-step", str(F), "--dump-outputs", str(out_dir)]
+    r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert r.returncode == 0, f"plain bench failed ({r.returncode}):\n{r.stderr[-4000:]}"
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0])
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full the line carries the headline and nothing that takes a
+    run of its own; --dump-outputs writes the last timed step's arrays as
+    float .npy files (keypoints whole, a fixed sample of pixels) within
+    64 MB, and a second run with the same arguments writes the same bytes."""
+    import numpy as np
+    steps, warmup, F = 2, 1, 24
+    d = _plain_dump(tmp_path / "a", steps, warmup, F)
+    assert d["full"] is False and d["steps"] == steps and d["warmup"] == warmup
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "frames/s" and d["dtype"] == "f32"
+    assert abs(d["value"] - steps * F / (d["ms_per_step"] * steps / 1e3)) <= 0.01 * d["value"]
+    assert d["cpu_baseline"] is None and d["pcie_inclusive"] is None and d["with_label_stats"] is None
+    assert d["verified"]["frames"] == 0
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["instance.npy", "keypoints_uv.npy", "keypoints_vis.npy", "rgb.npy"]
+    arrs = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+    assert sum(a.nbytes for a in arrs.values()) <= 64 * 1000 * 1000
+    kp = arrs["keypoints_uv"].shape[1]
+    assert arrs["keypoints_uv"].shape == (F, kp, 2) and arrs["keypoints_vis"].shape == (F, kp)
+    n = arrs["instance"].shape[0]
+    assert n > 900_000 and arrs["rgb"].shape == (n, 3)
+    rgb, inst = arrs["rgb"], arrs["instance"]
+    assert rgb.min() >= 0 and rgb.max() <= 255 and np.array_equal(rgb, np.round(rgb)) and len(np.unique(rgb)) > 16
+    assert inst.min() >= -1 and np.array_equal(inst, np.round(inst)) and len(np.unique(inst)) > 2
+    assert set(np.unique(arrs["keypoints_vis"])) <= {0.0, 1.0, 2.0} and arrs["keypoints_vis"].any()
+    _plain_dump(tmp_path / "b", steps, warmup, F)
+    for nm in names:
+        assert (tmp_path / "a" / nm).read_bytes() == (tmp_path / "b" / nm).read_bytes(), nm

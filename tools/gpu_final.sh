@@ -14,7 +14,7 @@ if [ "${TEST:-1}" = 1 ]; then
   tail -1 $O/smoke.log
 fi
 if [ "${BENCH:-1}" = 1 ]; then
-  timeout -k 10 600 python3 bench.py > $O/bench_C3.json 2> $O/bench_C3.err || { tail -8 $O/bench_C3.err; exit 1; }
+  timeout -k 10 600 python3 bench.py --full > $O/bench_C3.json 2> $O/bench_C3.err || { tail -8 $O/bench_C3.err; exit 1; }
   python3 -c "import json; d=json.load(open('$O/bench_C3.json')); print('C3', d['value'], d['roofline']['frac'], d['stage_ms_per_step'], d['verified']['bit_exact'], d['cpu_baseline']['value'])" || exit 1
   timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_C3_driver.json 2> $O/bench_C3_driver.err || { tail -8 $O/bench_C3_driver.err; exit 1; }
   python3 -c "import json; d=json.load(open('$O/bench_C3_driver.json')); print('driver', d['value'], d['roofline']['frac'])" || exit 1
@@ -28,6 +28,6 @@ if [ -n "$PMC" ]; then
   tail -3 $O/pmc.log
 fi
 for w in ${WORKLOADS-C2 C4 C5}; do
-  timeout -k 10 600 python3 bench.py --workload $w --pcie-steps 0 --stats-steps 0 > $O/bench_$w.json 2> $O/bench_$w.err || { echo "$w failed"; tail -5 $O/bench_$w.err; exit 1; }
+  timeout -k 10 600 python3 bench.py --workload $w --full --pcie-steps 0 --stats-steps 0 > $O/bench_$w.json 2> $O/bench_$w.err || { echo "$w failed"; tail -5 $O/bench_$w.err; exit 1; }
   python3 -c "import json; d=json.load(open('$O/bench_$w.json')); print('$w', d['value'], d['roofline']['frac'], d['config']['frames_per_step'], d['verified']['frames'])"
 done

@@ -28,7 +28,7 @@ for spec in ${VARIANTS:-base s108 w64h16 w32h16 w16h16}; do
   v=${spec%%:*}; envs=""; [ "$spec" != "$v" ] && envs=$(echo ${spec#*:} | tr ':' ' ')
   tag=$(echo $spec | tr ':=' '__')
   if [ $v = base ]; then lib=$L/libcsg.so; else lib=$L/libcsg_$v.so; fi
-  env CSG_LIB=$lib $envs timeout -k 10 300 python3 bench.py $ARGS --verify-frames 8 > $O/tile_$tag.json 2> $O/tile_$tag.err || { echo "$spec FAILED"; tail -5 $O/tile_$tag.err; exit 1; }
+  env CSG_LIB=$lib $envs timeout -k 10 300 python3 bench.py $ARGS --full --verify-frames 8 > $O/tile_$tag.json 2> $O/tile_$tag.err || { echo "$spec FAILED"; tail -5 $O/tile_$tag.err; exit 1; }
   python3 -c "import json; d=json.load(open('$O/tile_$tag.json')); ws=d.get('with_label_stats') or {}; print('$spec rep $rep', d['value'], d['stage_ms_per_step'], 'recs/frame', d['records_per_frame'], 'bins/frame', d['bin_entries_per_frame'], 'exact', d['verified']['bit_exact'], d['verified']['frames'], 'stats', ws.get('value'), 'occl', (ws.get('with_occlusion_and_depth_png') or {}).get('value'))" | tee -a $O/tile_ab.txt
 done
 done
