@@ -12,7 +12,7 @@ from typing import Optional
 PKG = os.path.dirname(os.path.abspath(__file__))
 # CSG_LIB names an alternative build of the same ABI (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("CSG_LIB") or os.path.join(PKG, "libcsg.so")
-ABI_VERSION = 11  # CSG_ABI_VERSION in include/csg_api.h
+ABI_VERSION = 12  # CSG_ABI_VERSION in include/csg_api.h
 KEEP_TEXTURE = -2  # CSG_KEEP_TEXTURE
 COVERED_UNKNOWN = 0x80000000  # csg_outputs.label_covered flag: a tile held more than 32 labels
 ERR_CAPACITY = -6  # CSG_ERR_CAPACITY
@@ -25,7 +25,7 @@ EXPORTED = (
     "csg_render_batch", "csg_render_batch_async", "csg_synchronize", "csg_get_batch_stats",
     "csg_project_keypoints", "csg_timing_reset", "csg_timing_read", "csg_set_dr_light", "csg_set_dr_textures",
     "csg_instance_bounds", "csg_copy_files", "csg_host_alloc", "csg_host_free", "csg_size_work",
-    "csg_get_work_info", "csg_host_id_bytes",
+    "csg_get_work_info", "csg_host_id_bytes", "csg_set_object_frames",
 )
 
 
@@ -73,7 +73,7 @@ class Outputs(C.Structure):
                 ("points", C.c_void_p), ("depth_vis", C.c_void_p), ("depth_range", C.c_void_p),
                 ("label_covered", C.c_void_p), ("file_kinds", C.c_uint32), ("pad_files", C.c_uint32),
                 ("files", C.c_void_p), ("files_cap", C.c_uint64), ("file_offsets", C.c_void_p),
-                ("depth_stats", C.c_void_p)]
+                ("depth_stats", C.c_void_p), ("obj_coords", C.c_void_p)]
 
 
 class BatchStats(C.Structure):
@@ -146,6 +146,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     lib.csg_set_light.argtypes = [vp, C.POINTER(Light)]
     lib.csg_set_instance_transforms.argtypes = [vp, u32, vp, u32]
     lib.csg_set_keypoints.argtypes = [vp, u32, vp, u32]
+    lib.csg_set_object_frames.argtypes = [vp, u32, vp, u32]
     lib.csg_render_batch.argtypes = [vp, vp, u32, C.POINTER(Outputs)]
     lib.csg_render_batch_async.argtypes = [vp, vp, u32, i32, C.POINTER(Outputs), vp]
     lib.csg_synchronize.argtypes = [vp]

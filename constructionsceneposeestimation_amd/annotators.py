@@ -21,7 +21,13 @@ build's additions.
   (0 on background; C5);
 * ``rgb`` -> H x W x 4 uint8;
 * ``bounding_box_2d_tight`` / ``keypoints_2d`` -> this build's per-instance
-  pixel boxes and 2D keypoints (uv, visibility).
+  pixel boxes and 2D keypoints (uv, visibility);
+* ``object_coordinates`` -> ``{"data": H x W x 3 uint16, "info": {"bounds":
+  {inst_idx: [lo, hi]}, "primPaths": {inst_idx: prim path}}}``: this build's
+  dense object-coordinate (NOCS) map, each labelled pixel's surface point in
+  its object's frame normalised to the object's box
+  (``labels.decode_obj_coords`` gives metres); 0 on background and on
+  objects without a box.
 """
 from __future__ import annotations
 
@@ -30,12 +36,13 @@ from typing import Dict, Optional
 import numpy as np
 
 from . import sensors
-from .labels import bbox3d_records
+from .labels import bbox3d_records, object_box
 
 SUPPORTED = ("rgb", "distance_to_image_plane", "instance_segmentation", "bounding_box_3d",
-             "bounding_box_2d_tight", "pointcloud", "keypoints_2d", "normals")
+             "bounding_box_2d_tight", "pointcloud", "keypoints_2d", "normals", "object_coordinates")
 # renderer outputs an annotator needs beyond the camera's defaults
-_NEEDS = {"pointcloud": ("points",), "normals": ("normals",), "bounding_box_3d": ("covered",)}
+_NEEDS = {"pointcloud": ("points",), "normals": ("normals",), "bounding_box_3d": ("covered",),
+          "object_coordinates": ("obj_coords",)}
 
 
 class Annotator:
@@ -97,6 +104,11 @@ class Annotator:
             return {"data": pts, "pointRgb": rgba, "info": {"pointInstance": sem}}
         if self.name == "normals":
             return out["normals"].copy()
+        if self.name == "object_coordinates":
+            boxes = {o.inst_idx: (o, object_box(o)) for o in scene.objects}
+            return {"data": out["obj_coords"].copy(), "info": {
+                "bounds": {i: [b[0].tolist(), b[1].tolist()] for i, (o, b) in boxes.items() if b is not None},
+                "primPaths": {i: o.prim_path for i, (o, b) in boxes.items() if b is not None}}}
         if self.name == "keypoints_2d":
             return {"data": out.get("keypoints_uv"), "visibility": out.get("keypoints_vis"),
                     "info": {"table": cam.stage.workload.kp_table}}

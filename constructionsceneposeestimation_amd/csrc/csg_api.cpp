@@ -119,6 +119,13 @@ struct csg_ctx {
   std::vector<uint8_t> kp_valid;
   DevBuf<float> kp;
   bool kp_dirty = true;
+  // object frames (csg_set_object_frames): per set and label a 3x4 world -> unit-box matrix
+  uint32_t n_lab = 1;                   // label-table length: largest instance label + 1, at least 1
+  std::vector<float> h_of;              // [sets][n_lab][12], zeros where never set
+  uint32_t of_sets = 0;                 // sets h_of holds
+  DevBuf<float> of;                     // [of_table_sets][n_lab][12] (sync_object_frames)
+  uint32_t of_table_sets = 0;
+  bool of_dirty = true;
 
   // per-batch work buffers: record and bin pools shared by the frames of a
   // launch chain, each frame's region (Slab) planned by k_plan from its hints
@@ -156,6 +163,7 @@ struct csg_ctx {
   DevBuf<int32_t> o_inst;
   DevBuf<float> o_depth, o_kp_uv, kp_w, o_points, cam;
   DevBuf<uint16_t> o_normals;
+  DevBuf<uint16_t> o_objc;              // object coordinates (host-output mode)
   DevBuf<int32_t> o_kp_vis;
   DevBuf<uint32_t> kp_pix, kp_tiles;
   DevBuf<uint32_t> o_stats;
@@ -374,6 +382,7 @@ void csg_destroy(csg_ctx* c) {
   c->o_inst.release(); c->o_depth.release(); c->o_kp_uv.release(); c->o_kp_vis.release(); c->o_stats.release();
   c->kp_w.release(); c->kp_pix.release(); c->kp_tiles.release();
   c->o_points.release(); c->o_normals.release(); c->cam.release(); c->fset.release();
+  c->of.release(); c->o_objc.release();
   c->o_dvis.release(); c->o_drange.release(); c->o_cov.release(); c->drange.release(); c->jet.release();
   for (uint32_t k = 0; k < csg_ctx::kStaging; ++k) {
     if (c->h_stage[k]) (void)hipHostFree(c->h_stage[k]);
@@ -499,6 +508,7 @@ int csg_upload_scene(csg_ctx* c, const csg_mesh* meshes, uint32_t n_meshes, cons
     int32_t lo = -1, hi = -1;
     for (const InstDesc& d : idesc) { lo = std::min(lo, d.label); hi = std::max(hi, d.label); }
     c->ids_bytes = lo < -1 ? 4u : hi <= 254 ? 1u : hi <= 65534 ? 2u : 4u;
+    c->n_lab = (uint32_t)std::max<int64_t>((int64_t)hi + 1, 1);
   }
   c->iset.release();   // rebuilt for the new instances by the next sync_scene_state
   HIP_TRY(c, hipMemcpy(c->chunks.p, ch.data(), ch.size() * sizeof(Chunk), hipMemcpyHostToDevice));
@@ -518,6 +528,9 @@ int csg_upload_scene(csg_ctx* c, const csg_mesh* meshes, uint32_t n_meshes, cons
   c->kp_valid.clear();
   c->n_kp = 0;
   c->kp_dirty = true;
+  c->h_of.clear();
+  c->of_sets = 0;
+  c->of_dirty = true;
   c->have_scene = true;
   c->work_frames = 0;  // re-size work buffers,
   c->rec_cap = 0;      // with caps derived from this scene (or the config's fixed ones)
@@ -613,6 +626,26 @@ int csg_set_keypoints(csg_ctx* c, uint32_t set_id, const float* pts, uint32_t n)
   memcpy(&c->h_kp[(size_t)set_id * n * 3], pts, (size_t)n * 3 * sizeof(float));
   c->kp_valid[set_id] = 1;
   c->kp_dirty = true;
+  return CSG_OK;
+}
+
+int csg_set_object_frames(csg_ctx* c, uint32_t set_id, const float* world_to_unit, uint32_t n) {
+  if (!c) return CSG_ERR_INVALID;
+  if (!c->have_scene) return c->fail(CSG_ERR_INVALID, "set_object_frames: no scene");
+  if (!world_to_unit || n != c->n_lab || set_id >= kMaxSets)
+    return c->fail(CSG_ERR_INVALID, "set_object_frames: need %u matrices (one per label), set < %u", c->n_lab,
+                   kMaxSets);
+  const size_t per = (size_t)c->n_lab * 12;
+  for (size_t k = 0; k < per; ++k)
+    if (!std::isfinite(world_to_unit[k]))
+      return c->fail(CSG_ERR_INVALID, "set_object_frames: label %u: value %u is not finite", (unsigned)(k / 12),
+                     (unsigned)(k % 12));
+  if (c->of_sets <= set_id) {
+    c->of_sets = set_id + 1;
+    c->h_of.resize(c->of_sets * per, 0.f);
+  }
+  memcpy(&c->h_of[set_id * per], world_to_unit, per * sizeof(float));
+  c->of_dirty = true;
   return CSG_OK;
 }
 
@@ -766,6 +799,26 @@ static int sync_scene_state(csg_ctx* c) {
   return CSG_OK;
 }
 
+// The device table of the object frames, for batches that ask for obj_coords:
+// one row block per transform set (the sets k_clip lets through, b.n_sets), so
+// b.fset indexes it; sets without a table -- and sets past the transform sets,
+// which no frame can name -- hold zeros.
+static int sync_object_frames(csg_ctx* c) {
+  const uint32_t n_sets = (uint32_t)c->set_valid.size();
+  if (!c->of_dirty && c->of_table_sets == n_sets && c->of.p) return CSG_OK;
+  const int rc = drain(c);   // batches in flight read the table this rewrites
+  if (rc) return rc;
+  const size_t per = (size_t)c->n_lab * 12;
+  std::vector<float> t((size_t)n_sets * per, 0.f);
+  const size_t have = std::min<size_t>(c->of_sets, n_sets) * per;
+  if (have) memcpy(t.data(), c->h_of.data(), have * sizeof(float));
+  HIP_TRY(c, c->of.alloc(std::max<size_t>(t.size(), 12)));
+  if (!t.empty()) HIP_TRY(c, hipMemcpy(c->of.p, t.data(), t.size() * 4, hipMemcpyHostToDevice));
+  c->of_table_sets = n_sets;
+  c->of_dirty = false;
+  return CSG_OK;
+}
+
 // Record cap no frame can exceed: every triangle, plus 1/8 for the second
 // triangle of near-plane clips (and slack), rounded to 16-B rect rows.
 static uint32_t full_record_cap(const csg_ctx* c) {
@@ -914,6 +967,12 @@ static int enqueue_batch(csg_ctx* c, const csg_frame* frames, uint32_t F, int fr
       return c->fail(CSG_ERR_INVALID, "render: device outputs must be aligned (instance, depth, points 16 B; "
                                       "normals 8 B; rgb 4 B)");
   }
+  if (out->on_device && out->obj_coords && ((uintptr_t)out->obj_coords & 7u) != 0)
+    return c->fail(CSG_ERR_INVALID, "render: device obj_coords must be 8-B aligned");
+  if (out->obj_coords) {
+    rc = sync_object_frames(c);
+    if (rc) return rc;
+  }
   rc = ensure_work(c);
   if (rc) return rc;
   const size_t npx = (size_t)c->cfg.width * c->cfg.height;
@@ -1029,6 +1088,21 @@ static int enqueue_batch(csg_ctx* c, const csg_frame* frames, uint32_t F, int fr
       else { HIP_TRY(c, c->o_drange.alloc((size_t)F * 2)); drange_out = c->o_drange.p; }
     }
   }
+  // object coordinates: from the depth and instance images (internal scratch
+  // when the caller did not ask for them)
+  uint16_t* objc = nullptr;
+  if (out->obj_coords) {
+    if (!b.depth) {
+      HIP_TRY(c, c->o_depth.alloc(F * npx));
+      b.depth = c->o_depth.p;
+    }
+    if (!b.inst) {
+      HIP_TRY(c, c->o_inst.alloc(F * npx));
+      b.inst = c->o_inst.p;
+    }
+    if (dev) objc = out->obj_coords;
+    else { HIP_TRY(c, c->o_objc.alloc(F * npx * 3)); objc = c->o_objc.p; }
+  }
   double* dstats = nullptr;
   if (out->depth_stats) {
     HIP_TRY(c, c->dstat_part.alloc(depth_stats_scratch_bytes(c->chain_frames)));
@@ -1067,6 +1141,7 @@ static int enqueue_batch(csg_ctx* c, const csg_frame* frames, uint32_t F, int fr
     bool pinned = true;
     const void* dsts[] = {out->rgb, narrow ? nullptr : out->instance, out->depth, out->normals, out->points,
                           out->inst_stats, out->label_covered, out->depth_vis, out->depth_range, out->depth_stats,
+                          out->obj_coords,
                           want_kp ? out->keypoints_uv : nullptr, want_kp ? out->keypoints_vis : nullptr};
     for (const void* d : dsts) pinned = pinned && (!d || host_pinned(d));
     if (pinned || c->split_pageable) G = std::min(G, std::max(kMinCopyChain, (F + kCopyChunks - 1) / kCopyChunks));
@@ -1151,6 +1226,7 @@ static int enqueue_batch(csg_ctx* c, const csg_frame* frames, uint32_t F, int fr
         launch_depth_vis(bc.depth, (uint32_t)npx, Fc, c->drange.p, c->jet.p, vo, ro, st);
       }
     }
+    if (objc) launch_obj_coords(s, bc, Fc, c->of.p, c->n_lab, objc + (size_t)c0 * npx * 3, st);
     c->last_F = Fc;
     if (narrow) launch_narrow_ids(b.inst, (size_t)c0 * npx, (size_t)(c0 + Fc) * npx, c->ids_bytes, c->o_ids_n.p, st);
     if (!dev) {   // this chain's outputs to the host, on the copy stream, behind its kernels
@@ -1181,6 +1257,7 @@ static int enqueue_batch(csg_ctx* c, const csg_frame* frames, uint32_t F, int fr
       if (b.stats) HIP_TRY(c, copy(out->inst_stats, b.stats, (size_t)out->n_labels * 5 * 4));
       if (b.covered) HIP_TRY(c, copy(out->label_covered, b.covered, (size_t)out->n_labels * 4));
       if (out->depth_vis) HIP_TRY(c, copy(out->depth_vis, dvis, npx * 3));
+      if (out->obj_coords) HIP_TRY(c, copy(out->obj_coords, objc, npx * 6));
       if (drange_out) HIP_TRY(c, copy(out->depth_range, drange_out, 8));
       if (dstats) HIP_TRY(c, copy(out->depth_stats, dstats, 48));
       if (want_kp && out->keypoints_uv) HIP_TRY(c, copy(out->keypoints_uv, b.kp_uv, (size_t)c->n_kp * 8));

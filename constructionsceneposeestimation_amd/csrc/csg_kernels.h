@@ -220,6 +220,11 @@ void launch_raster(const SceneDev& s, const BatchDev& b, uint32_t F, hipStream_t
 // the JET-coloured RGB8 image; lut = 256 packed r | g << 8 | b << 16
 void launch_depth_vis(const float* depth, uint32_t npx, uint32_t F, const uint32_t* range, const uint32_t* lut,
                       uint8_t* vis, float* range_out, hipStream_t st);
+// object coordinates (NOCS) of the chain's frames from b.depth and b.inst (both needed), behind k_raster:
+// table [b.n_sets][n_lab][12] world -> unit box per (set, label), indexed with b.fset; out [F][H][W][3]
+// uint16.  4-pixel groups when npx % 4 == 0, b.px_align == 0 and the pointers are aligned, else per pixel.
+void launch_obj_coords(const SceneDev& s, const BatchDev& b, uint32_t F, const float* table, uint32_t n_lab,
+                       uint16_t* out, hipStream_t st);
 void launch_init_stats(const BatchDev& b, uint32_t F, hipStream_t st);
 void launch_keypoints(const SceneDev& s, const BatchDev& b, uint32_t F, hipStream_t st);
 void launch_inst_bounds(const SceneDev& s, const Chunk* chunks, uint32_t n_chunks, const float* models,

@@ -2414,6 +2414,81 @@ __global__ __launch_bounds__(256) void k_depth_vis(const float* __restrict__ dep
 }
 
 // ---------------------------------------------------------------------------
+// Object coordinates (NOCS): for every pixel of a labelled instance, the
+// position of its surface point in the object's own frame, normalised to the
+// object's box and quantised to 16 bits per axis.  Per pixel with id L >= 0:
+// P = unproject(depth) (the bits of the `points` output), A = table[set][L]
+// (row-major 3x4, world -> unit box, made on the host in float64 and rounded
+// once), q_i = ((A_i0*P.x + A_i1*P.y) + A_i2*P.z) + A_i3 in float32 without
+// contraction, u_i = (uint16)(min(max(q_i, 0), 1) * 65535 + 0.5).  L < 0 gives
+// (0, 0, 0); so does an all-zero table row (label without a box, set without
+// a table).  A streaming pass behind k_raster: 4 B depth + 4 B id read and 6 B
+// written per pixel (14 B/pixel); the set's table (48 B per label) is read
+// from global memory and stays cache-resident.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void obj_coord(const float* __restrict__ tab, uint32_t n_lab, const float* cam, int px,
+                                          int py, int32_t L, float d, uint32_t u[3]) {
+  u[0] = u[1] = u[2] = 0u;
+  if (L < 0 || (uint32_t)L >= n_lab) return;
+  float P[3];
+  unproject(cam, px, py, d, P);
+  const float4* A = reinterpret_cast<const float4*>(tab) + (size_t)L * 3;   // rows of 16 B
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const float4 a = A[i];
+    const float q = ((a.x * P[0] + a.y * P[1]) + a.z * P[2]) + a.w;
+    const float c = fminf(fmaxf(q, 0.0f), 1.0f);
+    u[i] = (uint32_t)(c * 65535.0f + 0.5f);
+  }
+}
+
+// kVec: one item per 4-pixel group (npx % 4 == 0, aligned pointers): 16-B
+// loads of depth and ids, three 8-B non-temporal stores.  Otherwise one pixel
+// per item.  `table` is [n_sets][n_lab][12]; fset the chain's checked sets.
+template <bool kVec>
+__global__ __launch_bounds__(256) void k_obj_coords(const float* __restrict__ depth, const int32_t* __restrict__ inst,
+                                                    const float* __restrict__ cam, const uint32_t* __restrict__ fset,
+                                                    const float* __restrict__ table, uint32_t n_lab, uint32_t W,
+                                                    uint32_t npx, uint16_t* __restrict__ out) {
+  const uint32_t f = blockIdx.y;
+  const float* cm = cam + (size_t)f * kCamFloats;
+  const float* tab = table + (size_t)fset[f] * n_lab * 12;
+  const size_t base = (size_t)f * npx;
+  if constexpr (kVec) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= npx / 4u) return;
+    const float4 dv = reinterpret_cast<const float4*>(depth + base)[q];
+    const int4 lv = reinterpret_cast<const int4*>(inst + base)[q];
+    const float d[4] = {dv.x, dv.y, dv.z, dv.w};
+    const int32_t l[4] = {lv.x, lv.y, lv.z, lv.w};
+    uint32_t py = (4u * q) / W, px = 4u * q - py * W;
+    uint32_t h[12];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      obj_coord(tab, n_lab, cm, (int)px, (int)py, l[k], d[k], h + 3 * k);
+      if (++px == W) {   // (a group may cross a row end when W % 4 != 0)
+        px = 0;
+        ++py;
+      }
+    }
+    uint16_t* o = out + (base + 4u * (size_t)q) * 3;   // 12 halves x0 y0 z0 x1 ... z3 as 6 words
+    out_u2(o, h[0] | (h[1] << 16), h[2] | (h[3] << 16));
+    out_u2(o + 4, h[4] | (h[5] << 16), h[6] | (h[7] << 16));
+    out_u2(o + 8, h[8] | (h[9] << 16), h[10] | (h[11] << 16));
+  } else {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npx) return;
+    const uint32_t py = i / W, px = i - py * W;
+    uint32_t h[3];
+    obj_coord(tab, n_lab, cm, (int)px, (int)py, inst[base + i], depth[base + i], h);
+    uint16_t* o = out + (base + i) * 3;
+    o[0] = (uint16_t)h[0];
+    o[1] = (uint16_t)h[1];
+    o[2] = (uint16_t)h[2];
+  }
+}
+
+// ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
 void launch_clip(const SceneDev& s, const BatchDev& b, uint32_t F, hipStream_t st) {
@@ -2493,6 +2568,22 @@ void launch_depth_vis(const float* depth, uint32_t npx, uint32_t F, const uint32
   dim3 g(vis ? (items + 255u) / 256u : 1u, F);
   if (vec) hipLaunchKernelGGL(k_depth_vis<true>, g, dim3(256), 0, st, depth, npx, F, range, lut, vis, range_out);
   else hipLaunchKernelGGL(k_depth_vis<false>, g, dim3(256), 0, st, depth, npx, F, range, lut, vis, range_out);
+}
+
+void launch_obj_coords(const SceneDev& s, const BatchDev& b, uint32_t F, const float* table, uint32_t n_lab,
+                       uint16_t* out, hipStream_t st) {
+  const uint32_t npx = s.W * s.H;
+  // the 4-pixel variant: whole groups only, the chain starting on a group, 16-B loads and 8-B stores aligned
+  const bool vec = (npx % 4u) == 0 && b.px_align == 0 && ((uintptr_t)b.depth & 15u) == 0 &&
+                   ((uintptr_t)b.inst & 15u) == 0 && ((uintptr_t)out & 7u) == 0;
+  const uint32_t items = vec ? npx / 4u : npx;
+  dim3 g((items + 255u) / 256u, F);
+  if (vec)
+    hipLaunchKernelGGL(k_obj_coords<true>, g, dim3(256), 0, st, b.depth, b.inst, b.cam, b.fset, table, n_lab, s.W, npx,
+                       out);
+  else
+    hipLaunchKernelGGL(k_obj_coords<false>, g, dim3(256), 0, st, b.depth, b.inst, b.cam, b.fset, table, n_lab, s.W,
+                       npx, out);
 }
 
 // ---------------------------------------------------------------------------

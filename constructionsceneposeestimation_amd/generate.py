@@ -18,6 +18,9 @@ same files:
   depth/depth_%06d.npy             (optional)
   pointcloud/pointcloud_%06d.txt   (:1716-1757; points from the GPU resolve, text encoded on the GPU)
   normals/normals_%06d.npy         (C5 normals, f16, optional)
+  obj_coords/obj_coords_%06d.npy   (object coordinates / NOCS, H x W x 3 uint16, optional; no
+                                    reference counterpart) + obj_coords/objects.json (each
+                                    object's prim_path, class_name, inst_idx and box lo / hi)
   logs/generation_summary.json     (:2090; statistics, frame_logs, counters)
   logs/generation_detail.log       (:254-263, per-frame entries + report)
 
@@ -46,7 +49,7 @@ import numpy as np
 
 from . import camera_math as cm
 from . import prep_pool
-from .labels import OBJECT_LISTS, in_frustum, label_record, object_poses
+from .labels import OBJECT_LISTS, in_frustum, label_record, object_box, object_poses
 from .quality_log import QualityLog
 from .renderer import Renderer, make_frames, output_spec, scene_labels
 from .shard import shard_of_range
@@ -72,7 +75,7 @@ def _log_done(log: QualityLog, fut, log_args: dict, points: bool) -> None:
     log.frame(depth_stats=ds, points=ds["valid"] if points and ds else None, **log_args)
 
 
-OUTPUTS = ("rgb", "mask", "depth_csv", "depth_png", "depth_npy", "pointcloud", "normals")
+OUTPUTS = ("rgb", "mask", "depth_csv", "depth_png", "depth_npy", "pointcloud", "normals", "obj_coords")
 # What the reference writes for every frame (GDP:1668-1771, 2055-2072): RGB PNG, depth CSV and
 # JET depth PNG, point-cloud TXT, instance mask .npy; the label JSON is always written (it is the
 # resume marker).
@@ -112,11 +115,11 @@ def render_outputs(outs: set, gpu_files: bool, host_depth: bool, occlusion: bool
     if gpu_files:
         want = (["keypoints", "stats", "depth_stats"] + (["instance"] if "mask" in outs else [])
                 + (["depth"] if host_depth else []) + (["depth_range"] if "depth_png" in outs else [])
-                + (["normals"] if "normals" in outs else []))
+                + (["normals"] if "normals" in outs else []) + (["obj_coords"] if "obj_coords" in outs else []))
     else:
         want = (["rgb", "instance", "keypoints", "stats"] + (["depth"] if host_depth else [])
                 + (["depth_vis"] if "depth_png" in outs else []) + (["points"] if "pointcloud" in outs else [])
-                + (["normals"] if "normals" in outs else []))
+                + (["normals"] if "normals" in outs else []) + (["obj_coords"] if "obj_coords" in outs else []))
     return want + (["covered"] if occlusion else [])
 
 
@@ -169,6 +172,15 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
     wl = Workload(workload, seed=seed, width=width, height=height)
     for d in ("rgb", "labels", "depth", "pointcloud", "normals", "logs"):
         os.makedirs(os.path.join(out_dir, d), exist_ok=True)
+    if "obj_coords" in outs:   # the boxes that turn the maps back into metres (labels.decode_obj_coords)
+        os.makedirs(os.path.join(out_dir, "obj_coords"), exist_ok=True)
+        objs = []
+        for o in wl.scene.objects:
+            box = object_box(o)
+            objs.append({"prim_path": o.prim_path, "class_name": o.class_name, "inst_idx": int(o.inst_idx),
+                         "lo": box[0].tolist() if box else None, "hi": box[1].tolist() if box else None})
+        with open(os.path.join(out_dir, "obj_coords", "objects.json"), "w") as fh:
+            json.dump({"objects": objs}, fh, indent=2)
     if resume:
         frames = [f for f in frames if not os.path.exists(os.path.join(out_dir, "labels", f"label_{f:06d}.json"))]
     # batch preparation in worker processes, started (like the writer processes
@@ -274,6 +286,8 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
             st = wl.epoch(e)
             r.set_instance_transforms(k, st.models)
             r.set_keypoints(k, st.keypoints)
+            if "obj_coords" in outs:
+                r.set_object_frames(k, st.object_frames)
             if st.dr is not None:
                 r.set_dr_light(k, st.dr.light)
                 r.set_dr_textures(k, st.dr.textures)
@@ -396,6 +410,9 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                     files.append((file_path(out_dir, "pointcloud", f), "pointcloud", ("points", "rgb")))
                 if "normals" in outs:
                     files.append((os.path.join(out_dir, "normals", f"normals_{f:06d}.npy"), "npy", ("normals",)))
+                if "obj_coords" in outs:
+                    files.append((os.path.join(out_dir, "obj_coords", f"obj_coords_{f:06d}.npy"), "npy",
+                                  ("obj_coords",)))
                 fut = pool.submit(slot, k, files, lab, os.path.join(out_dir, "labels", f"label_{f:06d}.json"))
                 pending.append((fut, log_args))
             del out

@@ -101,6 +101,50 @@ def object_poses(scene, object_frames) -> List[dict]:
             for o, c, sz, e in zip(scene.objects, center.tolist(), size.tolist(), euler.tolist())]
 
 
+def object_box(o) -> Optional[tuple]:
+    """(lo, hi) float64 of an object's local box, or None when it has no
+    usable one (no bounds, a non-finite bound, an extent <= 0)."""
+    if o.local_bounds is None:
+        return None
+    b = np.asarray(o.local_bounds, np.float64).reshape(2, 3)
+    if not np.all(np.isfinite(b)) or not np.all(b[1] - b[0] > 0):
+        return None
+    return b[0], b[1]
+
+
+def object_unit_transforms(scene, object_frames: Sequence[np.ndarray]) -> np.ndarray:
+    """(n_labels, 3, 4) float32: per label the matrix taking a world point to
+    the object's unit box (the ``obj_coords`` output's table,
+    csg_set_object_frames): ``diag(1 / (hi - lo)) @ (T_obj^-1 with lo
+    subtracted from the translation column)``, computed in float64 and
+    rounded once.  Labels without a usable box, and labels that belong to no
+    object, get all-zero rows (their pixels read 0)."""
+    n = max([o.inst_idx for o in scene.objects] + [i.inst_idx for i in scene.instances] + [-1]) + 1
+    out = np.zeros((max(n, 1), 3, 4), np.float64)
+    for j, o in enumerate(scene.objects):
+        box = object_box(o)
+        if box is None or o.inst_idx < 0:
+            continue
+        lo, hi = box
+        inv = np.linalg.inv(np.asarray(object_frames[j], np.float64).reshape(4, 4))[:3].copy()
+        inv[:, 3] -= lo
+        A = inv / (hi - lo)[:, None]
+        if np.all(np.isfinite(A)):
+            out[o.inst_idx] = A
+    return out.astype(np.float32)
+
+
+def decode_obj_coords(u16: np.ndarray, lo, hi) -> np.ndarray:
+    """Object-frame metres (float64) of ``obj_coords`` values (..., 3) of an
+    object with local box ``lo``, ``hi``: the inverse of the quantisation, to
+    within ``(hi - lo) / 65535`` per axis for points inside the box.  (0, 0, 0)
+    is also the value of pixels without an object: mask with the instance
+    image first.)"""
+    lo = np.asarray(lo, np.float64)
+    hi = np.asarray(hi, np.float64)
+    return lo + np.asarray(u16, np.float64) / 65535.0 * (hi - lo)
+
+
 OBJECT_LISTS = ("visible", "frustum")
 
 

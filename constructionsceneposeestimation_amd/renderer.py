@@ -18,6 +18,7 @@ import numpy as np
 from . import _lib
 from ._lib import CsgError
 from .camera_math import Intrinsics
+from .labels import object_unit_transforms
 from .packing import PackedScene, light_constants, pack_scene
 from .scene.model import Scene
 
@@ -26,7 +27,7 @@ FRAME_DTYPE = np.dtype([("view", "<f4", 16), ("proj", "<f4", 16), ("xform_set", 
 assert FRAME_DTYPE.itemsize == C.sizeof(_lib.Frame)
 
 OUTPUT_KINDS = ("rgb", "instance", "depth", "keypoints", "stats", "normals", "points", "depth_vis", "depth_range",
-                "covered", "depth_stats")
+                "covered", "depth_stats", "obj_coords")
 
 
 def make_frames(views: np.ndarray, projs: np.ndarray, sets: Sequence[int], frame_ids: Sequence[int]) -> np.ndarray:
@@ -82,6 +83,8 @@ def output_spec(n: int, H: int, W: int, n_kp: int, n_labels: int, want: Iterable
         spec["depth_stats"] = ((n, 6), np.float64)
     if "covered" in want:     # unoccluded pixels per label (occlusionRatio)
         spec["label_covered"] = ((n, n_labels), np.uint32)
+    if "obj_coords" in want:  # object coordinates (NOCS), 16 bits per axis (labels.decode_obj_coords)
+        spec["obj_coords"] = ((n, H, W, 3), np.uint16)
     return spec
 
 
@@ -105,6 +108,7 @@ class Renderer:
         self.n_inst = len(scene.instances)
         self.n_labels = max(self.packed.n_labels, 1)
         assert self.n_labels == scene_labels(scene)
+        self._n_inst_labels = max(int(self.packed.inst_label.max(initial=-1)) + 1, 1)
         self.n_kp = 0
         self._pinned: List[C.c_void_p] = []
         self._upload()
@@ -194,6 +198,20 @@ class Renderer:
         self._check(self.lib.csg_set_keypoints(self.ctx, set_id, p.ctypes.data, p.shape[0]), "set_keypoints")
         self.n_kp = p.shape[0]
 
+    def set_object_frames(self, set_id: int, object_frames) -> None:
+        """Object frames of transform set ``set_id`` (``EpochState.object_frames``,
+        per object of the scene) for the ``obj_coords`` output: uploads
+        :func:`labels.object_unit_transforms`.  ``object_frames`` may also be
+        that table itself, an (n, 3, 4) array with one matrix per label."""
+        t = object_frames
+        if not (isinstance(t, np.ndarray) and t.ndim == 3 and t.shape[1:] == (3, 4)):
+            # (the C ABI's label table spans the instances' labels)
+            t = object_unit_transforms(self.scene, object_frames)[:self._n_inst_labels]
+        elif t.shape[0] == self.n_labels:
+            t = t[:self._n_inst_labels]
+        t = np.ascontiguousarray(t, np.float32)
+        self._check(self.lib.csg_set_object_frames(self.ctx, set_id, t.ctypes.data, t.shape[0]), "set_object_frames")
+
     # -- rendering ------------------------------------------------------------
     def output_spec(self, n: int, want: Iterable[str]) -> Dict[str, tuple]:
         """Host arrays :meth:`render` fills for ``want``: name -> (shape, dtype)."""
@@ -222,7 +240,8 @@ class Renderer:
                               ("keypoints_uv", "keypoints_uv"), ("keypoints_vis", "keypoints_vis"),
                               ("inst_stats", "inst_stats"), ("normals", "normals"), ("points", "points"),
                               ("depth_vis", "depth_vis"), ("depth_range", "depth_range"),
-                              ("label_covered", "label_covered"), ("depth_stats", "depth_stats")):
+                              ("label_covered", "label_covered"), ("depth_stats", "depth_stats"),
+                              ("obj_coords", "obj_coords")):
                 arr = out.get(key)
                 if arr is not None:
                     setattr(oo, name, arr[s:e].ctypes.data)
@@ -287,7 +306,7 @@ class Renderer:
             raise CsgError("render_files: files must be a C-contiguous uint8 array")
         oo = _lib.Outputs()
         for key in ("rgb", "instance", "depth", "keypoints_uv", "keypoints_vis", "inst_stats", "normals", "points",
-                    "depth_vis", "depth_range", "label_covered", "depth_stats"):
+                    "depth_vis", "depth_range", "label_covered", "depth_stats", "obj_coords"):
             arr = out.get(key)
             if arr is not None:
                 setattr(oo, key, arr.ctypes.data)
@@ -310,11 +329,12 @@ class Renderer:
     def render_into(self, frames_ptr: int, n: int, frames_on_device: bool, rgb: int = 0, instance: int = 0,
                     depth: int = 0, kp_uv: int = 0, kp_vis: int = 0, stats: int = 0, stream: int = 0,
                     normals: int = 0, points: int = 0, depth_vis: int = 0, depth_range: int = 0,
-                    covered: int = 0, depth_stats: int = 0) -> None:
+                    covered: int = 0, depth_stats: int = 0, obj_coords: int = 0) -> None:
         """Enqueue a batch writing device buffers (raw pointers, e.g. torch ``data_ptr()``)."""
         o = _lib.Outputs(rgb or None, instance or None, depth or None, kp_uv or None, kp_vis or None,
                          stats or None, self.n_labels, 1, normals or None, points or None, depth_vis or None,
-                         depth_range or None, covered or None, 0, 0, None, 0, None, depth_stats or None)
+                         depth_range or None, covered or None, 0, 0, None, 0, None, depth_stats or None,
+                         obj_coords or None)
         self._check(self.lib.csg_render_batch_async(self.ctx, frames_ptr, n, int(frames_on_device), C.byref(o),
                                                     stream or None), "render_batch_async")
 

@@ -99,7 +99,7 @@ class Camera:
 
     def require(self, outputs) -> None:
         """Annotators attached to this camera ask for extra renderer outputs
-        (``points``, ``normals``); takes effect from the next frame."""
+        (``points``, ``normals``, ``obj_coords``); takes effect from the next frame."""
         new = set(outputs) - self._extra
         if new:
             self._extra |= new
@@ -170,6 +170,7 @@ class Camera:
             r.set_instance_transforms(0, st.models)
             if st.keypoints.shape[0]:
                 r.set_keypoints(0, st.keypoints)
+            r.set_object_frames(0, st.object_frames)
             if st.dr is not None:
                 r.set_dr_light(0, st.dr.light)
                 r.set_dr_textures(0, st.dr.textures)

@@ -20,6 +20,9 @@
  *   csg_set_dr_textures         sun, texture swap; C4 of BASELINE.json)
  *   csg_set_keypoints ......... (new) 3D points whose 2D projection is
  *                               annotated; the reference produces none
+ *   csg_set_object_frames ..... (new) per transform set, each label's world -> unit-box
+ *                               matrix for csg_outputs.obj_coords (the dense object-
+ *                               coordinate / NOCS label); the reference produces none
  *   csg_render_batch .......... camera.set_world_pose + next_update_async
  *                               + get_rgba / distance_to_image_plane /
  *                               instance_segmentation .get_data()     :1586-1595, :1669,
@@ -54,7 +57,7 @@
 extern "C" {
 #endif
 
-#define CSG_ABI_VERSION 11
+#define CSG_ABI_VERSION 12
 
 typedef enum {
   CSG_OK = 0,
@@ -133,7 +136,7 @@ typedef struct {
   uint32_t* inst_stats;      /* [n][n_labels][5] = pixels, minx, miny, maxx, maxy */
   uint32_t n_labels;
   int32_t on_device;         /* 1: device pointers (stay in HBM; instance, depth and points
-                                16-B aligned, normals 8 B, rgb 4 B: CSG_ERR_INVALID otherwise,
+                                16-B aligned, normals and obj_coords 8 B, rgb 4 B: CSG_ERR_INVALID otherwise,
                                 as k_raster stores 4-pixel groups), 0: host pointers */
   uint16_t* normals;         /* [n][H][W][3] f16 bits: unit world-space face normal facing
                                 the camera; 0 where nothing is hit (C5 normals) */
@@ -164,6 +167,17 @@ typedef struct {
                                 pixels, sum / min / max of the valid depths (the reference's
                                 DataQualityLogger.log_depth, GDP:318-341); the sum in float64 in a
                                 fixed order (64 partial sums per frame, then in order) */
+  uint16_t* obj_coords;      /* [n][H][W][3] object coordinates (NOCS): the pixel's surface point in its
+                                object's frame, normalised to the object's box (csg_set_object_frames) and
+                                quantised: u = (uint16)(min(max(q, 0), 1) * 65535 + 0.5) per axis, q =
+                                A * (the pixel's `points` value) with A the frame's set's matrix of the
+                                pixel's instance id.  (0, 0, 0) where the id is -1 -- also the value of the
+                                box's low corner: the instance image tells them apart -- and for labels
+                                without a box or sets without a table.  Parts of an articulated object
+                                (human limbs, crane parts) are expressed in the object root's frame and
+                                box; a posed part that leaves that box is clamped.  8-B aligned with
+                                on_device = 1.  Depth and ids it needs are rendered to internal scratch
+                                when the caller did not ask for them. */
 } csg_outputs;
 
 /* csg_outputs.file_kinds */
@@ -202,6 +216,15 @@ int csg_set_light(csg_ctx* ctx, const csg_light* light);
 int csg_set_instance_transforms(csg_ctx* ctx, uint32_t set_id, const float* model4x4, uint32_t n);
 /* World-space keypoints of one transform set: [n][3]; n is fixed per scene. */
 int csg_set_keypoints(csg_ctx* ctx, uint32_t set_id, const float* pts_world, uint32_t n);
+/* Object frames of one transform set for csg_outputs.obj_coords: per label a
+ * row-major 3x4 float32 matrix [n][12] taking a world point to the label's
+ * unit box, diag(1 / (hi - lo)) * (T_obj^-1 with lo subtracted from the
+ * translation), computed in float64 and rounded once.  n must equal the
+ * scene's label-table length (largest inst_idx + 1, at least 1); every value
+ * finite (CSG_ERR_INVALID otherwise).  All-zero rows give output 0: the rule
+ * for labels without a box and for instances of no object; sets that never
+ * got a table hold zeros. */
+int csg_set_object_frames(csg_ctx* ctx, uint32_t set_id, const float* world_to_unit, uint32_t n);
 
 /* Domain randomisation per transform set (randomisation epoch; C4).
  * csg_set_dr_light: the set's lighting (dome tint/intensity, sun), replacing
