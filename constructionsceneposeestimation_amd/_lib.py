@@ -12,12 +12,14 @@ from typing import Optional
 PKG = os.path.dirname(os.path.abspath(__file__))
 # CSG_LIB names an alternative build of the same ABI (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("CSG_LIB") or os.path.join(PKG, "libcsg.so")
-ABI_VERSION = 12  # CSG_ABI_VERSION in include/csg_api.h
+ABI_VERSION = 13  # CSG_ABI_VERSION in include/csg_api.h
 KEEP_TEXTURE = -2  # CSG_KEEP_TEXTURE
 COVERED_UNKNOWN = 0x80000000  # csg_outputs.label_covered flag: a tile held more than 32 labels
 ERR_CAPACITY = -6  # CSG_ERR_CAPACITY
 # csg_outputs.file_kinds (CSG_FILE_*): files encoded on the GPU, one per kind per frame, in bit order
-FILE_KINDS = {"rgb_png": 1, "depth_csv": 2, "depth_png": 4, "pointcloud_txt": 8}
+FILE_KINDS = {"rgb_png": 1, "depth_csv": 2, "depth_png": 4, "pointcloud_txt": 8, "pointcloud_ply": 16,
+              "depth16_png": 32}
+DEPTH16_COUNTS_PER_METRE = 250.0  # csg_outputs.depth16_counts_per_metre = 0: 4 mm steps, 262.1 m range
 
 EXPORTED = (
     "csg_create", "csg_destroy", "csg_last_error", "csg_abi_version", "csg_upload_scene",
@@ -73,7 +75,8 @@ class Outputs(C.Structure):
                 ("points", C.c_void_p), ("depth_vis", C.c_void_p), ("depth_range", C.c_void_p),
                 ("label_covered", C.c_void_p), ("file_kinds", C.c_uint32), ("pad_files", C.c_uint32),
                 ("files", C.c_void_p), ("files_cap", C.c_uint64), ("file_offsets", C.c_void_p),
-                ("depth_stats", C.c_void_p), ("obj_coords", C.c_void_p)]
+                ("depth_stats", C.c_void_p), ("obj_coords", C.c_void_p),
+                ("depth16_counts_per_metre", C.c_float)]
 
 
 class BatchStats(C.Structure):

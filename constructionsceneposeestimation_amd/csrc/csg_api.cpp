@@ -177,13 +177,15 @@ struct csg_ctx {
   const float* last_depth = nullptr;
   const float* last_points = nullptr;
   const uint8_t* last_dvis = nullptr;
-  DevBuf<EncPng> enc_rgb, enc_dpng;
+  DevBuf<EncPng> enc_rgb, enc_dpng, enc_d16;
   DevBuf<uint2> enc_rowsum;
-  DevBuf<uint32_t> enc_rows_rgb, enc_rows_dpng, enc_rows_csv, enc_rows_pcd;
+  DevBuf<uint32_t> enc_rows_rgb, enc_rows_dpng, enc_rows_csv, enc_rows_pcd, enc_rows_d16, enc_rows_ply, enc_ply_n;
+  DevBuf<uint8_t> enc_d16img;           // [F][H][W] big-endian 16-bit depth samples
   DevBuf<uint64_t> enc_fsize, enc_foff, enc_zoff;
   DevBuf<uint8_t> enc_zbuf, enc_out;
   DevBuf<uint8_t> dstat_part;           // depth-statistics partial sums
   DevBuf<double> o_dstats;              // depth statistics (host-output mode)
+  float depth16_scale = 250.0f;         // counts per metre of the batch's 16-bit depth PNGs
   uint64_t enc_total = 0;               // bytes of the last batch's files (0: none)
   uint32_t enc_nfiles = 0;
   std::vector<uint64_t> h_foff;
@@ -1056,15 +1058,15 @@ static int enqueue_batch(csg_ctx* c, const csg_frame* frames, uint32_t F, int fr
   if (!out->inst_stats) b.stats = nullptr;
   if (!out->label_covered || !out->n_labels) b.covered = nullptr;
   // images only a file needs go to internal scratch
-  if ((fk & (CSG_FILE_RGB_PNG | CSG_FILE_POINTCLOUD_TXT)) && !b.rgb) {
+  if ((fk & (CSG_FILE_RGB_PNG | CSG_FILE_POINTCLOUD_TXT | CSG_FILE_POINTCLOUD_PLY)) && !b.rgb) {
     HIP_TRY(c, c->o_rgb.alloc(F * npx * 3));
     b.rgb = c->o_rgb.p;
   }
-  if ((fk & CSG_FILE_POINTCLOUD_TXT) && !b.points) {
+  if ((fk & (CSG_FILE_POINTCLOUD_TXT | CSG_FILE_POINTCLOUD_PLY)) && !b.points) {
     HIP_TRY(c, c->o_points.alloc(F * npx * 3));
     b.points = c->o_points.p;
   }
-  if ((fk & CSG_FILE_DEPTH_CSV || out->depth_stats) && !b.depth) {
+  if ((fk & (CSG_FILE_DEPTH_CSV | CSG_FILE_DEPTH16_PNG) || out->depth_stats) && !b.depth) {
     HIP_TRY(c, c->o_depth.alloc(F * npx));
     b.depth = c->o_depth.p;
   }
@@ -1315,18 +1317,21 @@ static int copy_files(csg_ctx* c, uint8_t* dst, uint64_t cap, uint64_t* offsets)
 // synchronisation to size the buffers, then the bytes, then one D2H copy.
 static int encode_files(csg_ctx* c, const csg_outputs* out, uint32_t F) {
   const uint32_t fk = out->file_kinds;
-  uint32_t nk = 0, slot_rgb = 0, slot_csv = 0, slot_dpng = 0, slot_pcd = 0;
+  uint32_t nk = 0, slot_rgb = 0, slot_csv = 0, slot_dpng = 0, slot_pcd = 0, slot_ply = 0, slot_d16 = 0;
   if (fk & CSG_FILE_RGB_PNG) slot_rgb = nk++;
   if (fk & CSG_FILE_DEPTH_CSV) slot_csv = nk++;
   if (fk & CSG_FILE_DEPTH_PNG) slot_dpng = nk++;
   if (fk & CSG_FILE_POINTCLOUD_TXT) slot_pcd = nk++;
+  if (fk & CSG_FILE_POINTCLOUD_PLY) slot_ply = nk++;
+  if (fk & CSG_FILE_DEPTH16_PNG) slot_d16 = nk++;
   const uint32_t W = c->cfg.width, H = c->cfg.height, n_files = F * nk;
   hipStream_t st = c->stream;
   const size_t rows = (size_t)F * png_units_per_frame(W, H), csv_rows = (size_t)F * csv_units_per_frame(W, H);
   HIP_TRY(c, c->enc_fsize.alloc(n_files));
   HIP_TRY(c, c->enc_foff.alloc(n_files + 1));
-  HIP_TRY(c, c->enc_zoff.alloc(2 * (size_t)F + 1));
-  if (fk & (CSG_FILE_RGB_PNG | CSG_FILE_DEPTH_PNG)) HIP_TRY(c, c->enc_rowsum.alloc(rows));
+  HIP_TRY(c, c->enc_zoff.alloc(kPngKinds * (size_t)F + 1));
+  // (the 16-bit image's rows are shorter than the RGB ones': never more units)
+  if (fk & (CSG_FILE_RGB_PNG | CSG_FILE_DEPTH_PNG | CSG_FILE_DEPTH16_PNG)) HIP_TRY(c, c->enc_rowsum.alloc(rows));
   if (fk & CSG_FILE_RGB_PNG) {
     HIP_TRY(c, c->enc_rgb.alloc(F));
     HIP_TRY(c, c->enc_rows_rgb.alloc(rows));
@@ -1347,14 +1352,29 @@ static int encode_files(csg_ctx* c, const csg_outputs* out, uint32_t F) {
     HIP_TRY(c, c->enc_rows_pcd.alloc(csv_rows));
     launch_pcd_sizes(c->last_points, c->last_rgb, W, H, F, c->enc_rows_pcd.p, c->enc_fsize.p, nk, slot_pcd, st);
   }
+  if (fk & CSG_FILE_POINTCLOUD_PLY) {
+    HIP_TRY(c, c->enc_rows_ply.alloc(csv_rows));
+    HIP_TRY(c, c->enc_ply_n.alloc(F));
+    launch_ply_sizes(c->last_points, W, H, F, c->enc_rows_ply.p, c->enc_ply_n.p, c->enc_fsize.p, nk, slot_ply, st);
+  }
+  if (fk & CSG_FILE_DEPTH16_PNG) {
+    const size_t npx = (size_t)F * W * H;
+    HIP_TRY(c, c->enc_d16.alloc(F));
+    HIP_TRY(c, c->enc_rows_d16.alloc((size_t)F * png_units_per_frame(W, H, 2)));
+    HIP_TRY(c, c->enc_d16img.alloc(2 * npx));
+    launch_depth16(c->last_depth, npx, c->depth16_scale, c->enc_d16img.p, st);
+    launch_png_sizes(c->enc_d16img.p, W, H, F, c->enc_d16.p, c->enc_rowsum.p, c->enc_rows_d16.p, c->enc_fsize.p, nk,
+                     slot_d16, st, 2);
+  }
   const EncPng* pa = (fk & CSG_FILE_RGB_PNG) ? c->enc_rgb.p : nullptr;
   const EncPng* pb = (fk & CSG_FILE_DEPTH_PNG) ? c->enc_dpng.p : nullptr;
-  launch_file_layout(c->enc_fsize.p, n_files, c->enc_foff.p, pa, pb, F, c->enc_zoff.p, st);
+  const EncPng* pc = (fk & CSG_FILE_DEPTH16_PNG) ? c->enc_d16.p : nullptr;
+  launch_file_layout(c->enc_fsize.p, n_files, c->enc_foff.p, pa, pb, pc, F, c->enc_zoff.p, st);
   HIP_TRY(c, hipGetLastError());
   c->h_foff.resize(n_files + 1);
   uint64_t ztotal = 0;
   HIP_TRY(c, hipMemcpyAsync(c->h_foff.data(), c->enc_foff.p, sizeof(uint64_t) * (n_files + 1), hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipMemcpyAsync(&ztotal, c->enc_zoff.p + 2 * (size_t)F, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(&ztotal, c->enc_zoff.p + kPngKinds * (size_t)F, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
   const uint64_t total = c->h_foff[n_files];
   HIP_TRY(c, c->enc_out.alloc(total + 4));
@@ -1373,6 +1393,12 @@ static int encode_files(csg_ctx* c, const csg_outputs* out, uint32_t F) {
   if (fk & CSG_FILE_POINTCLOUD_TXT)
     launch_pcd_emit(c->last_points, c->last_rgb, W, H, F, c->enc_rows_pcd.p, c->enc_out.p, c->enc_foff.p, nk, slot_pcd,
                     st);
+  if (fk & CSG_FILE_POINTCLOUD_PLY)
+    launch_ply_emit(c->last_points, c->last_rgb, W, H, F, c->enc_rows_ply.p, c->enc_ply_n.p, c->enc_out.p,
+                    c->enc_foff.p, nk, slot_ply, st);
+  if (pc)
+    launch_png_emit(c->enc_d16img.p, W, H, F, pc, c->enc_rows_d16.p, c->enc_zbuf.p, c->enc_zoff.p + 2 * (size_t)F,
+                    c->enc_out.p, c->enc_foff.p, nk, slot_d16, st, 2);
   HIP_TRY(c, hipGetLastError());
   c->enc_total = total;
   c->enc_nfiles = n_files;
@@ -1385,9 +1411,16 @@ int csg_render_batch(csg_ctx* c, const csg_frame* frames, uint32_t n_frames, con
   // an earlier asynchronous batch that overflowed is reported, not lost
   int rc = csg_synchronize(c);
   if (rc) return rc;
-  if (out && (out->file_kinds & ~(CSG_FILE_RGB_PNG | CSG_FILE_DEPTH_CSV | CSG_FILE_DEPTH_PNG | CSG_FILE_POINTCLOUD_TXT)))
+  if (out && (out->file_kinds & ~(CSG_FILE_RGB_PNG | CSG_FILE_DEPTH_CSV | CSG_FILE_DEPTH_PNG | CSG_FILE_POINTCLOUD_TXT |
+                                  CSG_FILE_POINTCLOUD_PLY | CSG_FILE_DEPTH16_PNG)))
     return c->fail(CSG_ERR_INVALID, "render: unknown file kinds %#x", out->file_kinds);
   const uint32_t fk = out ? out->file_kinds : 0u;
+  if (out) {
+    const float s = out->depth16_counts_per_metre;
+    if (!(s >= 0.0f) || !(s < INFINITY))
+      return c->fail(CSG_ERR_INVALID, "render: depth16_counts_per_metre must be finite and >= 0 (0: the default, 250)");
+    c->depth16_scale = s == 0.0f ? 250.0f : s;
+  }
   for (int attempt = 0; attempt < 6; ++attempt) {
     rc = enqueue_batch(c, frames, n_frames, 0, out, c->stream, fk);
     if (rc) return rc;

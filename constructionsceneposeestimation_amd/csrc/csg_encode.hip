@@ -3,6 +3,10 @@
 // PNG and the JET depth PNG (cv2.imwrite, generate_construction_data.py
 // :1672-1673, :1690-1709), the depth CSV (np.savetxt "%.6f" :1687-1688) and
 // the point-cloud TXT (np.savetxt of x y z r g b, :766-770, :1756-1757).
+// Two compact kinds beside the reference's: the point cloud as a binary PLY
+// (15 B per point against about 35 B of text) and the depth as a 16-bit grey
+// PNG at a fixed scale (k_depth16 quantises, the PNG passes encode it at 2
+// bytes per pixel).
 // The host then only copies the packed bytes out and writes them.
 //
 // Work is parallel over segments of image rows (PNG: one thread per 512 raw
@@ -33,6 +37,8 @@
 //                   IEND at the ends
 //   k_csv_emit / k_pcd_emit  each lane formats its text into the wave's LDS
 //                   buffer; the wave stores the buffer coalesced
+//   Binary PLY: k_ply_len / k_ply_layout / k_ply_emit, same units and shape
+//   (count by ballot, records packed in LDS by rank, stored coalesced)
 //
 // Bandwidth (measured): the text kernels stream at 1.3-3.0 TB/s,
 // the PNG passes at 0.4-0.9 TB/s; all of them together take a tenth of the
@@ -55,11 +61,13 @@ constexpr int kRowsPerBlock = 64;   // one wave of units per workgroup (one fram
 constexpr uint32_t kSegBytes = 512;  // PNG: raw row bytes per unit
 constexpr uint32_t kSegVals = 64;    // CSV: values per unit
 
-__host__ __device__ __forceinline__ uint32_t png_units(uint32_t W) { return (3u * W + kSegBytes - 1u) / kSegBytes; }
+// rb: raw bytes of an image row, bytes per pixel * W
+__host__ __device__ __forceinline__ uint32_t png_units(uint32_t rb) { return (rb + kSegBytes - 1u) / kSegBytes; }
 __host__ __device__ __forceinline__ uint32_t csv_units(uint32_t W) { return (W + kSegVals - 1u) / kSegVals; }
 
-// The filtered PNG stream of unit k of an 8-bit RGB image row: raw bytes
-// [k * kSegBytes, ...) each minus the byte one pixel (3 bytes) to its left (0
+// The filtered PNG stream of unit k of an image row of kBpp bytes per pixel (3:
+// 8-bit RGB, 2: 16-bit grey, big-endian samples): raw bytes
+// [k * kSegBytes, ...) each minus the byte one pixel (kBpp bytes) to its left (0
 // before the row: filter type 1, Sub), preceded in unit 0 by the filter-type
 // byte.  Units are tokenised independently: a run never crosses a unit
 // boundary (a literal starts each unit; valid deflate, a few bytes larger).
@@ -70,9 +78,9 @@ __device__ __forceinline__ uint32_t byte_of(const uint4& v, int t) {
   return (w >> (8 * (t & 3))) & 255u;
 }
 
-template <class Sink>
+template <uint32_t kBpp, class Sink>
 __device__ __forceinline__ void png_unit_bytes(const uint8_t* row, uint32_t W, uint32_t k, Sink& sink) {
-  const uint32_t j0 = k * kSegBytes, j1 = min(j0 + kSegBytes, 3u * W);
+  const uint32_t j0 = k * kSegBytes, j1 = min(j0 + kSegBytes, kBpp * W);
   if (k == 0) sink.push(1u);
   uint32_t j = j0;
   if (((reinterpret_cast<uintptr_t>(row) + j0) & 15u) == 0 && j + 16u <= j1) {
@@ -82,14 +90,14 @@ __device__ __forceinline__ void png_unit_bytes(const uint8_t* row, uint32_t W, u
       const uint4 nxt = j + 32u <= j1 ? *reinterpret_cast<const uint4*>(row + j + 16) : cur;
 #pragma unroll
       for (int t = 0; t < 16; ++t) {
-        const uint32_t b = byte_of(cur, t), l = t >= 3 ? byte_of(cur, t - 3) : byte_of(prev, 13 + t);
+        const uint32_t b = byte_of(cur, t), l = t >= (int)kBpp ? byte_of(cur, t - (int)kBpp) : byte_of(prev, 16 - (int)kBpp + t);
         sink.push((b - l) & 255u);
       }
       prev = cur;
       cur = nxt;
     }
   }
-  for (; j < j1; ++j) sink.push((uint32_t)(row[j] - (j >= 3u ? row[j - 3] : 0u)) & 255u);
+  for (; j < j1; ++j) sink.push((uint32_t)(row[j] - (j >= kBpp ? row[j - kBpp] : 0u)) & 255u);
 }
 
 // Adler sums of a byte stream starting from (0, 0), reduced lazily.
@@ -115,14 +123,15 @@ __device__ __forceinline__ void png_unit(uint32_t u, uint32_t U, uint32_t& r, ui
   r = u / U;
   k = u - r * U;
 }
-__device__ __forceinline__ uint32_t png_unit_len(uint32_t k, uint32_t W) {
-  return min((k + 1u) * kSegBytes, 3u * W) - k * kSegBytes + (k == 0 ? 1u : 0u);
+__device__ __forceinline__ uint32_t png_unit_len(uint32_t k, uint32_t rb) {
+  return min((k + 1u) * kSegBytes, rb) - k * kSegBytes + (k == 0 ? 1u : 0u);
 }
 
+template <uint32_t kBpp>
 __global__ __launch_bounds__(kRowsPerBlock) void k_png_scan(const uint8_t* __restrict__ img, uint32_t W, uint32_t H,
                                                             EncPng* __restrict__ png, uint2* __restrict__ usum) {
   __shared__ uint32_t hist[kLitCodes];
-  const uint32_t f = blockIdx.y, U = png_units(W), u = blockIdx.x * kRowsPerBlock + threadIdx.x;
+  const uint32_t f = blockIdx.y, U = png_units(kBpp * W), u = blockIdx.x * kRowsPerBlock + threadIdx.x;
   for (uint32_t s = threadIdx.x; s < (uint32_t)kLitCodes; s += kRowsPerBlock) hist[s] = 0;
   __syncthreads();
   if (u < H * U) {
@@ -143,7 +152,7 @@ __global__ __launch_bounds__(kRowsPerBlock) void k_png_scan(const uint8_t* __res
         tok.push(x);
       }
     } sink{{lit, match}, &ad};
-    png_unit_bytes(img + ((size_t)f * H + r) * (size_t)W * 3u, W, k, sink);
+    png_unit_bytes<kBpp>(img + ((size_t)f * H + r) * (size_t)W * kBpp, W, k, sink);
     sink.tok.finish();
     usum[(size_t)f * H * U + u] = make_uint2((uint32_t)(ad.a % kAdlerMod), (uint32_t)(ad.b % kAdlerMod));
   }
@@ -156,7 +165,7 @@ __global__ __launch_bounds__(kRowsPerBlock) void k_png_scan(const uint8_t* __res
 // PNG pass 2: codes and header (one workgroup of 256 threads per frame)
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_png_codes(EncPng* __restrict__ png, const uint2* __restrict__ rowsum,
-                                                   uint32_t W, uint32_t H) {
+                                                   uint32_t rb, uint32_t H) {
   __shared__ uint32_t freq[kLitCodes];
   __shared__ uint16_t sorted[kLitCodes];
   __shared__ uint32_t work[kLitCodes];
@@ -237,12 +246,12 @@ __global__ __launch_bounds__(256) void k_png_codes(EncPng* __restrict__ png, con
   // (a, b, length) is associative)
   __shared__ uint32_t sa[256], sb[256];
   __shared__ uint64_t sl[256];
-  const uint32_t U = png_units(W), n = H * U, per = (n + 255u) / 256u, lo = t * per, hi = min(n, lo + per);
+  const uint32_t U = png_units(rb), n = H * U, per = (n + 255u) / 256u, lo = t * per, hi = min(n, lo + per);
   uint32_t a = 0, b = 0;
   uint64_t l = 0;
   for (uint32_t u = lo; u < hi; ++u) {
     const uint2 v = rowsum[(size_t)f * n + u];
-    const uint32_t len = png_unit_len(u % U, W);
+    const uint32_t len = png_unit_len(u % U, rb);
     adler_cat(a, b, v.x, v.y, len);
     l += len;
   }
@@ -270,10 +279,11 @@ __global__ __launch_bounds__(256) void k_png_codes(EncPng* __restrict__ png, con
 // ---------------------------------------------------------------------------
 // PNG pass 3: bits per row
 // ---------------------------------------------------------------------------
+template <uint32_t kBpp>
 __global__ __launch_bounds__(kRowsPerBlock) void k_png_bits(const uint8_t* __restrict__ img, uint32_t W, uint32_t H,
                                                             const EncPng* __restrict__ png, uint32_t* __restrict__ ubits) {
   __shared__ uint8_t clen[kLitCodes];
-  const uint32_t f = blockIdx.y, U = png_units(W), u = blockIdx.x * kRowsPerBlock + threadIdx.x;
+  const uint32_t f = blockIdx.y, U = png_units(kBpp * W), u = blockIdx.x * kRowsPerBlock + threadIdx.x;
   for (uint32_t s = threadIdx.x; s < (uint32_t)kLitCodes; s += kRowsPerBlock) clen[s] = (uint8_t)(png[f].code[s] >> 16);
   __syncthreads();
   if (u >= H * U) return;
@@ -290,7 +300,7 @@ __global__ __launch_bounds__(kRowsPerBlock) void k_png_bits(const uint8_t* __res
     RunTokenizer<decltype(lit)&, decltype(match)&> tok;
     __device__ void push(uint32_t x) { tok.push(x); }
   } sink{{lit, match}};
-  png_unit_bytes(img + ((size_t)f * H + r) * (size_t)W * 3u, W, k, sink);
+  png_unit_bytes<kBpp>(img + ((size_t)f * H + r) * (size_t)W * kBpp, W, k, sink);
   sink.tok.finish();
   ubits[(size_t)f * H * U + u] = bits;
 }
@@ -438,10 +448,11 @@ __global__ __launch_bounds__(256) void k_csv_layout(uint32_t* __restrict__ ulen,
 
 // Offsets of the batch's files in the packed output (foff[n_files + 1]) and
 // of each PNG frame's zlib staging area (zoff: kind a frames, then kind b
-// frames, then the total; 256-B aligned).  A few hundred entries: one thread.
+// frames, then kind c frames, then the total; 256-B aligned).  A few hundred
+// entries: one thread.
 __global__ void k_file_layout(const uint64_t* __restrict__ fsize, uint32_t n_files, uint64_t* __restrict__ foff,
-                              const EncPng* __restrict__ png_a, const EncPng* __restrict__ png_b, uint32_t F,
-                              uint64_t* __restrict__ zoff) {
+                              const EncPng* __restrict__ png_a, const EncPng* __restrict__ png_b,
+                              const EncPng* __restrict__ png_c, uint32_t F, uint64_t* __restrict__ zoff) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   uint64_t run = 0;
   for (uint32_t k = 0; k < n_files; ++k) {
@@ -450,12 +461,13 @@ __global__ void k_file_layout(const uint64_t* __restrict__ fsize, uint32_t n_fil
   }
   foff[n_files] = run;
   uint64_t z = 0;
-  for (uint32_t k = 0; k < 2u * F; ++k) {
+  for (uint32_t k = 0; k < kPngKinds * F; ++k) {
     zoff[k] = z;
-    const EncPng* p = k < F ? png_a : png_b;
-    if (p) z += ((uint64_t)p[k < F ? k : k - F].zbytes + 255u) & ~255ull;
+    const uint32_t kind = k / F;
+    const EncPng* p = kind == 0 ? png_a : kind == 1 ? png_b : png_c;
+    if (p) z += ((uint64_t)p[k - kind * F].zbytes + 255u) & ~255ull;
   }
-  zoff[2u * F] = z;
+  zoff[kPngKinds * F] = z;
 }
 
 // ---------------------------------------------------------------------------
@@ -494,12 +506,13 @@ struct WordBits {
   }
 };
 
+template <uint32_t kBpp>
 __global__ __launch_bounds__(kRowsPerBlock) void k_png_emit(const uint8_t* __restrict__ img, uint32_t W, uint32_t H,
                                                             const EncPng* __restrict__ png,
                                                             const uint32_t* __restrict__ uoff, uint8_t* zbuf,
                                                             const uint64_t* __restrict__ zbase) {
   __shared__ uint32_t code[kLitCodes];
-  const uint32_t f = blockIdx.y, U = png_units(W), u = blockIdx.x * kRowsPerBlock + threadIdx.x;
+  const uint32_t f = blockIdx.y, U = png_units(kBpp * W), u = blockIdx.x * kRowsPerBlock + threadIdx.x;
   for (uint32_t s = threadIdx.x; s < (uint32_t)kLitCodes; s += kRowsPerBlock) code[s] = png[f].code[s];
   __syncthreads();
   if (u >= H * U) return;
@@ -520,7 +533,7 @@ __global__ __launch_bounds__(kRowsPerBlock) void k_png_emit(const uint8_t* __res
     RunTokenizer<decltype(lit)&, decltype(match)&> tok;
     __device__ void push(uint32_t x) { tok.push(x); }
   } sink{{lit, match}};
-  png_unit_bytes(img + ((size_t)f * H + r) * (size_t)W * 3u, W, k, sink);
+  png_unit_bytes<kBpp>(img + ((size_t)f * H + r) * (size_t)W * kBpp, W, k, sink);
   sink.tok.finish();
   wb.finish();
 }
@@ -593,7 +606,7 @@ struct Crc {
 __global__ __launch_bounds__(64) void k_png_pack(const EncPng* __restrict__ png, const uint8_t* __restrict__ zbuf,
                                                  const uint64_t* __restrict__ zbase, uint8_t* out,
                                                  const uint64_t* __restrict__ foff, uint32_t W, uint32_t H, uint32_t nk,
-                                                 uint32_t kslot) {
+                                                 uint32_t kslot, uint32_t bpp) {
   __shared__ uint32_t T[256];
   for (uint32_t k = threadIdx.x; k < 256u; k += 64) T[k] = crc_entry(k);
   __syncthreads();
@@ -610,8 +623,10 @@ __global__ __launch_bounds__(64) void k_png_pack(const EncPng* __restrict__ png,
     for (int k = 0; k < 8; ++k) o.put(sig[k]);
     o.be32(13u);
     Crc c{T, 0xFFFFFFFFu};
+    // 3 bytes per pixel: bit depth 8, colour type 2 (RGB); 2: bit depth 16, colour type 0 (grey)
     const uint8_t ihdr[17] = {'I', 'H', 'D', 'R', (uint8_t)(W >> 24), (uint8_t)(W >> 16), (uint8_t)(W >> 8), (uint8_t)W,
-                              (uint8_t)(H >> 24), (uint8_t)(H >> 16), (uint8_t)(H >> 8), (uint8_t)H, 8, 2, 0, 0, 0};
+                              (uint8_t)(H >> 24), (uint8_t)(H >> 16), (uint8_t)(H >> 8), (uint8_t)H,
+                              (uint8_t)(bpp == 2u ? 16 : 8), (uint8_t)(bpp == 2u ? 0 : 2), 0, 0, 0};
     for (int k = 0; k < 17; ++k) {
       o.put(ihdr[k]);
       c.add(ihdr[k]);
@@ -734,6 +749,146 @@ __global__ __launch_bounds__(64 * kTxtWaves) void k_pcd_emit(const float* __rest
 }
 
 // ---------------------------------------------------------------------------
+// Binary PLY point cloud (CSG_FILE_POINTCLOUD_PLY): the header below, then per
+// pixel with a point (pcd_valid, the TXT writer's rule) a 15-byte record: the
+// three float32 of `points` as they are (little-endian) and the three RGB
+// bytes; row-major.  Units as the text files' (one wave per 64 pixels of a
+// row).  k_ply_len: the unit's record bytes from one ballot; k_ply_layout: the
+// units' offsets, the frame's point count N and file size (the header's length
+// depends on N's digits); k_ply_emit: lane -> 15 bytes at 15 * (its rank among
+// the wave's points) in the wave's LDS buffer (960 B), stored coalesced.
+// ---------------------------------------------------------------------------
+#define CSG_PLY_HEAD "ply\nformat binary_little_endian 1.0\nelement vertex "
+#define CSG_PLY_TAIL \
+  "\nproperty float x\nproperty float y\nproperty float z\n" \
+  "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n"
+constexpr uint32_t kPlyHeadLen = sizeof(CSG_PLY_HEAD) - 1, kPlyTailLen = sizeof(CSG_PLY_TAIL) - 1;
+constexpr uint32_t kPlyRecord = 15;
+constexpr uint32_t kPlyBuf = 64u * kPlyRecord;   // 960 B per wave
+static_assert(kPlyHeadLen + 10u + kPlyTailLen <= kPlyBuf, "the header is staged in the record buffer");
+
+__device__ __forceinline__ uint32_t dec_digits(uint32_t n) {
+  uint32_t d = 1;
+  for (; n >= 10u; n /= 10u) ++d;
+  return d;
+}
+// byte i of the header of a file of N points (nd = dec_digits(N))
+__device__ __forceinline__ uint32_t ply_header_byte(uint32_t i, uint32_t N, uint32_t nd) {
+  if (i < kPlyHeadLen) return (uint8_t)CSG_PLY_HEAD[i];
+  i -= kPlyHeadLen;
+  if (i >= nd) return (uint8_t)CSG_PLY_TAIL[i - nd];
+  for (uint32_t k = nd - 1u - i; k; --k) N /= 10u;
+  return '0' + N % 10u;
+}
+
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__global__ __launch_bounds__(64 * kTxtWaves) void k_ply_len(const float* __restrict__ pts, uint32_t W, uint32_t H,
+                                                            uint32_t* __restrict__ ulen) {
+  const uint32_t f = blockIdx.y, V = csv_units(W), lane = threadIdx.x & 63u;
+  const uint32_t u = blockIdx.x * kTxtWaves + (threadIdx.x >> 6);
+  if (u >= H * V) return;
+  uint32_t r, x0, x1;
+  txt_unit(u, V, W, r, x0, x1);
+  const uint32_t x = x0 + lane;
+  bool valid = false;
+  if (x < x1) {
+    const size_t px = ((size_t)f * H + r) * W + x;
+    valid = pcd_valid(pts[3 * px], pts[3 * px + 1], pts[3 * px + 2]);
+  }
+  const uint64_t mask = __ballot(valid);
+  if (lane == 0) ulen[(size_t)f * H * V + u] = kPlyRecord * (uint32_t)__popcll(mask);
+}
+
+// one workgroup per frame: unit byte offsets (from the end of the header), N, file size
+__global__ __launch_bounds__(256) void k_ply_layout(uint32_t* __restrict__ ulen, uint32_t n, uint32_t* __restrict__ npts,
+                                                    uint64_t* __restrict__ fsize, uint32_t nk, uint32_t kslot) {
+  __shared__ uint32_t sh[256];
+  const uint32_t f = blockIdx.x;
+  const uint32_t total = block_scan_inplace(ulen + (size_t)f * n, n, sh);
+  if (threadIdx.x == 0) {
+    const uint32_t N = total / kPlyRecord;
+    npts[f] = N;
+    fsize[(size_t)f * nk + kslot] = (uint64_t)(kPlyHeadLen + dec_digits(N) + kPlyTailLen) + total;
+  }
+}
+
+__global__ __launch_bounds__(64 * kTxtWaves) void k_ply_emit(const float* __restrict__ pts, const uint8_t* __restrict__ rgb,
+                                                             uint32_t W, uint32_t H, const uint32_t* __restrict__ uoff,
+                                                             const uint32_t* __restrict__ npts, uint8_t* out,
+                                                             const uint64_t* __restrict__ foff, uint32_t nk,
+                                                             uint32_t kslot) {
+  __shared__ uint32_t rbuf[kTxtWaves][kPlyBuf / 4 + 1];
+  const uint32_t f = blockIdx.y, V = csv_units(W), lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint32_t u = blockIdx.x * kTxtWaves + wv;
+  if (u >= H * V) return;
+  uint32_t r, x0, x1;
+  txt_unit(u, V, W, r, x0, x1);
+  const uint32_t x = x0 + lane;
+  float P[3] = {0.0f, 0.0f, 0.0f};
+  uint8_t c[3] = {0, 0, 0};
+  bool valid = false;
+  if (x < x1) {
+    const size_t px = ((size_t)f * H + r) * W + x;
+    P[0] = pts[3 * px];
+    P[1] = pts[3 * px + 1];
+    P[2] = pts[3 * px + 2];
+    c[0] = rgb[3 * px];
+    c[1] = rgb[3 * px + 1];
+    c[2] = rgb[3 * px + 2];
+    valid = pcd_valid(P[0], P[1], P[2]);
+  }
+  const uint64_t mask = __ballot(valid);
+  const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+  const uint32_t N = npts[f], nd = dec_digits(N), hdr = kPlyHeadLen + nd + kPlyTailLen;
+  const uint64_t base = foff[(size_t)f * nk + kslot];
+  uint8_t* t = reinterpret_cast<uint8_t*>(rbuf[wv]);
+  if (u == 0) {   // the frame's first unit also writes the header
+    for (uint32_t i = lane; i < hdr; i += 64u) t[i] = (uint8_t)ply_header_byte(i, N, nd);
+    wave_lds_sync();
+    wave_copy_out(rbuf[wv], hdr, out, base, lane);
+    wave_lds_sync();
+  }
+  if (valid) {
+    uint8_t* q = t + kPlyRecord * rank;
+    __builtin_memcpy(q, P, 12);   // a bit copy: -0.0 stays -0.0
+    q[12] = c[0];
+    q[13] = c[1];
+    q[14] = c[2];
+  }
+  wave_lds_sync();
+  wave_copy_out(rbuf[wv], kPlyRecord * (uint32_t)__popcll(mask), out, base + hdr + uoff[(size_t)f * H * V + u], lane);
+}
+
+// ---------------------------------------------------------------------------
+// 16-bit depth image (CSG_FILE_DEPTH16_PNG): sample v of depth d at s counts
+// per metre -- 0 where d is not finite or <= 0, else t = fl32(d * s), v =
+// 65535 if t >= 65535, else (uint32) fl32(t + 0.5f) -- as big-endian bytes,
+// the raw image the PNG passes encode at 2 bytes per pixel.  A valid depth
+// below half a count reads 0 like "no hit"; depths beyond 65535 / s saturate.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t depth16_be(float d, float s) {
+  if (!(d > 0.0f) || !(d < INFINITY)) return 0u;
+  const float t = __fmul_rn(d, s);
+  const uint32_t v = t >= 65535.0f ? 65535u : (uint32_t)__fadd_rn(t, 0.5f);
+  return (v >> 8) | ((v & 255u) << 8);
+}
+
+// one thread per pair of pixels of the flat batch image (img 4-B aligned)
+__global__ __launch_bounds__(256) void k_depth16(const float* __restrict__ depth, size_t npx, float s,
+                                                 uint8_t* __restrict__ img) {
+  const size_t p = 2 * ((size_t)blockIdx.x * 256u + threadIdx.x);
+  if (p + 1 < npx)
+    *reinterpret_cast<uint32_t*>(img + 2 * p) = depth16_be(depth[p], s) | (depth16_be(depth[p + 1], s) << 16);
+  else if (p < npx)
+    *reinterpret_cast<uint16_t*>(img + 2 * p) = (uint16_t)depth16_be(depth[p], s);
+}
+
+// ---------------------------------------------------------------------------
 // depth statistics of the quality log (csg_outputs.depth_stats)
 // ---------------------------------------------------------------------------
 constexpr uint32_t kStatBlocks = 64;
@@ -806,18 +961,42 @@ __global__ void k_depth_stats_final(const DepthPartial* __restrict__ part, uint3
 // ---------------------------------------------------------------------------
 // launchers (csg_encode.h)
 // ---------------------------------------------------------------------------
-uint32_t png_units_per_frame(uint32_t W, uint32_t H) { return png_units(W) * H; }
+uint32_t png_units_per_frame(uint32_t W, uint32_t H, uint32_t bpp) { return png_units(bpp * W) * H; }
 uint32_t csv_units_per_frame(uint32_t W, uint32_t H) { return csv_units(W) * H; }
 
 void launch_png_sizes(const uint8_t* img, uint32_t W, uint32_t H, uint32_t F, EncPng* png, uint2* usum,
-                      uint32_t* ubits, uint64_t* fsize, uint32_t nk, uint32_t kslot, hipStream_t st) {
-  const uint32_t n = png_units_per_frame(W, H);
+                      uint32_t* ubits, uint64_t* fsize, uint32_t nk, uint32_t kslot, hipStream_t st, uint32_t bpp) {
+  const uint32_t n = png_units_per_frame(W, H, bpp);
   const dim3 units((n + kRowsPerBlock - 1) / kRowsPerBlock, F);
   (void)hipMemsetAsync(png, 0, sizeof(EncPng) * F, st);
-  hipLaunchKernelGGL(k_png_scan, units, dim3(kRowsPerBlock), 0, st, img, W, H, png, usum);
-  hipLaunchKernelGGL(k_png_codes, dim3(F), dim3(256), 0, st, png, usum, W, H);
-  hipLaunchKernelGGL(k_png_bits, units, dim3(kRowsPerBlock), 0, st, img, W, H, png, ubits);
+  if (bpp == 2u) hipLaunchKernelGGL(k_png_scan<2>, units, dim3(kRowsPerBlock), 0, st, img, W, H, png, usum);
+  else hipLaunchKernelGGL(k_png_scan<3>, units, dim3(kRowsPerBlock), 0, st, img, W, H, png, usum);
+  hipLaunchKernelGGL(k_png_codes, dim3(F), dim3(256), 0, st, png, usum, bpp * W, H);
+  if (bpp == 2u) hipLaunchKernelGGL(k_png_bits<2>, units, dim3(kRowsPerBlock), 0, st, img, W, H, png, ubits);
+  else hipLaunchKernelGGL(k_png_bits<3>, units, dim3(kRowsPerBlock), 0, st, img, W, H, png, ubits);
   hipLaunchKernelGGL(k_png_layout, dim3(F), dim3(256), 0, st, png, ubits, n, fsize, nk, kslot);
+}
+
+void launch_depth16(const float* depth, size_t npx, float counts_per_metre, uint8_t* img, hipStream_t st) {
+  const size_t items = (npx + 1) / 2;
+  hipLaunchKernelGGL(k_depth16, dim3((uint32_t)((items + 255) / 256)), dim3(256), 0, st, depth, npx, counts_per_metre,
+                     img);
+}
+
+void launch_ply_sizes(const float* points, uint32_t W, uint32_t H, uint32_t F, uint32_t* ulen, uint32_t* npts,
+                      uint64_t* fsize, uint32_t nk, uint32_t kslot, hipStream_t st) {
+  const uint32_t n = csv_units_per_frame(W, H);
+  const dim3 units((n + kTxtWaves - 1) / kTxtWaves, F);
+  hipLaunchKernelGGL(k_ply_len, units, dim3(64 * kTxtWaves), 0, st, points, W, H, ulen);
+  hipLaunchKernelGGL(k_ply_layout, dim3(F), dim3(256), 0, st, ulen, n, npts, fsize, nk, kslot);
+}
+
+void launch_ply_emit(const float* points, const uint8_t* rgb, uint32_t W, uint32_t H, uint32_t F, const uint32_t* uoff,
+                     const uint32_t* npts, uint8_t* out, const uint64_t* foff, uint32_t nk, uint32_t kslot,
+                     hipStream_t st) {
+  const uint32_t n = csv_units_per_frame(W, H);
+  hipLaunchKernelGGL(k_ply_emit, dim3((n + kTxtWaves - 1) / kTxtWaves, F), dim3(64 * kTxtWaves), 0, st, points, rgb, W,
+                     H, uoff, npts, out, foff, nk, kslot);
 }
 
 void launch_csv_sizes(const float* depth, uint32_t W, uint32_t H, uint32_t F, uint32_t* ulen, uint64_t* fsize,
@@ -837,22 +1016,25 @@ void launch_pcd_sizes(const float* points, const uint8_t* rgb, uint32_t W, uint3
 }
 
 void launch_file_layout(const uint64_t* fsize, uint32_t n_files, uint64_t* foff, const EncPng* png_a,
-                        const EncPng* png_b, uint32_t F, uint64_t* zoff, hipStream_t st) {
-  hipLaunchKernelGGL(k_file_layout, dim3(1), dim3(64), 0, st, fsize, n_files, foff, png_a, png_b, F, zoff);
+                        const EncPng* png_b, const EncPng* png_c, uint32_t F, uint64_t* zoff, hipStream_t st) {
+  hipLaunchKernelGGL(k_file_layout, dim3(1), dim3(64), 0, st, fsize, n_files, foff, png_a, png_b, png_c, F, zoff);
 }
 
 void launch_png_emit(const uint8_t* img, uint32_t W, uint32_t H, uint32_t F, const EncPng* png, const uint32_t* rowoff,
                      uint8_t* zbuf, const uint64_t* zbase, uint8_t* out, const uint64_t* foff, uint32_t nk,
-                     uint32_t kslot, hipStream_t st) {
-  const uint32_t n = png_units_per_frame(W, H);
-  hipLaunchKernelGGL(k_png_emit, dim3((n + kRowsPerBlock - 1) / kRowsPerBlock, F), dim3(kRowsPerBlock), 0, st, img, W,
-                     H, png, rowoff, zbuf, zbase);
+                     uint32_t kslot, hipStream_t st, uint32_t bpp) {
+  const uint32_t n = png_units_per_frame(W, H, bpp);
+  const dim3 units((n + kRowsPerBlock - 1) / kRowsPerBlock, F);
+  if (bpp == 2u)
+    hipLaunchKernelGGL(k_png_emit<2>, units, dim3(kRowsPerBlock), 0, st, img, W, H, png, rowoff, zbuf, zbase);
+  else
+    hipLaunchKernelGGL(k_png_emit<3>, units, dim3(kRowsPerBlock), 0, st, img, W, H, png, rowoff, zbuf, zbase);
   hipLaunchKernelGGL(k_png_ends, dim3(F), dim3(64), 0, st, png, zbuf, zbase);
   // chunks per frame: at most the worst-case stream size / kIdatBytes
-  const uint64_t max_z = (uint64_t)H * (3ull * W + 1ull) * 2ull + 65536ull;
+  const uint64_t max_z = (uint64_t)H * ((uint64_t)bpp * W + 1ull) * 2ull + 65536ull;
   const uint32_t max_ch = (uint32_t)((max_z + kIdatBytes - 1) / kIdatBytes);
   hipLaunchKernelGGL(k_png_pack, dim3((max_ch + 63) / 64, F), dim3(64), 0, st, png, zbuf, zbase, out, foff, W, H, nk,
-                     kslot);
+                     kslot, bpp);
 }
 
 size_t depth_stats_scratch_bytes(uint32_t F) { return sizeof(DepthPartial) * kStatBlocks * F; }

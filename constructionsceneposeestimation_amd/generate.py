@@ -17,6 +17,11 @@ same files:
   depth/depth_%06d.png             (:1690-1709, JET colour map made on the GPU)
   depth/depth_%06d.npy             (optional)
   pointcloud/pointcloud_%06d.txt   (:1716-1757; points from the GPU resolve, text encoded on the GPU)
+  pointcloud/pointcloud_%06d.ply   (optional "pointcloud_ply": the same points as a binary PLY, xyz
+                                    float32 + rgb uchar, 15 B per point; no reference counterpart)
+  depth/depth16_%06d.png           (optional "depth16_png": 16-bit grey PNG at a fixed number of counts
+                                    per metre, writers.depth_to_u16) + depth/depth16.json (the scale;
+                                    0 = no hit)
   normals/normals_%06d.npy         (C5 normals, f16, optional)
   obj_coords/obj_coords_%06d.npy   (object coordinates / NOCS, H x W x 3 uint16, optional; no
                                     reference counterpart) + obj_coords/objects.json (each
@@ -75,7 +80,8 @@ def _log_done(log: QualityLog, fut, log_args: dict, points: bool) -> None:
     log.frame(depth_stats=ds, points=ds["valid"] if points and ds else None, **log_args)
 
 
-OUTPUTS = ("rgb", "mask", "depth_csv", "depth_png", "depth_npy", "pointcloud", "normals", "obj_coords")
+OUTPUTS = ("rgb", "mask", "depth_csv", "depth_png", "depth_npy", "pointcloud", "normals", "obj_coords",
+           "pointcloud_ply", "depth16_png")
 # What the reference writes for every frame (GDP:1668-1771, 2055-2072): RGB PNG, depth CSV and
 # JET depth PNG, point-cloud TXT, instance mask .npy; the label JSON is always written (it is the
 # resume marker).
@@ -84,9 +90,12 @@ REFERENCE_OUTPUTS = ("rgb", "mask", "depth_csv", "depth_png", "pointcloud")
 
 # outputs encoded on the GPU in thread mode -> their csg_outputs.file_kinds kind (_lib.FILE_KINDS)
 FILE_OF_OUTPUT = (("rgb", "rgb_png"), ("depth_csv", "depth_csv"), ("depth_png", "depth_png"),
-                  ("pointcloud", "pointcloud_txt"))
+                  ("pointcloud", "pointcloud_txt"), ("pointcloud_ply", "pointcloud_ply"),
+                  ("depth16_png", "depth16_png"))
 _PATHS = {"rgb": ("rgb", "rgb_{:06d}.png"), "depth_csv": ("depth", "depth_{:06d}.csv"),
-          "depth_png": ("depth", "depth_{:06d}.png"), "pointcloud": ("pointcloud", "pointcloud_{:06d}.txt")}
+          "depth_png": ("depth", "depth_{:06d}.png"), "pointcloud": ("pointcloud", "pointcloud_{:06d}.txt"),
+          "pointcloud_ply": ("pointcloud", "pointcloud_{:06d}.ply"), "depth16_png": ("depth", "depth16_{:06d}.png")}
+_ENCODED_KIND = {"pointcloud": "encoded_pointcloud", "pointcloud_ply": "encoded_ply"}   # writer_pool.write_frame
 
 
 def file_path(out_dir: str, output: str, frame: int) -> str:
@@ -118,7 +127,8 @@ def render_outputs(outs: set, gpu_files: bool, host_depth: bool, occlusion: bool
                 + (["normals"] if "normals" in outs else []) + (["obj_coords"] if "obj_coords" in outs else []))
     else:
         want = (["rgb", "instance", "keypoints", "stats"] + (["depth"] if host_depth else [])
-                + (["depth_vis"] if "depth_png" in outs else []) + (["points"] if "pointcloud" in outs else [])
+                + (["depth_vis"] if "depth_png" in outs else [])
+                + (["points"] if outs & {"pointcloud", "pointcloud_ply"} else [])
                 + (["normals"] if "normals" in outs else []) + (["obj_coords"] if "obj_coords" in outs else []))
     return want + (["covered"] if occlusion else [])
 
@@ -129,7 +139,8 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
              resume: bool = True, normals: bool = False, outputs: Optional[tuple] = None,
              writer_mode: str = "thread", renderers: int = 0, object_list: str = "visible",
              occlusion: bool = False, sink: str = "disk", validate_pointcloud: bool = False,
-             min_points: int = 100, max_retries: int = 5, prep_workers: int = -1) -> dict:
+             min_points: int = 100, max_retries: int = 5, prep_workers: int = -1,
+             depth16_counts_per_metre: float = 250.0) -> dict:
     """Render ``frames`` on one GPU and write them (``outputs``, default the
     reference's set; ``depth`` / ``depth_csv`` / ``pointcloud`` / ``normals``
     add the depth .npy, the depth .npy + CSV, the point cloud, the normals).
@@ -155,6 +166,8 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
     rendered again from a jittered camera (Workload.camera's ``attempt``,
     GDP:1573-1581), up to ``max_retries`` attempts in all (GDP:60); a frame
     that fails them all is logged failed and writes no files (GDP:1662-1666).
+    ``depth16_counts_per_metre``: the scale of the "depth16_png" output
+    (default 250: 4 mm steps, 262.1 m range; recorded in depth/depth16.json).
     ``prep_workers``: processes that prepare batches ahead (epoch layouts,
     object poses, cameras; prep_pool.py), so that numpy work does not hold
     this process's GIL; -1 = two for runs of at least 20 batches, else none."""
@@ -181,6 +194,12 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                          "lo": box[0].tolist() if box else None, "hi": box[1].tolist() if box else None})
         with open(os.path.join(out_dir, "obj_coords", "objects.json"), "w") as fh:
             json.dump({"objects": objs}, fh, indent=2)
+    if "depth16_png" in outs:   # what a reader needs to turn the samples back into metres
+        s16 = float(depth16_counts_per_metre)
+        if not (np.isfinite(s16) and s16 > 0):
+            raise ValueError(f"depth16_counts_per_metre {depth16_counts_per_metre!r}: a finite number > 0")
+        with open(os.path.join(out_dir, "depth", "depth16.json"), "w") as fh:
+            json.dump({"counts_per_metre": s16, "invalid": 0}, fh)
     if resume:
         frames = [f for f in frames if not os.path.exists(os.path.join(out_dir, "labels", f"label_{f:06d}.json"))]
     # batch preparation in worker processes, started (like the writer processes
@@ -199,7 +218,7 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
     kinds = tuple(k for o, k in FILE_OF_OUTPUT if o in outs) if gpu_files else ()
     # host depth for its own files; the quality log's depth counts come from
     # the GPU (depth_stats) in thread mode, from the host depth otherwise
-    host_depth = "depth_npy" in outs or (not gpu_files and bool(outs & {"depth_csv", "pointcloud"}))
+    host_depth = "depth_npy" in outs or (not gpu_files and bool(outs & {"depth_csv", "pointcloud", "depth16_png"}))
     log = QualityLog(os.path.join(out_dir, "logs"))
     want = render_outputs(outs, gpu_files, host_depth, occlusion)
     if validate_pointcloud and "depth_stats" not in want:
@@ -222,7 +241,8 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
     r = rends[0]
     if gpu_files:   # page-locked slots, and buffers for the encoded files (an estimate, grown on demand)
         npx = wl.width * wl.height
-        est = {"rgb_png": 2 * npx, "depth_csv": 10 * npx, "depth_png": npx, "pointcloud_txt": 48 * npx}
+        est = {"rgb_png": 2 * npx, "depth_csv": 10 * npx, "depth_png": npx, "pointcloud_txt": 48 * npx,
+               "pointcloud_ply": 15 * npx + 256, "depth16_png": 2 * npx}
         pool.use_pinned(r.host_buffer, batch * sum(est[k] for k in kinds) + (1 << 20) if kinds else 0,
                         free=r.free_host_buffer)
     nk = len(kinds)
@@ -231,6 +251,7 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
     lw = LabelWriter(wl.kp_table, wl.intr.params(), scene_labels(wl.scene), wl.height, wl.width) if gpu_files else None
     pose_cache = {}
     pending = []
+    has_points = bool(outs & {"pointcloud", "pointcloud_ply"})   # the quality log's point count
 
     def cov_of(out, k):   # the frame's label coverage (occlusion_ratio), when rendered
         return out["label_covered"][k] if "label_covered" in out else None
@@ -300,7 +321,8 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
             fr = make_frames(views, projs, sets, fb)
             if kinds:
                 outs_b = {k: v[:len(fb)] for k, v in arrays.items() if k not in ("files", "file_offsets")}
-                out, offsets, need = r.render_files(fr, kinds, arrays["files"], want=want, out=outs_b)
+                out, offsets, need = r.render_files(fr, kinds, arrays["files"], want=want, out=outs_b,
+                                                    depth16_counts_per_metre=depth16_counts_per_metre)
                 if offsets is None:   # the files did not fit: a larger buffer, no re-render
                     offsets = r.copy_files(pool.grow_files(slot, need + need // 4, alloc=r.host_buffer,
                                                            free=r.free_host_buffer), len(fb) * nk)
@@ -393,8 +415,7 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                 if kinds:   # GPU-encoded: file j = frame * nk + index of its kind
                     for o, kd in FILE_OF_OUTPUT:
                         if o in outs:
-                            files.append((file_path(out_dir, o, f),
-                                          "encoded_pointcloud" if o == "pointcloud" else "encoded",
+                            files.append((file_path(out_dir, o, f), _ENCODED_KIND.get(o, "encoded"),
                                           (k * nk + kinds.index(kd),)))
                 elif "rgb" in outs:
                     files.append((file_path(out_dir, "rgb", f), "png", ("rgb",)))
@@ -408,6 +429,11 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                     files.append((file_path(out_dir, "depth_png", f), "png", ("depth_vis",)))
                 if "pointcloud" in outs and not kinds:
                     files.append((file_path(out_dir, "pointcloud", f), "pointcloud", ("points", "rgb")))
+                if "pointcloud_ply" in outs and not kinds:
+                    files.append((file_path(out_dir, "pointcloud_ply", f), "ply", ("points", "rgb")))
+                if "depth16_png" in outs and not kinds:
+                    files.append((file_path(out_dir, "depth16_png", f), "depth16", ("depth",),
+                                  float(depth16_counts_per_metre)))
                 if "normals" in outs:
                     files.append((os.path.join(out_dir, "normals", f"normals_{f:06d}.npy"), "npy", ("normals",)))
                 if "obj_coords" in outs:
@@ -419,9 +445,9 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
             t_labels += time.time() - tl
             # log frames in order as they complete
             while pending and pending[0][0].done():
-                _log_done(log, *pending.pop(0), "pointcloud" in outs)
+                _log_done(log, *pending.pop(0), has_points)
         for p in pending:
-            _log_done(log, *p, "pointcloud" in outs)
+            _log_done(log, *p, has_points)
         t_done = time.time()   # every file written (teardown below: freeing page-locked buffers)
     finally:
         ahead.shutdown(wait=True)
@@ -488,6 +514,8 @@ def main(argv=None):
                          "(the reference's enable_pointcloud_validation, off by default there too)")
     ap.add_argument("--min-points", type=int, default=100, help="point-cloud validation threshold (GDP:59)")
     ap.add_argument("--max-retries", type=int, default=5, help="validation attempts per frame (GDP:60)")
+    ap.add_argument("--depth16-counts-per-metre", type=float, default=250.0,
+                    help="scale of the depth16_png output (default 250: 4 mm steps, 262.1 m range)")
     ap.add_argument("--prep-workers", type=int, default=-1,
                     help="processes preparing batches ahead (-1: two for runs of >= 20 batches)")
     a = ap.parse_args(argv)
@@ -498,7 +526,7 @@ def main(argv=None):
                        outputs=parse_outputs(a.outputs), writer_mode=a.writer_mode, renderers=a.renderers,
                        object_list=a.object_list, occlusion=a.occlusion, sink=a.sink,
                        validate_pointcloud=a.validate_pointcloud, min_points=a.min_points, max_retries=a.max_retries,
-                       prep_workers=a.prep_workers)
+                       prep_workers=a.prep_workers, depth16_counts_per_metre=a.depth16_counts_per_metre)
     print(json.dumps(summary))
 
 

@@ -273,9 +273,13 @@ class Renderer:
         raise CsgError("free_host_buffer: not a buffer of this renderer")
 
     def render_files(self, frames: np.ndarray, kinds: Sequence[str], files: np.ndarray,
-                     want: Iterable[str] = (), out: Optional[Dict[str, np.ndarray]] = None):
+                     want: Iterable[str] = (), out: Optional[Dict[str, np.ndarray]] = None,
+                     depth16_counts_per_metre: float = 0.0):
         """Render a batch (at most ``max_frames``) and encode ``kinds`` (of
-        ``_lib.FILE_KINDS``: "rgb_png", "depth_csv", "depth_png", "pointcloud_txt") on the GPU
+        ``_lib.FILE_KINDS``: "rgb_png", "depth_csv", "depth_png", "pointcloud_txt",
+        "pointcloud_ply", "depth16_png") on the GPU.  ``depth16_counts_per_metre``
+        is the scale of "depth16_png" (0: ``_lib.DEPTH16_COUNTS_PER_METRE``; the
+        quantiser is ``writers.depth_to_u16``).  The files go
         into ``files`` (uint8 host array, pinned from :meth:`host_buffer` for
         speed), growing nothing: returns (outputs dict as :meth:`render`,
         offsets) with file j = frame * len(kinds) + k (kinds in bit order) at
@@ -312,6 +316,7 @@ class Renderer:
                 setattr(oo, key, arr.ctypes.data)
         oo.n_labels, oo.on_device = self.n_labels, 0
         oo.file_kinds, oo.files, oo.files_cap, oo.file_offsets = mask, files.ctypes.data, files.nbytes, offsets.ctypes.data
+        oo.depth16_counts_per_metre = float(depth16_counts_per_metre)
         rc = self.lib.csg_render_batch(self.ctx, frames.ctypes.data, n, C.byref(oo))
         if rc == _lib.ERR_CAPACITY:
             return out, None, int(offsets[-1])

@@ -76,15 +76,15 @@ def write_frame(arrays: Dict[str, np.ndarray], k: int, files: List[Tuple[str, st
                 label: dict, label_path: str, sink: str = "disk") -> Optional[dict]:
     """Every file of frame ``k`` of a batch, then its label JSON (the resume
     marker, GDP:1357-1367 scans labels/).  ``files`` = (path, kind, array
-    names); kind "encoded" names the file index j in the batch's files
+    names[, a parameter of the kind: the counts per metre of "depth16"]); kind "encoded" names the file index j in the batch's files
     encoded on the GPU (arrays "files" + "file_offsets"); ``label`` is the
     label dict, or a callable that writes the label file to the path it is
     given (writers.LabelWriter); returns the frame's depth counts for the
     quality log.  ``sink`` "discard": every file goes to /dev/null."""
     from . import writers as fileio
     from .labels import label_json_bytes
-    for path, kind, keys in files:
-        if kind in ("encoded", "encoded_pointcloud"):
+    for path, kind, keys, *param in files:
+        if kind in ("encoded", "encoded_pointcloud", "encoded_ply"):
             off = arrays["file_offsets"]
             j = keys[0]
             data = arrays["files"][int(off[j]):int(off[j + 1])]
@@ -93,10 +93,14 @@ def write_frame(arrays: Dict[str, np.ndarray], k: int, files: List[Tuple[str, st
             # GDP:723-725; the depth fallback saves only len(xyzrgb) > 0, :1755)
             if kind == "encoded_pointcloud" and len(data) <= len(POINTCLOUD_HEADER):
                 continue
+            if kind == "encoded_ply" and len(data) <= len(fileio.ply_header(0)):   # the same rule: only a header
+                continue
             _atomic(path, _write_bytes, data, sink=sink)
             continue
         a = [arrays[x][k] for x in keys]
         if kind == "pointcloud" and np.isnan(a[0]).all():   # no point: no file (GDP:723-725, :1755)
+            continue
+        if kind == "ply" and np.isnan(a[0]).any(axis=-1).all():   # the same rule: no pixel is a point
             continue
         if kind == "png":
             _atomic(path, _write_png, *a, sink=sink)
@@ -106,6 +110,10 @@ def write_frame(arrays: Dict[str, np.ndarray], k: int, files: List[Tuple[str, st
             _atomic(path, fileio.write_depth_csv, *a, sink=sink)
         elif kind == "pointcloud":
             _atomic(path, fileio.write_pointcloud_txt, *a, sink=sink)
+        elif kind == "ply":
+            _atomic(path, fileio.write_pointcloud_ply, *a, sink=sink)
+        elif kind == "depth16":
+            _atomic(path, fileio.write_depth16_png, *a, *param, sink=sink)
         else:
             raise ValueError(kind)
     if callable(label):   # a native label writer job (writers.LabelWriter.write bound to the frame)

@@ -106,6 +106,85 @@ def write_pointcloud_txt(path: str, points: np.ndarray, rgb: np.ndarray) -> None
            "write_pointcloud_txt", path)
 
 
+# -- the compact kinds (no reference counterpart): binary PLY, 16-bit depth PNG ------
+PLY_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+assert PLY_DTYPE.itemsize == 15
+
+
+def ply_header(n: int) -> bytes:
+    """Header of a binary PLY of ``n`` points (CSG_FILE_POINTCLOUD_PLY, include/csg_api.h)."""
+    return (b"ply\nformat binary_little_endian 1.0\nelement vertex %d\n"
+            b"property float x\nproperty float y\nproperty float z\n"
+            b"property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % n)
+
+
+def pointcloud_ply_bytes(points: np.ndarray, rgb: np.ndarray) -> bytes:
+    p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    c = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)
+    assert p.shape == c.shape
+    keep = ~np.isnan(p).any(axis=1)   # the TXT writer's rule: a point has no NaN in x, y, z
+    rec = np.empty(int(keep.sum()), PLY_DTYPE)
+    # (bit copies: the float fields are assigned as uint32 views, so -0.0 and NaN payloads survive)
+    bits = p[keep].view(np.uint32)
+    for k, name in enumerate(("x", "y", "z")):
+        rec[name].view(np.uint32)[...] = bits[:, k]
+    for k, name in enumerate(("red", "green", "blue")):
+        rec[name] = c[keep, k]
+    return ply_header(rec.shape[0]) + rec.tobytes()
+
+
+def write_pointcloud_ply(path: str, points: np.ndarray, rgb: np.ndarray) -> None:
+    """The point cloud as a binary PLY, 15 bytes per point: ``points`` (..., 3)
+    float32 world xyz (NaN = no hit), ``rgb`` (..., 3) uint8; row-major."""
+    with open(path, "wb") as fh:
+        fh.write(pointcloud_ply_bytes(points, rgb))
+
+
+def depth_to_u16(depth: np.ndarray, counts_per_metre: float = 250.0) -> np.ndarray:
+    """The 16-bit depth sample of CSG_FILE_DEPTH16_PNG, in float32 throughout:
+    0 where the depth is not finite or <= 0; else t = d * s (rounded to
+    float32), 65535 where t >= 65535, else the integer part of t + 0.5
+    (rounded to float32).  A valid depth below half a count reads 0 like "no
+    hit"; depths beyond 65535 / s saturate."""
+    d = np.asarray(depth, np.float32)
+    s = np.float32(counts_per_metre)
+    ok = np.isfinite(d) & (d > 0)
+    with np.errstate(over="ignore", invalid="ignore"):
+        t = np.where(ok, d, np.float32(0)) * s
+        sat = t >= np.float32(65535)
+        v = (np.where(sat, np.float32(0), t) + np.float32(0.5)).astype(np.uint32)
+    return np.where(sat, 65535, v).astype(np.uint16)
+
+
+def _png_chunk(tag: bytes, data: bytes) -> bytes:
+    import struct
+    import zlib
+    return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+
+
+def depth16_png_bytes(u16: np.ndarray, level: int = 1) -> bytes:
+    """A 16-bit greyscale PNG (bit depth 16, colour type 0) of an (H, W) uint16
+    array: filter Sub on every row (distance 2 bytes), one IDAT chunk."""
+    import struct
+    import zlib
+    a = np.ascontiguousarray(u16, np.uint16)
+    assert a.ndim == 2, a.shape
+    H, W = a.shape
+    raw = a.astype(">u2").view(np.uint8).reshape(H, 2 * W)
+    filt = np.empty((H, 2 * W + 1), np.uint8)
+    filt[:, 0] = 1
+    filt[:, 1:3] = raw[:, :2]
+    filt[:, 3:] = raw[:, 2:] - raw[:, :-2]
+    return (b"\x89PNG\r\n\x1a\n" + _png_chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 16, 0, 0, 0, 0))
+            + _png_chunk(b"IDAT", zlib.compress(filt.tobytes(), level)) + _png_chunk(b"IEND", b""))
+
+
+def write_depth16_png(path: str, depth: np.ndarray, counts_per_metre: float = 250.0) -> None:
+    """``depth`` (H, W) float32 metres as a 16-bit PNG at ``counts_per_metre`` (:func:`depth_to_u16`)."""
+    with open(path, "wb") as fh:
+        fh.write(depth16_png_bytes(depth_to_u16(depth, counts_per_metre)))
+
+
 class LabelWriter:
     """Label files written natively (csgio_write_label_json, GIL released):
     byte-identical to ``save_label_json(label_record(...))`` (labels.py) for

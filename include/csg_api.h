@@ -34,6 +34,9 @@
  *                               images, np.savetxt of the depth  :1672-1673,
  *                               and of the point cloud           :1687-1709,
  *                                                                :714-775, :1716-1757
+ *                               plus two compact kinds without a reference
+ *                               counterpart: the point cloud as a binary PLY
+ *                               and the depth as a 16-bit greyscale PNG
  *   csg_copy_files / csg_host_alloc / csg_host_free (pinned buffers for them)
  *   csg_size_work / csg_get_work_info (per-frame work-buffer caps measured
  *                               on a sample of frames; no reference counterpart:
@@ -57,7 +60,7 @@
 extern "C" {
 #endif
 
-#define CSG_ABI_VERSION 12
+#define CSG_ABI_VERSION 13
 
 typedef enum {
   CSG_OK = 0,
@@ -178,6 +181,9 @@ typedef struct {
                                 box; a posed part that leaves that box is clamped.  8-B aligned with
                                 on_device = 1.  Depth and ids it needs are rendered to internal scratch
                                 when the caller did not ask for them. */
+  float depth16_counts_per_metre; /* scale of CSG_FILE_DEPTH16_PNG: sample = depth in metres * this.  0 = the
+                                default, 250 (4 mm steps; 65535 / 250 = 262.1 m covers the default 250 m far
+                                clip).  Negative or not finite: CSG_ERR_INVALID (csg_render_batch) */
 } csg_outputs;
 
 /* csg_outputs.file_kinds */
@@ -192,6 +198,25 @@ typedef struct {
                                       header="x y z r g b", comments="") of the pixels with a point
                                       (csg_outputs.points not NaN), row-major (GDP:766-770,
                                       :1716-1757), byte-identical */
+#define CSG_FILE_POINTCLOUD_PLY 16u /* the same points as a binary PLY: the header
+                                        ply\n
+                                        format binary_little_endian 1.0\n
+                                        element vertex <N>\n            (N plain decimal)
+                                        property float x\n  property float y\n  property float z\n
+                                        property uchar red\n  property uchar green\n  property uchar blue\n
+                                        end_header\n
+                                      (one property per line, no indentation), then N records of 15 bytes:
+                                      the pixel's three float32 of csg_outputs.points as a bit copy
+                                      (little-endian; -0.0 stays -0.0) and its three RGB bytes.  A pixel is
+                                      a point under the TXT kind's rule (no NaN in x, y, z); row-major.  A
+                                      frame without a point is the header with "element vertex 0" */
+#define CSG_FILE_DEPTH16_PNG 32u   /* the depth as a 16-bit greyscale PNG (bit depth 16, colour type 0; filter
+                                      Sub at distance 2, otherwise encoded as the RGB PNG) at s =
+                                      depth16_counts_per_metre: sample v = 0 where the depth is not finite
+                                      or <= 0, else t = fl32(d * s), v = 65535 if t >= 65535, else
+                                      (uint32) fl32(t + 0.5f) (multiply and add rounded separately).  So a
+                                      valid depth below half a count reads 0 like "no hit", and depths
+                                      beyond 65535 / s saturate at 65535 */
 
 typedef struct {
   uint64_t records;          /* raster triangles emitted (all frames of the last launch chain) */

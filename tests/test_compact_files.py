@@ -1,0 +1,193 @@
+"""The compact file kinds (binary PLY point cloud, 16-bit depth PNG) on the
+host: the NumPy statement of the depth quantiser, the host writers of writer
+processes against restatements written here, and the ABI's new field.  The
+restatements and the PNG decoder below are also what the GPU encoders are held
+to (tests/test_gpu_compact_files.py)."""
+import os
+import struct
+import subprocess
+import tempfile
+import zlib
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def restate_ply(points: np.ndarray, rgb: np.ndarray) -> bytes:
+    """The PLY of include/csg_api.h (CSG_FILE_POINTCLOUD_PLY): header, then a
+    structured array of the pixels without a NaN, row-major."""
+    p = np.asarray(points, np.float32).reshape(-1, 3)
+    c = np.asarray(rgb, np.uint8).reshape(-1, 3)
+    ok = ~np.isnan(p).any(axis=1)
+    rec = np.zeros(int(ok.sum()), np.dtype({"names": ["xyz", "rgb"], "formats": [("<u4", 3), ("u1", 3)],
+                                            "offsets": [0, 12], "itemsize": 15}))
+    rec["xyz"] = p[ok].view(np.uint32)   # bit copies
+    rec["rgb"] = c[ok]
+    head = ("ply\nformat binary_little_endian 1.0\nelement vertex " + str(rec.shape[0]) + "\n"
+            "property float x\nproperty float y\nproperty float z\n"
+            "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n")
+    return head.encode("ascii") + rec.tobytes()
+
+
+def decode_png16(data: bytes) -> np.ndarray:
+    """Decode a 16-bit greyscale PNG whose rows all use filter Sub (or None):
+    every chunk's CRC and the zlib stream's Adler-32 are checked, the stream
+    must end exactly, and nothing may follow IEND.  Returns (H, W) uint16."""
+    assert data[:8] == b"\x89PNG\r\n\x1a\n"
+    pos, idat, ihdr, ended = 8, b"", None, False
+    while pos < len(data):
+        assert not ended, "bytes after IEND"
+        n, = struct.unpack(">I", data[pos:pos + 4])
+        tag, body = data[pos + 4:pos + 8], data[pos + 8:pos + 8 + n]
+        assert len(body) == n
+        crc, = struct.unpack(">I", data[pos + 8 + n:pos + 12 + n])
+        assert crc == (zlib.crc32(tag + body) & 0xFFFFFFFF), f"CRC of {tag!r} at {pos}"
+        if tag == b"IHDR":
+            ihdr = struct.unpack(">IIBBBBB", body)
+        elif tag == b"IDAT":
+            idat += body
+        elif tag == b"IEND":
+            assert n == 0
+            ended = True
+        pos += 12 + n
+    assert ended and pos == len(data) and ihdr is not None
+    W, H, depth, ctype, comp, filt, lace = ihdr
+    assert (depth, ctype, comp, filt, lace) == (16, 0, 0, 0, 0)
+    d = zlib.decompressobj()
+    raw = d.decompress(idat)          # (raises on a wrong Adler-32)
+    assert d.eof and d.unused_data == b"", "the zlib stream must end exactly at the end of the IDAT data"
+    assert zlib.adler32(raw) == struct.unpack(">I", idat[-4:])[0]
+    rows = np.frombuffer(raw, np.uint8).reshape(H, 2 * W + 1)
+    ft, px = rows[:, 0], rows[:, 1:].copy()
+    assert np.isin(ft, (0, 1)).all()
+    sub = ft == 1
+    # undo Sub at distance 2: a running sum (mod 256) over each byte lane of the 2-byte pixels
+    lanes = px[sub].reshape(-1, W, 2)
+    px[sub] = np.cumsum(lanes, axis=1, dtype=np.uint64).astype(np.uint8).reshape(-1, 2 * W)
+    return px.view(">u2").astype(np.uint16).reshape(H, W)
+
+
+def test_depth_to_u16_edge_values():
+    from constructionsceneposeestimation_amd.writers import depth_to_u16
+    d = np.array([0, -1, np.inf, np.nan, 1e-9, 0.002, 0.5, 250.0, 262.14, 262.2, 1e30], np.float32)
+    got = depth_to_u16(d, 250)
+    assert got.dtype == np.uint16
+    assert got.tolist() == [0, 0, 0, 0, 0, 1, 125, 62500, 65535, 65535, 65535]
+    # the statement itself, element by element in float32
+    rng = np.random.default_rng(5)
+    x = np.concatenate([rng.uniform(0, 300, 4000), rng.uniform(0, 0.01, 500), (np.arange(600) + 0.5) / 250.0,
+                        [-np.inf, -0.0]]).astype(np.float32)
+    for s in (250.0, 1000.0, 0.3):
+        exp = []
+        for v in x:
+            if not np.isfinite(v) or v <= 0:
+                exp.append(0)
+                continue
+            t = np.float32(v * np.float32(s))
+            exp.append(65535 if t >= 65535 else int(np.float32(t + np.float32(0.5))))
+        assert depth_to_u16(x, s).tolist() == exp, s
+    assert depth_to_u16(x.reshape(2, -1)).shape == (2, x.size // 2)
+
+
+def _cloud(n, seed=3):
+    rng = np.random.default_rng(seed)
+    p = rng.normal(0, 30, (n, 3)).astype(np.float32)
+    c = rng.integers(0, 256, (n, 3)).astype(np.uint8)
+    p[::7] = np.nan          # no hit
+    p[3, 1] = np.nan         # one NaN component: not a point either
+    p[4] = (-0.0, 0.0, -0.0)
+    p[5] = (np.inf, -np.inf, 1e-42)   # infinities and denormals are numbers
+    return p, c
+
+
+def test_write_pointcloud_ply_matches_restatement(tmp_path):
+    from constructionsceneposeestimation_amd.writers import write_pointcloud_ply
+    p, c = _cloud(1000)
+    write_pointcloud_ply(str(tmp_path / "a.ply"), p.reshape(25, 40, 3), c.reshape(25, 40, 3))
+    got = open(tmp_path / "a.ply", "rb").read()
+    assert got == restate_ply(p, c)
+    n = int((~np.isnan(p).any(axis=1)).sum())
+    assert b"element vertex %d\n" % n in got and got.endswith(c[-1].tobytes())
+    body = got[got.index(b"end_header\n") + 11:]
+    assert len(body) == 15 * n
+    assert body[15 * 2:15 * 2 + 12] == np.array([-0.0, 0.0, -0.0], "<f4").tobytes()   # row 4 is the 3rd point
+    # no point at all: the header alone
+    z = np.full((6, 3), np.nan, np.float32)
+    write_pointcloud_ply(str(tmp_path / "z.ply"), z, np.zeros((6, 3), np.uint8))
+    got = open(tmp_path / "z.ply", "rb").read()
+    assert got == restate_ply(z, np.zeros((6, 3), np.uint8)) and b"element vertex 0\n" in got
+    assert got.endswith(b"end_header\n")
+
+
+def test_write_depth16_png_roundtrip(tmp_path):
+    from constructionsceneposeestimation_amd.writers import depth_to_u16, write_depth16_png
+    rng = np.random.default_rng(11)
+    for (H, W) in ((37, 301), (5, 1), (64, 64)):
+        d = rng.uniform(0.2, 270.0, (H, W)).astype(np.float32)
+        d[rng.random((H, W)) < 0.2] = np.inf
+        d[0, 0] = np.nan
+        write_depth16_png(str(tmp_path / "d.png"), d)
+        got = decode_png16(open(tmp_path / "d.png", "rb").read())
+        assert np.array_equal(got, depth_to_u16(d, 250.0)), (H, W)
+        write_depth16_png(str(tmp_path / "e.png"), d, 1000.0)
+        assert np.array_equal(decode_png16(open(tmp_path / "e.png", "rb").read()), depth_to_u16(d, 1000.0))
+    assert (depth_to_u16(d, 1000.0) == 65535).any()
+
+
+def test_decoder_rejects_damage(tmp_path):
+    """The decoder used for the GPU files does check what it claims to."""
+    import pytest
+    from constructionsceneposeestimation_amd.writers import depth16_png_bytes
+    good = depth16_png_bytes(np.arange(600, dtype=np.uint16).reshape(20, 30) * 97)
+    assert np.array_equal(decode_png16(good), np.arange(600, dtype=np.uint16).reshape(20, 30) * 97)
+    bad = bytearray(good)
+    bad[60] ^= 1                      # inside the IDAT data: its CRC no longer matches
+    with pytest.raises(AssertionError):
+        decode_png16(bytes(bad))
+    with pytest.raises(AssertionError):
+        decode_png16(good + b"\0")    # bytes after IEND
+
+
+def test_parse_outputs_and_kinds():
+    from constructionsceneposeestimation_amd import _lib
+    from constructionsceneposeestimation_amd.generate import (FILE_OF_OUTPUT, OUTPUTS, REFERENCE_OUTPUTS, file_path,
+                                                              parse_outputs, render_outputs)
+    assert parse_outputs("rgb,mask,depth16_png,pointcloud_ply") == ("rgb", "mask", "depth16_png", "pointcloud_ply")
+    assert {"pointcloud_ply", "depth16_png"} <= set(OUTPUTS) and parse_outputs("all") == OUTPUTS
+    assert parse_outputs("reference") == REFERENCE_OUTPUTS == ("rgb", "mask", "depth_csv", "depth_png", "pointcloud")
+    assert _lib.FILE_KINDS["pointcloud_ply"] == 16 and _lib.FILE_KINDS["depth16_png"] == 32
+    assert _lib.ABI_VERSION == 13
+    # the generator lists a frame's encoded files in the ABI's bit order
+    bits = [_lib.FILE_KINDS[k] for _, k in FILE_OF_OUTPUT]
+    assert bits == sorted(bits) and len(bits) == len(_lib.FILE_KINDS)
+    assert file_path("o", "pointcloud_ply", 7) == os.path.join("o", "pointcloud", "pointcloud_000007.ply")
+    assert file_path("o", "depth16_png", 7) == os.path.join("o", "depth", "depth16_000007.png")
+    # writer processes get the arrays the host writers read; the reference set asks for nothing new
+    host = render_outputs({"pointcloud_ply", "depth16_png"}, False, True, False)
+    assert {"points", "rgb", "depth"} <= set(host)
+    assert "points" not in render_outputs({"pointcloud_ply"}, True, False, False)
+
+
+def test_header_new_field_is_last():
+    """C compiled against the header: the two kinds' bits, the ABI version, and
+    depth16_counts_per_metre as csg_outputs' last member (ctypes agrees)."""
+    import ctypes as C
+    from constructionsceneposeestimation_amd import _lib
+    prog = ('#include <stdio.h>\n#include <stddef.h>\n#include "csg_api.h"\nint main(){\n'
+            'csg_outputs o; printf("%zu %zu %zu %zu %zu %u %u %d\\n", sizeof(csg_outputs), '
+            'offsetof(csg_outputs, depth16_counts_per_metre), sizeof(o.depth16_counts_per_metre), '
+            'offsetof(csg_outputs, obj_coords), sizeof(o.obj_coords), '
+            'CSG_FILE_POINTCLOUD_PLY, CSG_FILE_DEPTH16_PNG, CSG_ABI_VERSION);\nreturn 0;}\n')
+    with tempfile.TemporaryDirectory() as d:
+        src, exe = os.path.join(d, "t.c"), os.path.join(d, "t")
+        open(src, "w").write(prog)
+        subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe], check=True)
+        size, off, fsz, off_prev, sz_prev, ply, d16, abi = map(int, subprocess.run(
+            [exe], check=True, capture_output=True, text=True).stdout.split())
+    assert (ply, d16, abi) == (16, 32, 13)
+    assert fsz == 4 and off == off_prev + sz_prev            # right behind the former last member
+    assert off + fsz <= size < off + fsz + 8                 # and nothing but padding after it
+    f = _lib.Outputs.depth16_counts_per_metre
+    assert _lib.Outputs._fields_[-1][0] == "depth16_counts_per_metre" and f.offset == off and f.size == 4
+    assert C.sizeof(_lib.Outputs) == size

@@ -34,7 +34,8 @@ def main():
             epochs = sorted({f // 10 for f in fb})
             batches.append((fb, epochs, wl.frame_params(fb)))
         r.set_keypoints(0, wl.epoch(120).keypoints)   # (the keypoint count shapes the outputs)
-        per_px = {"rgb_png": 3, "depth_csv": 12, "depth_png": 3, "pointcloud_txt": 72}   # upper estimates
+        per_px = {"rgb_png": 3, "depth_csv": 12, "depth_png": 3, "pointcloud_txt": 72, "pointcloud_ply": 16,
+                  "depth16_png": 3}   # upper estimates
         files = r.host_buffer(F * sum(per_px[k] for k in kinds) * wl.width * wl.height)
         spec = r.output_spec(F, want)
         host = {}
