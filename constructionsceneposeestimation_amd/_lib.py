@@ -27,7 +27,7 @@ EXPORTED = (
     "csg_render_batch", "csg_render_batch_async", "csg_synchronize", "csg_get_batch_stats",
     "csg_project_keypoints", "csg_timing_reset", "csg_timing_read", "csg_set_dr_light", "csg_set_dr_textures",
     "csg_instance_bounds", "csg_copy_files", "csg_host_alloc", "csg_host_free", "csg_size_work",
-    "csg_get_work_info", "csg_host_id_bytes", "csg_set_object_frames",
+    "csg_get_work_info", "csg_host_id_bytes", "csg_set_object_frames", "csg_crop_objects",
 )
 
 
@@ -99,6 +99,22 @@ class WorkInfo(C.Structure):
                 ("hinted", C.c_uint32), ("hint_retries", C.c_uint32)]
 
 
+class CropInfo(C.Structure):
+    """csg_crop_info: one crop slot (crops.CROP_INFO_DTYPE is its numpy form)."""
+    _fields_ = [("label", C.c_int32), ("pixels", C.c_uint32), ("x0", C.c_float), ("y0", C.c_float),
+                ("side", C.c_float), ("frame", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class CropJob(C.Structure):
+    """csg_crop_job (csg_crop_objects)."""
+    _fields_ = [("size", C.c_uint32), ("per_frame", C.c_uint32), ("min_pixels", C.c_uint32), ("pad", C.c_float),
+                ("explicit_boxes", C.c_int32), ("n_labels", C.c_uint32), ("rgb", C.c_void_p),
+                ("instance", C.c_void_p), ("obj_coords", C.c_void_p), ("depth", C.c_void_p),
+                ("inst_stats", C.c_void_p), ("eligible", C.c_void_p), ("crop_rgb", C.c_void_p),
+                ("crop_mask", C.c_void_p), ("crop_coords", C.c_void_p), ("crop_depth", C.c_void_p),
+                ("info", C.c_void_p)]
+
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -165,6 +181,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     lib.csg_instance_bounds.argtypes = [vp, u32, vp]
     lib.csg_size_work.argtypes = [vp, vp, u32, i32, C.c_float, C.POINTER(WorkInfo)]
     lib.csg_get_work_info.argtypes = [vp, C.POINTER(WorkInfo)]
+    lib.csg_crop_objects.argtypes = [vp, C.POINTER(CropJob), u32, vp]
     if lib.csg_abi_version() != ABI_VERSION:
         raise CsgError(f"libcsg.so ABI {lib.csg_abi_version()} != binding ABI {ABI_VERSION}; rebuild")
     _lib = lib

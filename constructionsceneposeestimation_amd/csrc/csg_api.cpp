@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/csg_api.h"
+#include "csg_crops.h"
 #include "csg_encode.h"
 #include "csg_kernels.h"
 #include "csg_widen.h"
@@ -1859,6 +1860,62 @@ int csg_instance_bounds(csg_ctx* c, uint32_t set_id, float* out) {
     const uint32_t u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
     memcpy(&out[k], &u, 4);
   }
+  return CSG_OK;
+}
+
+// Object crops: a stand-alone pass over device arrays (no scene state, no
+// work buffers), so it only validates the job and enqueues the two kernels.
+int csg_crop_objects(csg_ctx* c, const csg_crop_job* job, uint32_t n_frames, void* stream) {
+  static_assert(sizeof(CropSlot) == sizeof(csg_crop_info) && sizeof(csg_crop_info) == 32, "csg_crop_info layout");
+  static_assert(offsetof(CropSlot, side) == offsetof(csg_crop_info, side) &&
+                offsetof(CropSlot, frame) == offsetof(csg_crop_info, frame), "csg_crop_info layout");
+  if (!c) return CSG_ERR_INVALID;
+  if (!job) return c->fail(CSG_ERR_INVALID, "crop_objects: null job");
+  if (n_frames == 0) return c->fail(CSG_ERR_INVALID, "crop_objects: no frames");
+  if (job->size < 16 || job->size > 512 || (job->size & 3u))
+    return c->fail(CSG_ERR_INVALID, "crop_objects: size %u is not a multiple of 4 in 16..512", job->size);
+  if (job->per_frame < 1 || job->per_frame > 64)
+    return c->fail(CSG_ERR_INVALID, "crop_objects: per_frame %u outside 1..64", job->per_frame);
+  if (job->min_pixels < 1) return c->fail(CSG_ERR_INVALID, "crop_objects: min_pixels must be at least 1");
+  if (!std::isfinite(job->pad) || !(job->pad >= 1.0f))
+    return c->fail(CSG_ERR_INVALID, "crop_objects: pad %g is not a finite value >= 1", (double)job->pad);
+  if (!job->info) return c->fail(CSG_ERR_INVALID, "crop_objects: info is NULL");
+  if (!job->instance) return c->fail(CSG_ERR_INVALID, "crop_objects: the instance image is always needed");
+  if (job->crop_rgb && !job->rgb) return c->fail(CSG_ERR_INVALID, "crop_objects: crop_rgb needs rgb");
+  if (job->crop_coords && !job->obj_coords)
+    return c->fail(CSG_ERR_INVALID, "crop_objects: crop_coords needs obj_coords");
+  if (job->crop_depth && !job->depth) return c->fail(CSG_ERR_INVALID, "crop_objects: crop_depth needs depth");
+  if (!job->explicit_boxes && !job->inst_stats)
+    return c->fail(CSG_ERR_INVALID, "crop_objects: planning needs inst_stats (or explicit_boxes = 1)");
+  if (((uintptr_t)job->crop_rgb & 3u) || ((uintptr_t)job->crop_mask & 3u) || ((uintptr_t)job->crop_coords & 7u) ||
+      ((uintptr_t)job->crop_depth & 15u) || ((uintptr_t)job->info & 3u))
+    return c->fail(CSG_ERR_INVALID, "crop_objects: crop_rgb, crop_mask and info must be 4-byte aligned, crop_coords "
+                                    "8-byte, crop_depth 16-byte");
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+  CropArgs a{};
+  a.W = c->cfg.width;
+  a.H = c->cfg.height;
+  a.S = job->size;
+  a.K = job->per_frame;
+  a.min_pixels = job->min_pixels;
+  a.pad = job->pad;
+  a.n_labels = job->n_labels;
+  a.explicit_boxes = job->explicit_boxes ? 1 : 0;
+  a.rgb = job->rgb;
+  a.instance = job->instance;
+  a.obj_coords = job->obj_coords;
+  a.depth = job->depth;
+  a.stats = job->inst_stats;
+  a.eligible = job->eligible;
+  a.crop_rgb = job->crop_rgb;
+  a.crop_mask = job->crop_mask;
+  a.crop_coords = job->crop_coords;
+  a.crop_depth = job->crop_depth;
+  a.info = reinterpret_cast<CropSlot*>(job->info);
+  if (!a.explicit_boxes) launch_crop_plan(a, n_frames, st);
+  if (a.crop_rgb || a.crop_mask || a.crop_coords || a.crop_depth) launch_crop_sample(a, n_frames, st);
+  HIP_TRY(c, hipGetLastError());
   return CSG_OK;
 }
 

@@ -1,0 +1,44 @@
+// csg_crops.h — host launchers of the object-crop kernels (csg_crops.hip),
+// called by csg_api.cpp for csg_crop_objects.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace csg {
+
+// One crop slot: the layout of csg_crop_info (include/csg_api.h), 32 bytes.
+struct CropSlot {
+  int32_t label;
+  uint32_t pixels;
+  float x0, y0, side;
+  uint32_t frame;
+  uint32_t reserved[2];
+};
+
+// A csg_crop_job with the frame size; all pointers are device memory.
+struct CropArgs {
+  uint32_t W, H;                 // source frames
+  uint32_t S, K;                 // crop side (multiple of 4), slots per frame
+  uint32_t min_pixels;
+  float pad;
+  uint32_t n_labels;
+  int32_t explicit_boxes;
+  const uint8_t* rgb;            // [n][H][W][3]
+  const int32_t* instance;       // [n][H][W]
+  const uint16_t* obj_coords;    // [n][H][W][3]
+  const float* depth;            // [n][H][W]
+  const uint32_t* stats;         // [n][n_labels][5]
+  const uint8_t* eligible;       // [n_labels] or null
+  uint8_t* crop_rgb;             // [n][K][S][S][3]
+  uint8_t* crop_mask;            // [n][K][S][S]
+  uint16_t* crop_coords;         // [n][K][S][S][3]
+  float* crop_depth;             // [n][K][S][S]
+  CropSlot* info;                // [n][K]
+};
+
+// k_crop_plan: fills info [n][K] from the frames' label statistics.
+void launch_crop_plan(const CropArgs& a, uint32_t n, hipStream_t st);
+// k_crop_sample: resamples every slot of info into the requested images.
+void launch_crop_sample(const CropArgs& a, uint32_t n, hipStream_t st);
+
+}  // namespace csg

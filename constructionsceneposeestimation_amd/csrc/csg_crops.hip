@@ -1,0 +1,204 @@
+// csg_crops.hip — object crops (zoom-in patches) for csg_crop_objects: the
+// fixed-size patches around the largest visible objects of each frame that
+// two-stage pose networks train on, cut on the GPU from the arrays a render
+// wrote.  The arithmetic is the spec of include/csg_api.h,
+// float32 with -ffp-contract=off, restated in NumPy by tests/test_object_crops.py.
+//
+//   k_crop_plan    per frame, the K labels with the most visible pixels and
+//                  their padded square windows (deterministic top-K)
+//   k_crop_sample  per slot, S x S samples of the window: nearest for mask,
+//                  object coordinates and depth, integer-weight bilinear for RGB
+#include "csg_crops.h"
+
+#include <math.h>
+
+namespace csg {
+
+namespace {
+
+typedef uint32_t v2u32 __attribute__((ext_vector_type(2)));
+typedef uint32_t v3u32 __attribute__((ext_vector_type(3)));
+typedef float v4f32 __attribute__((ext_vector_type(4)));
+
+constexpr uint32_t kCropBlock = 256;
+
+// ---------------------------------------------------------------------------
+// k_crop_plan: one workgroup per frame, K rounds of a block arg-max over the
+// keys pixels << 32 | (0xFFFFFFFF - label): a larger key is more pixels, then
+// the lower label, so "the largest key strictly below the previous winner" is
+// the spec's order by construction -- no scratch, no atomics, and the result
+// does not depend on how threads are scheduled.  Labels are visited in a
+// strided loop (n_labels may exceed the block).  A candidate has pixels >=
+// min_pixels >= 1, so key 0 means "none", and every later slot is empty too.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kCropBlock) void k_crop_plan(CropArgs a) {
+  __shared__ unsigned long long wmax[kCropBlock / 64];
+  const uint32_t f = blockIdx.x;
+  const uint32_t* st = a.stats + (size_t)f * a.n_labels * 5;
+  CropSlot* out = a.info + (size_t)f * a.K;
+  unsigned long long prev = 0;
+  for (uint32_t k = 0; k < a.K; ++k) {
+    unsigned long long best = 0;
+    if (k == 0 || prev != 0) {   // block-uniform
+      for (uint32_t l = threadIdx.x; l < a.n_labels; l += kCropBlock) {
+        const uint32_t px = st[5 * (size_t)l];
+        if (px < a.min_pixels || (a.eligible && !a.eligible[l])) continue;
+        const unsigned long long key = ((unsigned long long)px << 32) | (0xFFFFFFFFu - l);
+        if ((k == 0 || key < prev) && key > best) best = key;
+      }
+#pragma unroll
+      for (int off = 32; off; off >>= 1) {
+        const unsigned long long o = __shfl_xor(best, off);
+        best = o > best ? o : best;
+      }
+      if ((threadIdx.x & 63u) == 0) wmax[threadIdx.x >> 6] = best;
+      __syncthreads();
+      best = 0;
+#pragma unroll
+      for (uint32_t w = 0; w < kCropBlock / 64; ++w) best = wmax[w] > best ? wmax[w] : best;
+      __syncthreads();           // wmax is rewritten by the next round
+    }
+    if (threadIdx.x == 0) {
+      CropSlot s = {-1, 0u, 0.0f, 0.0f, 0.0f, 0u, {0u, 0u}};
+      if (best) {
+        const uint32_t l = 0xFFFFFFFFu - (uint32_t)best;
+        const uint32_t* b = st + 5 * (size_t)l;
+        const uint32_t minx = b[1], miny = b[2], maxx = b[3], maxy = b[4];
+        const uint32_t w = maxx - minx + 1u, h = maxy - miny + 1u;
+        const float cx = (float)(minx + maxx + 1u) * 0.5f, cy = (float)(miny + maxy + 1u) * 0.5f;
+        const float side = a.pad * (float)(w > h ? w : h);
+        s.label = (int32_t)l;
+        s.pixels = (uint32_t)(best >> 32);
+        s.x0 = cx - side * 0.5f;
+        s.y0 = cy - side * 0.5f;
+        s.side = side;
+        s.frame = f;
+      }
+      out[k] = s;
+    }
+    prev = best;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// k_crop_sample: grid (quads of a crop / 256, K, frames); one thread makes 4
+// consecutive pixels of a crop row and stores them as k_raster and
+// k_obj_coords store theirs: RGB as three dwords, the mask as one, the
+// coordinates as three 8-B stores, the depth as one 16-B store, all
+// non-temporal (written once, never read back here).  Source reads are direct
+// global gathers: neighbouring lanes read neighbouring or identical pixels and
+// a crop's window is reused across its rows from cache.  Sample positions are
+// tested against the frame as floats before they become integers, so no window
+// (NaN, infinite or far away) yields an index outside the frame.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t rgb_tap(const uint8_t* __restrict__ fr, int x, int y, uint32_t W, uint32_t H) {
+  if ((uint32_t)x >= W || (uint32_t)y >= H) return 0u;
+  const uint8_t* p = fr + ((size_t)y * W + (uint32_t)x) * 3;
+  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+}
+
+__device__ __forceinline__ uint32_t blend(uint32_t a, uint32_t b, uint32_t c, uint32_t d, uint32_t wx, uint32_t wy,
+                                          uint32_t shift) {
+  const uint32_t top = ((a >> shift) & 255u) * (256u - wx) + ((b >> shift) & 255u) * wx;
+  const uint32_t bot = ((c >> shift) & 255u) * (256u - wx) + ((d >> shift) & 255u) * wx;
+  return (top * (256u - wy) + bot * wy + 32768u) >> 16;
+}
+
+__global__ __launch_bounds__(kCropBlock) void k_crop_sample(CropArgs a, uint32_t f0) {
+  const uint32_t S = a.S, qrow = S >> 2;
+  const uint32_t q = blockIdx.x * kCropBlock + threadIdx.x;
+  if (q >= qrow * S) return;
+  const uint32_t k = blockIdx.y, f = f0 + blockIdx.z;
+  const size_t slot = (size_t)f * a.K + k;
+  const CropSlot sl = a.info[slot];
+  const size_t o = slot * S * S + 4u * (size_t)q;   // the thread's first crop pixel
+  bool live = sl.label >= 0 && (uint32_t)sl.label < a.n_labels;
+  if (a.explicit_boxes)   // (NaN fails every comparison)
+    live = live && sl.side > 0.0f && sl.side <= 32768.0f && fabsf(sl.x0) <= 1048576.0f && fabsf(sl.y0) <= 1048576.0f;
+  if (!live) {   // block-uniform: the whole slot is zeros, its depth +inf
+    if (a.crop_rgb) __builtin_nontemporal_store(v3u32{0u, 0u, 0u}, reinterpret_cast<v3u32*>(a.crop_rgb + o * 3));
+    if (a.crop_mask) __builtin_nontemporal_store(0u, reinterpret_cast<uint32_t*>(a.crop_mask + o));
+    if (a.crop_coords) {
+#pragma unroll
+      for (int t = 0; t < 3; ++t)
+        __builtin_nontemporal_store(v2u32{0u, 0u}, reinterpret_cast<v2u32*>(a.crop_coords + o * 3 + 4 * t));
+    }
+    if (a.crop_depth)
+      __builtin_nontemporal_store(v4f32{INFINITY, INFINITY, INFINITY, INFINITY},
+                                  reinterpret_cast<v4f32*>(a.crop_depth + o));
+    return;
+  }
+  const uint32_t W = a.W, H = a.H;
+  const float fW = (float)W, fH = (float)H;
+  const size_t fpx = (size_t)f * W * H;             // the frame's first pixel
+  const uint32_t j = q / qrow, i0 = (q - j * qrow) * 4u;
+  const float step = sl.side / (float)S;
+  const float sy = sl.y0 + ((float)j + 0.5f) * step;
+  const bool yin = sy >= 0.0f && sy < fH;           // floorf(sy) in [0, H)
+  const uint32_t py = yin ? (uint32_t)floorf(sy) : 0u;
+  const float ty = sy - 0.5f;
+  const bool yv = ty >= -1.0f && ty < fH;           // a tap row may lie in the frame
+  const float yl = yv ? floorf(ty) : -2.0f;
+  const uint32_t wy = yv ? (uint32_t)(int)((ty - yl) * 256.0f) : 0u;
+  const uint8_t* rgb = a.crop_rgb ? a.rgb + fpx * 3 : nullptr;
+  uint32_t c[4] = {0u, 0u, 0u, 0u}, m = 0u, h[12];
+  float d[4];
+#pragma unroll
+  for (uint32_t t = 0; t < 4; ++t) {
+    const float sx = sl.x0 + ((float)(i0 + t) + 0.5f) * step;
+    const bool in = yin && sx >= 0.0f && sx < fW;
+    const size_t at = fpx + (size_t)py * W + (in ? (uint32_t)floorf(sx) : 0u);
+    const bool hit = in && a.instance[at] == sl.label;
+    m |= hit ? (255u << (8 * t)) : 0u;
+    h[3 * t] = h[3 * t + 1] = h[3 * t + 2] = 0u;
+    if (a.crop_coords && hit) {
+      const uint16_t* u = a.obj_coords + at * 3;
+      h[3 * t] = u[0];
+      h[3 * t + 1] = u[1];
+      h[3 * t + 2] = u[2];
+    }
+    d[t] = (a.crop_depth && hit) ? a.depth[at] : INFINITY;
+    if (rgb) {
+      const float tx = sx - 0.5f;
+      const bool xv = yv && tx >= -1.0f && tx < fW;
+      if (xv) {
+        const float xl = floorf(tx);
+        const uint32_t wx = (uint32_t)(int)((tx - xl) * 256.0f);
+        const int x = (int)xl, y = (int)yl;
+        const uint32_t p00 = rgb_tap(rgb, x, y, W, H), p10 = rgb_tap(rgb, x + 1, y, W, H);
+        const uint32_t p01 = rgb_tap(rgb, x, y + 1, W, H), p11 = rgb_tap(rgb, x + 1, y + 1, W, H);
+        c[t] = blend(p00, p10, p01, p11, wx, wy, 0) | (blend(p00, p10, p01, p11, wx, wy, 8) << 8) |
+               (blend(p00, p10, p01, p11, wx, wy, 16) << 16);
+      }
+    }
+  }
+  if (a.crop_rgb)
+    __builtin_nontemporal_store(v3u32{c[0] | (c[1] << 24), (c[1] >> 8) | (c[2] << 16), (c[2] >> 16) | (c[3] << 8)},
+                                reinterpret_cast<v3u32*>(a.crop_rgb + o * 3));
+  if (a.crop_mask) __builtin_nontemporal_store(m, reinterpret_cast<uint32_t*>(a.crop_mask + o));
+  if (a.crop_coords) {
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+      __builtin_nontemporal_store(v2u32{h[4 * t] | (h[4 * t + 1] << 16), h[4 * t + 2] | (h[4 * t + 3] << 16)},
+                                  reinterpret_cast<v2u32*>(a.crop_coords + o * 3 + 4 * t));
+  }
+  if (a.crop_depth)
+    __builtin_nontemporal_store(v4f32{d[0], d[1], d[2], d[3]}, reinterpret_cast<v4f32*>(a.crop_depth + o));
+}
+
+}  // namespace
+
+void launch_crop_plan(const CropArgs& a, uint32_t n, hipStream_t st) {
+  hipLaunchKernelGGL(k_crop_plan, dim3(n), dim3(kCropBlock), 0, st, a);
+}
+
+void launch_crop_sample(const CropArgs& a, uint32_t n, hipStream_t st) {
+  const uint32_t quads = a.S * a.S / 4u;
+  for (uint32_t f0 = 0; f0 < n; f0 += 65535u) {   // grid z limit
+    const uint32_t nf = n - f0 < 65535u ? n - f0 : 65535u;
+    hipLaunchKernelGGL(k_crop_sample, dim3((quads + kCropBlock - 1) / kCropBlock, a.K, nf), dim3(kCropBlock), 0, st, a,
+                       f0);
+  }
+}
+
+}  // namespace csg

@@ -18,6 +18,7 @@ import numpy as np
 from . import _lib
 from ._lib import CsgError
 from .camera_math import Intrinsics
+from .crops import CROP_INFO_DTYPE, DYNAMIC_KINDS, crop_intrinsics, eligible_labels
 from .labels import object_unit_transforms
 from .packing import PackedScene, light_constants, pack_scene
 from .scene.model import Scene
@@ -96,6 +97,7 @@ class Renderer:
         self.scene = scene
         self.width, self.height = int(width), int(height)
         self.max_frames = int(max_frames)
+        self.device = int(device)
         self.intr = intrinsics or Intrinsics(self.width, self.height)
         cfg = _lib.Config(device, self.width, self.height, self.max_frames, self.intr.near, self.intr.far,
                           records_per_frame, bins_per_frame, frames_per_launch)
@@ -342,6 +344,105 @@ class Renderer:
                          obj_coords or None)
         self._check(self.lib.csg_render_batch_async(self.ctx, frames_ptr, n, int(frames_on_device), C.byref(o),
                                                     stream or None), "render_batch_async")
+
+    # -- object crops -----------------------------------------------------------
+    def crop_objects(self, n: int, *, size: int, per_frame: int, min_pixels: int = 64, pad: float = 1.5,
+                     instance: int, rgb: int = 0, obj_coords: int = 0, depth: int = 0, stats: int = 0,
+                     eligible: int = 0, crop_rgb: int = 0, crop_mask: int = 0, crop_coords: int = 0,
+                     crop_depth: int = 0, info: int, explicit: bool = False, stream: int = 0,
+                     n_labels: Optional[int] = None) -> None:
+        """Enqueue the crops of ``n`` frames (csg_crop_objects; raw device
+        pointers, the counterpart of :meth:`render_into`): up to ``per_frame``
+        windows per frame resampled to ``size`` x ``size`` from the arrays a
+        render wrote (``instance`` always; ``rgb``, ``obj_coords``, ``depth``
+        for the crop image that reads them) into ``crop_rgb`` (n, K, S, S, 3)
+        uint8, ``crop_mask`` (n, K, S, S) uint8 255 / 0, ``crop_coords``
+        (n, K, S, S, 3) uint16 and ``crop_depth`` (n, K, S, S) float32.  The
+        windows are planned from ``stats`` (the render's ``inst_stats``) for
+        the labels ``eligible`` allows (a uint8 table, 0 = all) and written to
+        ``info`` (n, K) of ``crops.CROP_INFO_DTYPE``; with ``explicit`` they
+        are read from ``info`` instead.  ``n_labels`` is the length of the
+        label tables (default: the scene's).  On the stream of the render no
+        synchronisation is needed in between."""
+        job = _lib.CropJob(int(size), int(per_frame), int(min_pixels), float(pad), int(bool(explicit)),
+                           self.n_labels if n_labels is None else int(n_labels), rgb or None, instance or None,
+                           obj_coords or None, depth or None, stats or None, eligible or None, crop_rgb or None,
+                           crop_mask or None, crop_coords or None, crop_depth or None, info or None)
+        self._check(self.lib.csg_crop_objects(self.ctx, C.byref(job), int(n), stream or None), "crop_objects")
+
+    def render_crops(self, frames: np.ndarray, size: int = 128, per_frame: int = 8, min_pixels: int = 64,
+                     pad: float = 1.5, kinds: Sequence[str] = DYNAMIC_KINDS,
+                     want: Iterable[str] = ("rgb", "mask", "coords"), object_frames=None) -> Dict[str, np.ndarray]:
+        """Render ``frames`` and deliver only their object crops to the host:
+        chunks of ``max_frames`` are rendered into device tensors (torch),
+        cropped on the same stream, and the crops and their ``info`` copied to
+        page-locked host arrays; whole frames never cross PCIe.  ``want``
+        chooses among "rgb", "mask", "coords", "depth"; ``kinds`` the object
+        kinds that may be cropped (:func:`crops.eligible_labels`).  Returns
+        ``crop_rgb`` / ``crop_mask`` / ``crop_coords`` / ``crop_depth`` (those
+        wanted, shaped as :meth:`crop_objects` says), ``info`` (n, K) and
+        ``intrinsics`` (n, K, 3, 3; :func:`crops.crop_intrinsics`).
+
+        "coords" crops the ``obj_coords`` output, which needs the object-frame
+        table of every transform set the frames use (:meth:`set_object_frames`;
+        without one the coordinates are 0).  ``object_frames`` = {set id:
+        ``EpochState.object_frames``} uploads them first; otherwise nothing is
+        uploaded here."""
+        import torch
+        frames = np.ascontiguousarray(frames, FRAME_DTYPE)
+        n, S, K, H, W = frames.shape[0], int(size), int(per_frame), self.height, self.width
+        want = set(want)
+        if not want or want - {"rgb", "mask", "coords", "depth"}:
+            raise CsgError(f"render_crops: want {sorted(want)} must be a non-empty subset of rgb, mask, coords, depth")
+        for set_id, of in (object_frames or {}).items():
+            self.set_object_frames(int(set_id), of)
+        dev = torch.device("cuda", self.device)
+        m = min(n, self.max_frames)
+
+        def dbuf(cond, shape, dt):
+            return torch.empty(shape, dtype=dt, device=dev) if cond else None
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else 0
+
+        src = {"rgb": dbuf("rgb" in want, (m, H, W, 3), torch.uint8), "instance": dbuf(True, (m, H, W), torch.int32),
+               "depth": dbuf("depth" in want, (m, H, W), torch.float32),
+               "obj_coords": dbuf("coords" in want, (m, H, W, 3), torch.int16),
+               "stats": dbuf(True, (m, self.n_labels, 5), torch.int32)}
+        shapes = {"crop_rgb": ("rgb", (K, S, S, 3), torch.uint8), "crop_mask": ("mask", (K, S, S), torch.uint8),
+                  "crop_coords": ("coords", (K, S, S, 3), torch.int16), "crop_depth": ("depth", (K, S, S), torch.float32),
+                  "info": (None, (K, CROP_INFO_DTYPE.itemsize), torch.uint8)}
+        d_out = {k: dbuf(w is None or w in want, (m,) + sh, dt) for k, (w, sh, dt) in shapes.items()}
+        h_out = {k: torch.empty((n,) + sh, dtype=dt, pin_memory=True)
+                 for k, (w, sh, dt) in shapes.items() if d_out[k] is not None}
+        elig = torch.from_numpy(eligible_labels(self.scene, kinds)[:self.n_labels].copy()).to(dev)
+        stream = torch.cuda.Stream(dev)   # (the null stream's handle 0 would mean "the context's own stream")
+        stream.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(stream):
+            for s in range(0, n, self.max_frames):
+                e = min(n, s + self.max_frames)
+                self.render_into(frames[s:e].ctypes.data, e - s, False, rgb=ptr(src["rgb"]),
+                                 instance=ptr(src["instance"]), depth=ptr(src["depth"]), stats=ptr(src["stats"]),
+                                 obj_coords=ptr(src["obj_coords"]), stream=stream.cuda_stream)
+                self.crop_objects(e - s, size=S, per_frame=K, min_pixels=min_pixels, pad=pad,
+                                  instance=ptr(src["instance"]), rgb=ptr(src["rgb"]), obj_coords=ptr(src["obj_coords"]),
+                                  depth=ptr(src["depth"]), stats=ptr(src["stats"]), eligible=elig.data_ptr(),
+                                  crop_rgb=ptr(d_out["crop_rgb"]), crop_mask=ptr(d_out["crop_mask"]),
+                                  crop_coords=ptr(d_out["crop_coords"]), crop_depth=ptr(d_out["crop_depth"]),
+                                  info=ptr(d_out["info"]), stream=stream.cuda_stream)
+                for k, h in h_out.items():
+                    h[s:e].copy_(d_out[k][:e - s], non_blocking=True)
+        stream.synchronize()
+        self.synchronize()
+        out = {k: h.numpy() for k, h in h_out.items()}
+        if "crop_coords" in out:
+            out["crop_coords"] = out["crop_coords"].view(np.uint16)
+        info = out["info"].view(CROP_INFO_DTYPE).reshape(n, K)
+        # (the kernel numbers frames within a chunk: here they index `frames`)
+        info["frame"] = np.where(info["label"] >= 0, np.arange(n, dtype=np.uint32)[:, None], np.uint32(0))
+        out["info"] = info
+        out["intrinsics"] = crop_intrinsics(self.intr, info, S)
+        return out
 
     def instance_bounds(self, set_id: int = 0) -> np.ndarray:
         """(I, 2, 3) float32 world-space AABB of every instance under a transform set (GPU reduction)."""

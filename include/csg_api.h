@@ -44,6 +44,11 @@
  *   csg_host_id_bytes ......... width of the instance ids on the host wire
  *                               (int32 mask of :1909-1910 narrowed to
  *                               id + 1 bytes on PCIe, widened on the host)
+ *   csg_crop_objects .......... (new) fixed-size zoomed-in patches around the largest
+ *                               visible objects of each frame (RGB, visible mask, object
+ *                               coordinates, depth and the windows they were cut from),
+ *                               the input of two-stage pose networks; the reference
+ *                               produces none (its users crop whole frames on the host)
  *   csg_last_error / csg_destroy
  *
  * Threading: several contexts may share a device (each has its own stream
@@ -374,6 +379,83 @@ int csg_get_work_info(csg_ctx* ctx, csg_work_info* out);
  * stream completes; CSG_NARROW_IDS=0 at csg_create keeps int32 on the wire.
  * Returns the width (1, 2 or 4), or a negative status. */
 int csg_host_id_bytes(const csg_ctx* ctx);
+
+/* Object crops (zoom-in patches): for each frame, up to per_frame square
+ * windows resampled to size x size pixels from arrays a render wrote (or any
+ * arrays of the same layout); a stand-alone pass that needs no scene and no
+ * earlier render, on device memory only.  The frame size is the context's.
+ *
+ * All float arithmetic below is float32, each operation rounded once in the
+ * written order.
+ *
+ * Plan (explicit_boxes = 0), per frame: label l is a candidate iff eligible[l]
+ * != 0 (or eligible is NULL) and inst_stats[l][0] >= min_pixels.  Candidates
+ * are ordered by pixels descending, ties to the lower label; the first
+ * per_frame fill slots 0.. in that order, the other slots are empty (label -1,
+ * every other field 0).  A filled slot's window comes from the label's inclusive
+ * box minx, miny, maxx, maxy (unsigned 32-bit arithmetic): w = maxx - minx + 1,
+ * h = maxy - miny + 1, cx = (float)(minx + maxx + 1) * 0.5f, cy likewise, side =
+ * pad * (float)max(w, h), x0 = cx - side * 0.5f, y0 = cy - side * 0.5f.
+ *
+ * Explicit boxes (explicit_boxes = 1): `info` is read and never written; slot
+ * [f][k] samples frame f (its `frame` and `pixels` fields are ignored).  A slot
+ * is live iff 0 <= label < n_labels, side is finite with 0 < side <= 32768, and
+ * |x0|, |y0| are finite and <= 2^20; any other slot behaves as an empty one.
+ *
+ * Sample, for a live slot with label L, output column i, row j (S = size):
+ * step = side / (float)S, sx = x0 + ((float)i + 0.5f) * step, sy likewise.
+ * Nearest pixel px = floor(sx), py = floor(sy), `inside` iff it lies in the
+ * frame.  mask = 255 iff inside and instance[py][px] == L, else 0; coords =
+ * obj_coords[py][px] where the mask is set, else (0, 0, 0); depth =
+ * depth[py][px] where the mask is set, else +inf.  RGB is bilinear and not
+ * masked: tx = sx - 0.5f, xl = floorf(tx), wx = (int)((tx - xl) * 256.0f), and
+ * ty, yl, wy likewise; taps (xl, yl) .. (xl + 1, yl + 1), a tap outside the
+ * frame reads (0, 0, 0); per channel top = a * (256 - wx) + b * wx, bot
+ * likewise, value = (top * (256 - wy) + bot * wy + 32768) >> 16.  Empty slots
+ * write zeros to every requested image, +inf to the depth.  So a window with
+ * integer x0, y0 and side == S copies the source window exactly; windows with
+ * step > 1 alias (no area filter).
+ *
+ * No source value can make a kernel read or write outside the arrays described:
+ * every tap is checked against the frame and every label against n_labels. */
+typedef struct {            /* 32 bytes */
+  int32_t  label;           /* inst_idx of the slot's object; -1 = empty slot */
+  uint32_t pixels;          /* its visible pixels (inst_stats[.][label][0]); 0 in explicit mode */
+  float    x0, y0, side;    /* the square source window, in source pixels */
+  uint32_t frame;           /* index of the frame in the batch */
+  uint32_t reserved[2];     /* 0 */
+} csg_crop_info;
+
+typedef struct {
+  uint32_t size;            /* S: crop side, multiple of 4, 16..512 */
+  uint32_t per_frame;       /* K: slots per frame, 1..64 */
+  uint32_t min_pixels;      /* >= 1: a label needs this many visible pixels */
+  float    pad;             /* window side = pad * max(w, h) of the visible 2D box; finite, >= 1 */
+  int32_t  explicit_boxes;  /* 0: plan from inst_stats; 1: `info` is an input */
+  uint32_t n_labels;
+  /* sources, device memory, [n][H][W]...: the arrays a render wrote */
+  const uint8_t*  rgb;         /* needed iff crop_rgb */
+  const int32_t*  instance;    /* always */
+  const uint16_t* obj_coords;  /* iff crop_coords */
+  const float*    depth;       /* iff crop_depth */
+  const uint32_t* inst_stats;  /* [n][n_labels][5], iff explicit_boxes == 0 */
+  const uint8_t*  eligible;    /* [n_labels], non-zero = may be cropped; NULL = all */
+  /* outputs, device memory; any of the four images may be NULL */
+  uint8_t*  crop_rgb;          /* [n][K][S][S][3], 4-B aligned */
+  uint8_t*  crop_mask;         /* [n][K][S][S], 255 / 0, 4-B aligned */
+  uint16_t* crop_coords;       /* [n][K][S][S][3], 8-B aligned */
+  float*    crop_depth;        /* [n][K][S][S], 16-B aligned */
+  csg_crop_info* info;         /* [n][K], 4-B aligned; output, or input when explicit_boxes = 1 */
+} csg_crop_job;
+
+/* Enqueues on `stream` (a hipStream_t, NULL = the context's stream) and
+ * returns; on the stream of the render that wrote the sources it needs no
+ * synchronisation in between.  csg_synchronize waits for it when the stream is
+ * the context's or that of the context's last batch; otherwise the caller
+ * synchronises its stream.  CSG_ERR_INVALID for size, per_frame, min_pixels or
+ * pad out of range, a missing source of a requested output, a misaligned
+ * output, info NULL or n_frames == 0. */
+int csg_crop_objects(csg_ctx* ctx, const csg_crop_job* job, uint32_t n_frames, void* stream);
 
 /* Stand-alone 3D->2D projection (host buffers): uv [n][2], vis [n] without a
  * depth test (1 = in front and inside the image, 0 otherwise). */

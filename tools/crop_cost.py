@@ -1,0 +1,224 @@
+"""Cost of the object crops (csg_crop_objects: k_crop_plan + k_crop_sample).
+
+C3 at 1080p, device-resident batches of F frames (device frame records,
+device outputs, Renderer.render_into on the caller's stream), timed with HIP
+events around the enqueue, variants alternated, median of --reps after one
+warm-up of each:
+
+  render       rgb + instance + depth + stats + obj_coords (what the crops read)
+  with_crops   ... + csg_crop_objects with all four crop images, same stream
+  crops_only   csg_crop_objects alone on the arrays the last render left
+
+`with_crops - render` is the crop kernels behind a render; `crops_only` the
+same kernels timed directly.  Their own bytes are what the spec writes (14 B
+per crop pixel + 32 B per slot) plus every live window's source pixels read
+once (17 B per window pixel inside the frame: 3 rgb + 4 id + 6 coords + 4
+depth), computed from the `info` the plan wrote; the implied rate stands next
+to the ~6.3 TB/s a copy kernel reaches in HBM.  A minified window (step > 1)
+is point-sampled, not read whole, so that count overstates what such a crop
+touches; `sampled_bytes` counts what the samples ask for instead (per sample
+of a live slot 4 B id + 12 B of RGB taps, + 10 B under the mask) and
+`written_bytes` what is stored.
+
+The host leg delivers --host-frames frames to page-locked host memory two
+ways, alternated, wall clock, median of --host-reps after a warm-up: only the
+crops and `info` (Renderer.render_crops), and the whole frames a host-side
+cropper would need (rgb + instance + obj_coords through Renderer.render).
+Writes one JSON file.
+
+    python tools/crop_cost.py --frames 480 --out profiles/object_crops/cost.json
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+CROP_BYTES_PER_PIXEL = 3 + 1 + 6 + 4
+SOURCE_BYTES_PER_PIXEL = 3 + 4 + 6 + 4
+HBM_COPY_TBS = 6.3
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=480)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--size", type=int, default=128)
+    ap.add_argument("--per-frame", type=int, default=8)
+    ap.add_argument("--host-frames", type=int, default=96)
+    ap.add_argument("--host-reps", type=int, default=3)
+    ap.add_argument("--width", type=int)
+    ap.add_argument("--height", type=int)
+    ap.add_argument("--out", default=os.path.join("profiles", "object_crops", "cost.json"))
+    a = ap.parse_args()
+    import numpy as np
+    import torch
+    from constructionsceneposeestimation_amd.crops import CROP_INFO_DTYPE, eligible_labels
+    from constructionsceneposeestimation_amd.renderer import Renderer, make_frames
+    from constructionsceneposeestimation_amd.workload import Workload
+    if not torch.cuda.is_available():
+        raise SystemExit("crop_cost: needs the GPU (no CPU timing stands in for it)")
+    wl = Workload("C3", seed=0, width=a.width, height=a.height)
+    n, H, W, S, K = a.frames, wl.height, wl.width, a.size, a.per_frame
+    fids = list(range(n))
+    epochs = sorted({f // 10 for f in fids})
+    dev = torch.device("cuda", 0)
+    with Renderer(wl.scene, W, H, max_frames=n) as r:
+        for k, e in enumerate(epochs):
+            st = wl.epoch(e)
+            r.set_instance_transforms(k, st.models)
+            r.set_object_frames(k, st.object_frames)
+        V, P = wl.frame_params(fids)
+        fr = make_frames(V, P, [epochs.index(f // 10) for f in fids], fids)
+        frames_dev = torch.from_numpy(fr.view(np.uint8).copy()).to(dev)
+        r.size_work(frames_dev.data_ptr(), n, on_device=True)   # work buffers sized for these frames, as bench.py
+        rgb = torch.empty((n, H, W, 3), dtype=torch.uint8, device=dev)
+        inst = torch.empty((n, H, W), dtype=torch.int32, device=dev)
+        depth = torch.empty((n, H, W), dtype=torch.float32, device=dev)
+        oc = torch.empty((n, H, W, 3), dtype=torch.int16, device=dev)
+        stats = torch.empty((n, r.n_labels, 5), dtype=torch.int32, device=dev)
+        c_rgb = torch.empty((n, K, S, S, 3), dtype=torch.uint8, device=dev)
+        c_mask = torch.empty((n, K, S, S), dtype=torch.uint8, device=dev)
+        c_oc = torch.empty((n, K, S, S, 3), dtype=torch.int16, device=dev)
+        c_depth = torch.empty((n, K, S, S), dtype=torch.float32, device=dev)
+        info = torch.empty((n, K, CROP_INFO_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        elig = torch.from_numpy(eligible_labels(wl.scene)).to(dev)
+        stream = torch.cuda.Stream(dev)   # (the null stream's handle 0 would mean "the context's own stream")
+
+        def render():
+            r.render_into(frames_dev.data_ptr(), n, True, rgb.data_ptr(), inst.data_ptr(), depth.data_ptr(),
+                          stats=stats.data_ptr(), obj_coords=oc.data_ptr(), stream=stream.cuda_stream)
+
+        def crops():
+            r.crop_objects(n, size=S, per_frame=K, instance=inst.data_ptr(), rgb=rgb.data_ptr(),
+                           obj_coords=oc.data_ptr(), depth=depth.data_ptr(), stats=stats.data_ptr(),
+                           eligible=elig.data_ptr(), crop_rgb=c_rgb.data_ptr(), crop_mask=c_mask.data_ptr(),
+                           crop_coords=c_oc.data_ptr(), crop_depth=c_depth.data_ptr(), info=info.data_ptr(),
+                           stream=stream.cuda_stream)
+
+        variants = {"render": (render,), "with_crops": (render, crops), "crops_only": (crops,)}
+
+        def once(steps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for s in steps:
+                s()
+            e1.record(stream)
+            e1.synchronize()
+            r.synchronize()
+            return e0.elapsed_time(e1) / 1e3
+
+        for steps in variants.values():   # warm-up of every variant
+            once(steps)
+        times = {k: [] for k in variants}
+        for _ in range(a.reps):           # alternating
+            for k, steps in variants.items():
+                times[k].append(once(steps))
+        slots = info.cpu().numpy().view(CROP_INFO_DTYPE).reshape(n, K)
+        mask_share = float((c_mask != 0).float().mean().item())
+
+        del rgb, inst, depth, oc, c_rgb, c_mask, c_oc, c_depth
+        torch.cuda.empty_cache()
+
+    # -- host leg: a renderer of its own (default work buffers, host frame records) --
+    hn = min(a.host_frames, n)
+    hfr = fr[:hn]
+    with Renderer(wl.scene, W, H, max_frames=hn) as r:
+        for k, e in enumerate(epochs[:(hn - 1) // 10 + 1]):
+            st = wl.epoch(e)
+            r.set_instance_transforms(k, st.models)
+            r.set_object_frames(k, st.object_frames)
+        spec = r.output_spec(hn, ("rgb", "instance", "obj_coords"))
+        whole = {k: r.host_buffer(int(np.prod(sh)) * np.dtype(dt).itemsize).view(dt).reshape(sh)
+                 for k, (sh, dt) in spec.items()}
+
+        def host_whole():
+            t0 = time.perf_counter()
+            r.render(hfr, want=("rgb", "instance", "obj_coords"), out=whole)
+            return time.perf_counter() - t0
+
+        crop_bytes = [0]
+
+        def host_crops():
+            t0 = time.perf_counter()
+            out = r.render_crops(hfr, size=S, per_frame=K, want=("rgb", "mask", "coords", "depth"))
+            dt = time.perf_counter() - t0
+            crop_bytes[0] = sum(v.nbytes for k, v in out.items() if k != "intrinsics")
+            return dt
+
+        legs = {"whole_frames": host_whole, "crops": host_crops}
+        for fn in legs.values():
+            fn()
+        host = {k: [] for k in legs}
+        for _ in range(a.host_reps):
+            for k, fn in legs.items():
+                host[k].append(fn())
+        whole_bytes = sum(v.nbytes for v in whole.values())
+        id_wire = r.host_id_bytes()
+
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    hmed = {k: sorted(v)[len(v) // 2] for k, v in host.items()}
+    live = slots["label"] >= 0
+    # a live window's source pixels inside the frame
+    x0 = np.clip(np.floor(slots["x0"].astype(np.float64)), 0, W)
+    y0 = np.clip(np.floor(slots["y0"].astype(np.float64)), 0, H)
+    x1 = np.clip(np.ceil(slots["x0"].astype(np.float64) + slots["side"]), 0, W)
+    y1 = np.clip(np.ceil(slots["y0"].astype(np.float64) + slots["side"]), 0, H)
+    window_px = int(((x1 - x0) * (y1 - y0))[live].sum())
+    written = n * K * (S * S * CROP_BYTES_PER_PIXEL + CROP_INFO_DTYPE.itemsize)
+    own_bytes = written + window_px * SOURCE_BYTES_PER_PIXEL
+    # what the samples themselves ask for: per sample of a live slot its id and four RGB taps, plus the
+    # coordinates and depth under the mask (a point sampler touches no other pixel of a minified window)
+    masked = int(round(mask_share * n * K * S * S))
+    sampled_bytes = written + int(live.sum()) * S * S * (4 + 4 * 3) + masked * (6 + 4)
+    behind = med["with_crops"] - med["render"]
+    direct = med["crops_only"]
+    step = (slots["side"] / np.float32(S))[live]
+
+    def rate(t):
+        return round(own_bytes / t / 1e12, 3) if t > 0 else None
+
+    res = {"workload": "C3", "width": W, "height": H, "frames": n, "size": S, "per_frame": K, "min_pixels": 64, "pad": 1.5,
+           "method": f"HIP events around the enqueue on the caller's stream, device frame records and outputs, "
+                     f"variants alternated, median of {a.reps} after one warm-up each",
+           "render_s": round(med["render"], 6), "with_crops_s": round(med["with_crops"], 6),
+           "crops_only_s": round(direct, 6),
+           "runs_s": {k: [round(t, 6) for t in v] for k, v in times.items()},
+           "crops_behind_render_s": round(behind, 6), "crops_behind_render_us_per_frame": round(behind / n * 1e6, 2),
+           "crops_only_us_per_frame": round(direct / n * 1e6, 2),
+           "extra_fraction_of_render": round(behind / med["render"], 4),
+           "written_bytes": written, "window_source_pixels": window_px, "own_bytes": own_bytes,
+           "implied_tb_per_s_behind_render": rate(behind), "implied_tb_per_s_crops_only": rate(direct),
+           "hbm_copy_tb_per_s": HBM_COPY_TBS,
+           "fraction_of_hbm_copy_crops_only": round(rate(direct) / HBM_COPY_TBS, 3) if rate(direct) else None,
+           "sampled_bytes": sampled_bytes,
+           "sampled_tb_per_s_crops_only": round(sampled_bytes / direct / 1e12, 3) if direct > 0 else None,
+           "written_tb_per_s_crops_only": round(written / direct / 1e12, 3) if direct > 0 else None,
+           "mean_live_slots_per_frame": round(float(live.sum(1).mean()), 3),
+           "frames_with_all_slots_live": int((live.sum(1) == K).sum()),
+           "step_min_median_max": [round(float(v), 3) for v in (step.min(), np.median(step), step.max())],
+           "minified_share_of_live_slots": round(float((step > 1).mean()), 4),
+           "mask_pixel_share": round(mask_share, 4),
+           "host_leg": {"frames": hn,
+                        "method": f"wall clock of synchronous calls into page-locked host memory, alternated, median of "
+                                  f"{a.host_reps} after one warm-up each",
+                        "whole_frames_outputs": ["rgb", "instance", "obj_coords"],
+                        "whole_frames_s": round(hmed["whole_frames"], 6), "crops_s": round(hmed["crops"], 6),
+                        "runs_s": {k: [round(t, 6) for t in v] for k, v in host.items()},
+                        "whole_frames_per_s": round(hn / hmed["whole_frames"], 1),
+                        "crops_frames_per_s": round(hn / hmed["crops"], 1),
+                        "speedup": round(hmed["whole_frames"] / hmed["crops"], 3),
+                        "whole_host_bytes_per_frame": whole_bytes // hn, "instance_id_wire_bytes": id_wire,
+                        "crops_host_bytes_per_frame": crop_bytes[0] // hn}}
+    if os.path.dirname(a.out):
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()
