@@ -12,7 +12,7 @@ from typing import Optional
 PKG = os.path.dirname(os.path.abspath(__file__))
 # CSG_LIB names an alternative build of the same ABI (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("CSG_LIB") or os.path.join(PKG, "libcsg.so")
-ABI_VERSION = 13  # CSG_ABI_VERSION in include/csg_api.h
+ABI_VERSION = 14  # CSG_ABI_VERSION in include/csg_api.h
 KEEP_TEXTURE = -2  # CSG_KEEP_TEXTURE
 COVERED_UNKNOWN = 0x80000000  # csg_outputs.label_covered flag: a tile held more than 32 labels
 ERR_CAPACITY = -6  # CSG_ERR_CAPACITY
@@ -27,7 +27,7 @@ EXPORTED = (
     "csg_render_batch", "csg_render_batch_async", "csg_synchronize", "csg_get_batch_stats",
     "csg_project_keypoints", "csg_timing_reset", "csg_timing_read", "csg_set_dr_light", "csg_set_dr_textures",
     "csg_instance_bounds", "csg_copy_files", "csg_host_alloc", "csg_host_free", "csg_size_work",
-    "csg_get_work_info", "csg_host_id_bytes", "csg_set_object_frames", "csg_crop_objects",
+    "csg_get_work_info", "csg_host_id_bytes", "csg_set_object_frames", "csg_crop_objects", "csg_encode_files",
 )
 
 
@@ -115,6 +115,14 @@ class CropJob(C.Structure):
                 ("info", C.c_void_p)]
 
 
+class EncodeJob(C.Structure):
+    """csg_encode_job (csg_encode_files)."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n_frames", C.c_uint32), ("file_kinds", C.c_uint32),
+                ("rgb", C.c_void_p), ("depth_vis", C.c_void_p), ("depth", C.c_void_p), ("points", C.c_void_p),
+                ("depth16_counts_per_metre", C.c_float), ("files", C.c_void_p), ("files_cap", C.c_uint64),
+                ("file_offsets", C.c_void_p), ("depth_stats", C.c_void_p)]
+
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -182,6 +190,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     lib.csg_size_work.argtypes = [vp, vp, u32, i32, C.c_float, C.POINTER(WorkInfo)]
     lib.csg_get_work_info.argtypes = [vp, C.POINTER(WorkInfo)]
     lib.csg_crop_objects.argtypes = [vp, C.POINTER(CropJob), u32, vp]
+    lib.csg_encode_files.argtypes = [vp, C.POINTER(EncodeJob)]
     if lib.csg_abi_version() != ABI_VERSION:
         raise CsgError(f"libcsg.so ABI {lib.csg_abi_version()} != binding ABI {ABI_VERSION}; rebuild")
     _lib = lib

@@ -1313,11 +1313,25 @@ static int copy_files(csg_ctx* c, uint8_t* dst, uint64_t cap, uint64_t* offsets)
   return CSG_OK;
 }
 
-// The files of a rendered batch (csg_outputs.file_kinds), encoded on the GPU
-// from the images still in HBM (csg_encode.hip): sizes first, then one
-// synchronisation to size the buffers, then the bytes, then one D2H copy.
-static int encode_files(csg_ctx* c, const csg_outputs* out, uint32_t F) {
-  const uint32_t fk = out->file_kinds;
+// What encode_files reads and where its bytes go: the device images of the
+// kinds asked for and their frame size -- the rendered batch's
+// (csg_render_batch) or a caller's (csg_encode_files).
+struct EncSrc {
+  uint32_t W, H, file_kinds;
+  const uint8_t* rgb;
+  const uint8_t* dvis;
+  const float* depth;
+  const float* points;
+  uint8_t* files;
+  uint64_t files_cap;
+  uint64_t* file_offsets;
+};
+
+// The files of a batch of images in HBM (csg_outputs.file_kinds), encoded on
+// the GPU (csg_encode.hip): sizes first, then one synchronisation to size the
+// buffers, then the bytes, then one D2H copy.
+static int encode_files(csg_ctx* c, const EncSrc& src, uint32_t F) {
+  const uint32_t fk = src.file_kinds;
   uint32_t nk = 0, slot_rgb = 0, slot_csv = 0, slot_dpng = 0, slot_pcd = 0, slot_ply = 0, slot_d16 = 0;
   if (fk & CSG_FILE_RGB_PNG) slot_rgb = nk++;
   if (fk & CSG_FILE_DEPTH_CSV) slot_csv = nk++;
@@ -1325,7 +1339,7 @@ static int encode_files(csg_ctx* c, const csg_outputs* out, uint32_t F) {
   if (fk & CSG_FILE_POINTCLOUD_TXT) slot_pcd = nk++;
   if (fk & CSG_FILE_POINTCLOUD_PLY) slot_ply = nk++;
   if (fk & CSG_FILE_DEPTH16_PNG) slot_d16 = nk++;
-  const uint32_t W = c->cfg.width, H = c->cfg.height, n_files = F * nk;
+  const uint32_t W = src.W, H = src.H, n_files = F * nk;
   hipStream_t st = c->stream;
   const size_t rows = (size_t)F * png_units_per_frame(W, H), csv_rows = (size_t)F * csv_units_per_frame(W, H);
   HIP_TRY(c, c->enc_fsize.alloc(n_files));
@@ -1336,34 +1350,34 @@ static int encode_files(csg_ctx* c, const csg_outputs* out, uint32_t F) {
   if (fk & CSG_FILE_RGB_PNG) {
     HIP_TRY(c, c->enc_rgb.alloc(F));
     HIP_TRY(c, c->enc_rows_rgb.alloc(rows));
-    launch_png_sizes(c->last_rgb, W, H, F, c->enc_rgb.p, c->enc_rowsum.p, c->enc_rows_rgb.p, c->enc_fsize.p, nk,
+    launch_png_sizes(src.rgb, W, H, F, c->enc_rgb.p, c->enc_rowsum.p, c->enc_rows_rgb.p, c->enc_fsize.p, nk,
                      slot_rgb, st);
   }
   if (fk & CSG_FILE_DEPTH_PNG) {
     HIP_TRY(c, c->enc_dpng.alloc(F));
     HIP_TRY(c, c->enc_rows_dpng.alloc(rows));
-    launch_png_sizes(c->last_dvis, W, H, F, c->enc_dpng.p, c->enc_rowsum.p, c->enc_rows_dpng.p, c->enc_fsize.p, nk,
+    launch_png_sizes(src.dvis, W, H, F, c->enc_dpng.p, c->enc_rowsum.p, c->enc_rows_dpng.p, c->enc_fsize.p, nk,
                      slot_dpng, st);
   }
   if (fk & CSG_FILE_DEPTH_CSV) {
     HIP_TRY(c, c->enc_rows_csv.alloc(csv_rows));
-    launch_csv_sizes(c->last_depth, W, H, F, c->enc_rows_csv.p, c->enc_fsize.p, nk, slot_csv, st);
+    launch_csv_sizes(src.depth, W, H, F, c->enc_rows_csv.p, c->enc_fsize.p, nk, slot_csv, st);
   }
   if (fk & CSG_FILE_POINTCLOUD_TXT) {
     HIP_TRY(c, c->enc_rows_pcd.alloc(csv_rows));
-    launch_pcd_sizes(c->last_points, c->last_rgb, W, H, F, c->enc_rows_pcd.p, c->enc_fsize.p, nk, slot_pcd, st);
+    launch_pcd_sizes(src.points, src.rgb, W, H, F, c->enc_rows_pcd.p, c->enc_fsize.p, nk, slot_pcd, st);
   }
   if (fk & CSG_FILE_POINTCLOUD_PLY) {
     HIP_TRY(c, c->enc_rows_ply.alloc(csv_rows));
     HIP_TRY(c, c->enc_ply_n.alloc(F));
-    launch_ply_sizes(c->last_points, W, H, F, c->enc_rows_ply.p, c->enc_ply_n.p, c->enc_fsize.p, nk, slot_ply, st);
+    launch_ply_sizes(src.points, W, H, F, c->enc_rows_ply.p, c->enc_ply_n.p, c->enc_fsize.p, nk, slot_ply, st);
   }
   if (fk & CSG_FILE_DEPTH16_PNG) {
     const size_t npx = (size_t)F * W * H;
     HIP_TRY(c, c->enc_d16.alloc(F));
     HIP_TRY(c, c->enc_rows_d16.alloc((size_t)F * png_units_per_frame(W, H, 2)));
     HIP_TRY(c, c->enc_d16img.alloc(2 * npx));
-    launch_depth16(c->last_depth, npx, c->depth16_scale, c->enc_d16img.p, st);
+    launch_depth16(src.depth, npx, c->depth16_scale, c->enc_d16img.p, st);
     launch_png_sizes(c->enc_d16img.p, W, H, F, c->enc_d16.p, c->enc_rowsum.p, c->enc_rows_d16.p, c->enc_fsize.p, nk,
                      slot_d16, st, 2);
   }
@@ -1384,18 +1398,18 @@ static int encode_files(csg_ctx* c, const csg_outputs* out, uint32_t F) {
     HIP_TRY(c, hipMemsetAsync(c->enc_zbuf.p, 0, ztotal, st));
   }
   if (pa)
-    launch_png_emit(c->last_rgb, W, H, F, pa, c->enc_rows_rgb.p, c->enc_zbuf.p, c->enc_zoff.p, c->enc_out.p,
+    launch_png_emit(src.rgb, W, H, F, pa, c->enc_rows_rgb.p, c->enc_zbuf.p, c->enc_zoff.p, c->enc_out.p,
                     c->enc_foff.p, nk, slot_rgb, st);
   if (pb)
-    launch_png_emit(c->last_dvis, W, H, F, pb, c->enc_rows_dpng.p, c->enc_zbuf.p, c->enc_zoff.p + F, c->enc_out.p,
+    launch_png_emit(src.dvis, W, H, F, pb, c->enc_rows_dpng.p, c->enc_zbuf.p, c->enc_zoff.p + F, c->enc_out.p,
                     c->enc_foff.p, nk, slot_dpng, st);
   if (fk & CSG_FILE_DEPTH_CSV)
-    launch_csv_emit(c->last_depth, W, H, F, c->enc_rows_csv.p, c->enc_out.p, c->enc_foff.p, nk, slot_csv, st);
+    launch_csv_emit(src.depth, W, H, F, c->enc_rows_csv.p, c->enc_out.p, c->enc_foff.p, nk, slot_csv, st);
   if (fk & CSG_FILE_POINTCLOUD_TXT)
-    launch_pcd_emit(c->last_points, c->last_rgb, W, H, F, c->enc_rows_pcd.p, c->enc_out.p, c->enc_foff.p, nk, slot_pcd,
+    launch_pcd_emit(src.points, src.rgb, W, H, F, c->enc_rows_pcd.p, c->enc_out.p, c->enc_foff.p, nk, slot_pcd,
                     st);
   if (fk & CSG_FILE_POINTCLOUD_PLY)
-    launch_ply_emit(c->last_points, c->last_rgb, W, H, F, c->enc_rows_ply.p, c->enc_ply_n.p, c->enc_out.p,
+    launch_ply_emit(src.points, src.rgb, W, H, F, c->enc_rows_ply.p, c->enc_ply_n.p, c->enc_out.p,
                     c->enc_foff.p, nk, slot_ply, st);
   if (pc)
     launch_png_emit(c->enc_d16img.p, W, H, F, pc, c->enc_rows_d16.p, c->enc_zbuf.p, c->enc_zoff.p + 2 * (size_t)F,
@@ -1403,7 +1417,19 @@ static int encode_files(csg_ctx* c, const csg_outputs* out, uint32_t F) {
   HIP_TRY(c, hipGetLastError());
   c->enc_total = total;
   c->enc_nfiles = n_files;
-  return copy_files(c, out->files, out->files_cap, out->file_offsets);
+  return copy_files(c, src.files, src.files_cap, src.file_offsets);
+}
+
+// The checks csg_render_batch and csg_encode_files share: known kinds, and the
+// 16-bit depth scale (kept in the context for encode_files).
+static int check_file_request(csg_ctx* c, const char* who, uint32_t fk, float s) {
+  if (fk & ~(CSG_FILE_RGB_PNG | CSG_FILE_DEPTH_CSV | CSG_FILE_DEPTH_PNG | CSG_FILE_POINTCLOUD_TXT |
+             CSG_FILE_POINTCLOUD_PLY | CSG_FILE_DEPTH16_PNG))
+    return c->fail(CSG_ERR_INVALID, "%s: unknown file kinds %#x", who, fk);
+  if (!(s >= 0.0f) || !(s < INFINITY))
+    return c->fail(CSG_ERR_INVALID, "%s: depth16_counts_per_metre must be finite and >= 0 (0: the default, 250)", who);
+  c->depth16_scale = s == 0.0f ? 250.0f : s;
+  return CSG_OK;
 }
 
 int csg_render_batch(csg_ctx* c, const csg_frame* frames, uint32_t n_frames, const csg_outputs* out) {
@@ -1412,15 +1438,10 @@ int csg_render_batch(csg_ctx* c, const csg_frame* frames, uint32_t n_frames, con
   // an earlier asynchronous batch that overflowed is reported, not lost
   int rc = csg_synchronize(c);
   if (rc) return rc;
-  if (out && (out->file_kinds & ~(CSG_FILE_RGB_PNG | CSG_FILE_DEPTH_CSV | CSG_FILE_DEPTH_PNG | CSG_FILE_POINTCLOUD_TXT |
-                                  CSG_FILE_POINTCLOUD_PLY | CSG_FILE_DEPTH16_PNG)))
-    return c->fail(CSG_ERR_INVALID, "render: unknown file kinds %#x", out->file_kinds);
   const uint32_t fk = out ? out->file_kinds : 0u;
   if (out) {
-    const float s = out->depth16_counts_per_metre;
-    if (!(s >= 0.0f) || !(s < INFINITY))
-      return c->fail(CSG_ERR_INVALID, "render: depth16_counts_per_metre must be finite and >= 0 (0: the default, 250)");
-    c->depth16_scale = s == 0.0f ? 250.0f : s;
+    rc = check_file_request(c, "render", fk, out->depth16_counts_per_metre);
+    if (rc) return rc;
   }
   for (int attempt = 0; attempt < 6; ++attempt) {
     rc = enqueue_batch(c, frames, n_frames, 0, out, c->stream, fk);
@@ -1428,7 +1449,12 @@ int csg_render_batch(csg_ctx* c, const csg_frame* frames, uint32_t n_frames, con
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     uint32_t ov = 0;
     HIP_TRY(c, hipMemcpy(&ov, c->overflow.p, 4, hipMemcpyDeviceToHost));
-    if (!ov) return fk ? encode_files(c, out, n_frames) : CSG_OK;
+    if (!ov) {
+      if (!fk) return CSG_OK;
+      const EncSrc src{c->cfg.width, c->cfg.height, fk, c->last_rgb, c->last_dvis, c->last_depth, c->last_points,
+                       out->files, out->files_cap, out->file_offsets};
+      return encode_files(c, src, n_frames);
+    }
     HIP_TRY(c, hipMemsetAsync(c->overflow.p, 0, 4, c->stream));   // before the re-render, on its stream
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (ov & (kOvBadSet | kOvBadKpSet))   // host frames are validated before launch: cannot happen
@@ -1490,6 +1516,44 @@ int csg_copy_files(csg_ctx* c, uint8_t* dst, uint64_t cap, uint64_t* offsets) {
   if (!c->enc_nfiles) return c->fail(CSG_ERR_INVALID, "copy_files: no batch with files rendered");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   return copy_files(c, dst, cap, offsets);
+}
+
+// The encoder passes on a caller's device arrays: csg_render_batch's own code
+// path (encode_files, launch_depth_stats) with the job's sources and size.
+int csg_encode_files(csg_ctx* c, const csg_encode_job* job) {
+  if (!c) return CSG_ERR_INVALID;
+  if (!job) return c->fail(CSG_ERR_INVALID, "encode_files: null job");
+  const uint32_t fk = job->file_kinds, W = job->width, H = job->height, F = job->n_frames;
+  if (W == 0 || H == 0 || W > 8192 || H > 8192)
+    return c->fail(CSG_ERR_INVALID, "encode_files: %u x %u is not a frame size in 1..8192", W, H);
+  if (F == 0) return c->fail(CSG_ERR_INVALID, "encode_files: no frames");
+  int rc = check_file_request(c, "encode_files", fk, job->depth16_counts_per_metre);
+  if (rc) return rc;
+  if (!fk && !job->depth_stats) return c->fail(CSG_ERR_INVALID, "encode_files: no file kind and no depth_stats asked for");
+  if ((fk & (CSG_FILE_RGB_PNG | CSG_FILE_POINTCLOUD_TXT | CSG_FILE_POINTCLOUD_PLY)) && !job->rgb)
+    return c->fail(CSG_ERR_INVALID, "encode_files: the RGB PNG and the point-cloud kinds need rgb");
+  if ((fk & CSG_FILE_DEPTH_PNG) && !job->depth_vis) return c->fail(CSG_ERR_INVALID, "encode_files: the depth PNG needs depth_vis");
+  if (((fk & (CSG_FILE_DEPTH_CSV | CSG_FILE_DEPTH16_PNG)) || job->depth_stats) && !job->depth)
+    return c->fail(CSG_ERR_INVALID, "encode_files: the depth CSV, the 16-bit depth PNG and depth_stats need depth");
+  if ((fk & (CSG_FILE_POINTCLOUD_TXT | CSG_FILE_POINTCLOUD_PLY)) && !job->points)
+    return c->fail(CSG_ERR_INVALID, "encode_files: the point-cloud kinds need points");
+  if (((uintptr_t)job->depth & 3u) || ((uintptr_t)job->points & 3u))
+    return c->fail(CSG_ERR_INVALID, "encode_files: depth and points must be 4-byte aligned");
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  rc = csg_synchronize(c);
+  if (rc) return rc;
+  if (job->depth_stats) {   // before the files: a too-small files buffer still delivers them
+    HIP_TRY(c, c->dstat_part.alloc(depth_stats_scratch_bytes(F)));
+    HIP_TRY(c, c->o_dstats.alloc((size_t)F * 6));
+    launch_depth_stats(job->depth, W * H, F, c->dstat_part.p, c->o_dstats.p, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(job->depth_stats, c->o_dstats.p, sizeof(double) * 6 * F, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  if (!fk) return CSG_OK;
+  const EncSrc src{W, H, fk, job->rgb, job->depth_vis, job->depth, job->points, job->files, job->files_cap,
+                   job->file_offsets};
+  return encode_files(c, src, F);
 }
 
 int csg_host_alloc(csg_ctx* c, uint64_t bytes, void** out) {

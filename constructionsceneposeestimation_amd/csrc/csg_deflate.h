@@ -30,7 +30,8 @@ constexpr int kMaxBits = 15;          // deflate code length limit
 constexpr int kMaxClBits = 7;         // code-length code limit
 constexpr uint32_t kEob = 256;
 constexpr uint32_t kIdatBytes = 2048; // zlib bytes per IDAT chunk (one CRC, one GPU thread per chunk)
-constexpr uint32_t kMaxHeaderWords = 160;   // 2 zlib bytes + block header bits (< 4,800 bits)
+constexpr uint32_t kSegBytes = 512;   // raw bytes of an image row per work unit; units are tokenised on their own
+constexpr uint32_t kMaxHeaderWords = 160;  // 2 zlib bytes + block header bits (< 4,800 bits)
 constexpr uint32_t kAdlerMod = 65521;
 
 // Match length 3..258 -> symbol 257..285, extra-bit count and value (RFC 1951 3.2.5).

@@ -58,7 +58,7 @@ namespace {
 constexpr int kRowsPerBlock = 64;   // one wave of units per workgroup (one frame per workgroup)
 // Work units: segments of rows, so that a batch offers tens of thousands of
 // threads (one thread per 1080p row left the GPU mostly idle).
-constexpr uint32_t kSegBytes = 512;  // PNG: raw row bytes per unit
+// (PNG: kSegBytes raw row bytes per unit, csg_deflate.h)
 constexpr uint32_t kSegVals = 64;    // CSV: values per unit
 
 // rb: raw bytes of an image row, bytes per pixel * W

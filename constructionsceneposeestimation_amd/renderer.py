@@ -333,6 +333,43 @@ class Renderer:
                     "copy_files")
         return offsets
 
+    def encode_files(self, n: int, width: int, height: int, kinds, files: Optional[np.ndarray], *, rgb: int = 0,
+                     depth_vis: int = 0, depth: int = 0, points: int = 0, depth16_counts_per_metre: float = 0.0,
+                     depth_stats: bool = False):
+        """Encode ``kinds`` from device arrays the caller supplies
+        (csg_encode_files; raw device pointers, e.g. torch ``data_ptr()``) of
+        ``n`` frames of ``width`` x ``height`` -- any size, not the
+        renderer's: ``rgb`` and ``depth_vis`` (n, H, W, 3) uint8 at any
+        alignment, ``depth`` (n, H, W) and ``points`` (n, H, W, 3) float32.
+        ``kinds`` are names of ``_lib.FILE_KINDS`` or a CSG_FILE_* bit mask.
+        Synchronous, on the renderer's stream: the arrays must be complete.
+        Returns ``(offsets, need)`` as :meth:`render_files` does (``None``
+        offsets when ``files`` was too small: :meth:`copy_files`), and with
+        ``depth_stats`` a third item, the (n, 6) float64 statistics."""
+        if isinstance(kinds, (int, np.integer)):
+            mask = int(kinds)
+        else:
+            mask = 0
+            for k in kinds:
+                if k not in _lib.FILE_KINDS:
+                    raise CsgError(f"unknown file kind {k!r}; choose from {tuple(_lib.FILE_KINDS)}")
+                mask |= _lib.FILE_KINDS[k]
+        if files is None:
+            files = np.zeros(0, np.uint8)
+        if files.dtype != np.uint8 or not files.flags.c_contiguous:
+            raise CsgError("encode_files: files must be a C-contiguous uint8 array")
+        n = int(n)
+        offsets = np.zeros(n * bin(mask).count("1") + 1, np.uint64)
+        stats = np.zeros((n, 6), np.float64) if depth_stats else None
+        job = _lib.EncodeJob(int(width), int(height), n, mask, rgb or None, depth_vis or None, depth or None,
+                             points or None, float(depth16_counts_per_metre), files.ctypes.data if files.size else None,
+                             files.nbytes, offsets.ctypes.data, stats.ctypes.data if depth_stats else None)
+        rc = self.lib.csg_encode_files(self.ctx, C.byref(job))
+        if rc != _lib.ERR_CAPACITY:
+            self._check(rc, "encode_files")
+        res = (None if rc else offsets, int(offsets[-1]))
+        return res + (stats,) if depth_stats else res
+
     def render_into(self, frames_ptr: int, n: int, frames_on_device: bool, rgb: int = 0, instance: int = 0,
                     depth: int = 0, kp_uv: int = 0, kp_vis: int = 0, stats: int = 0, stream: int = 0,
                     normals: int = 0, points: int = 0, depth_vis: int = 0, depth_range: int = 0,

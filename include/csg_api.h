@@ -38,6 +38,8 @@
  *                               counterpart: the point cloud as a binary PLY
  *                               and the depth as a 16-bit greyscale PNG
  *   csg_copy_files / csg_host_alloc / csg_host_free (pinned buffers for them)
+ *   csg_encode_files .......... (new) the same encoders on device arrays the
+ *                               caller supplies, at the job's own frame size
  *   csg_size_work / csg_get_work_info (per-frame work-buffer caps measured
  *                               on a sample of frames; no reference counterpart:
  *                               Kit sizes its own render buffers)
@@ -65,7 +67,7 @@
 extern "C" {
 #endif
 
-#define CSG_ABI_VERSION 13
+#define CSG_ABI_VERSION 14
 
 typedef enum {
   CSG_OK = 0,
@@ -317,6 +319,38 @@ int csg_instance_bounds(csg_ctx* ctx, uint32_t set_id, float* out);
  * (after CSG_ERR_CAPACITY): dst host memory of cap bytes; offsets as
  * csg_outputs.file_offsets (may be NULL). */
 int csg_copy_files(csg_ctx* ctx, uint8_t* dst, uint64_t cap, uint64_t* offsets);
+/* The file encoders on device arrays the caller supplies instead of a rendered
+ * batch's: the same passes csg_render_batch runs for csg_outputs.file_kinds
+ * and csg_outputs.depth_stats, so any array of the layouts below -- a render's
+ * outputs kept in HBM, or synthetic data -- becomes the same files.  The frame
+ * size is the job's, not the context's (1..8192 each way); n_frames is not
+ * bound by max_frames (the encoders' scratch grows with the job).  Files and
+ * offsets are laid out as csg_outputs says: file j = frame * n_kinds + k.
+ *
+ * Synchronous: waits for the context's earlier work (as csg_synchronize, whose
+ * errors it returns), runs on the context's stream and returns with `files`
+ * and `depth_stats` written.  The caller's arrays must be complete before the
+ * call (work on other streams is not waited for).  CSG_ERR_INVALID for a NULL
+ * source of a requested kind (see the members), a zero or too large
+ * dimension, n_frames == 0, an unknown kind, a depth16_counts_per_metre that
+ * is negative or not finite, depth or points off 4-byte alignment, or nothing
+ * asked for.  CSG_ERR_CAPACITY when files_cap is too small: file_offsets holds
+ * the sizes and csg_copy_files fetches the bytes, as after csg_render_batch
+ * (depth_stats is written in that case too). */
+typedef struct {
+  uint32_t width, height, n_frames, file_kinds;  /* file_kinds: CSG_FILE_* (0: depth_stats only) */
+  const uint8_t* rgb;        /* [n][H][W][3], any alignment: RGB_PNG, POINTCLOUD_TXT, POINTCLOUD_PLY */
+  const uint8_t* depth_vis;  /* [n][H][W][3], any alignment: DEPTH_PNG */
+  const float* depth;        /* [n][H][W]: DEPTH_CSV, DEPTH16_PNG, depth_stats */
+  const float* points;       /* [n][H][W][3]: POINTCLOUD_TXT, POINTCLOUD_PLY */
+  float depth16_counts_per_metre;  /* as csg_outputs' */
+  uint8_t* files;            /* host, files_cap bytes */
+  uint64_t files_cap;
+  uint64_t* file_offsets;    /* host, n_frames * n_kinds + 1 */
+  double* depth_stats;       /* host [n][6] as csg_outputs.depth_stats, or NULL */
+} csg_encode_job;
+int csg_encode_files(csg_ctx* ctx, const csg_encode_job* job);
+
 /* Page-locked host memory for csg_outputs.files and the other host outputs. */
 int csg_host_alloc(csg_ctx* ctx, uint64_t bytes, void** out);
 int csg_host_free(csg_ctx* ctx, void* p);

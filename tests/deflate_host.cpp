@@ -2,9 +2,13 @@
 // encoders: a one-thread PNG writer built from the same helpers as
 // csg_encode.hip (row tokens, Huffman lengths, canonical codes, header, Adler,
 // CRC) and the "%.6f" formatter.  Built and run by tests/test_deflate_host.py;
-// not part of the product.
+// not part of the product.  The PNG writer splits rows into the GPU's work
+// units (kSegBytes raw bytes, tokenised on their own), so its file is the one
+// the GPU must produce, byte for byte (tests/test_gpu_encoders.py).
 //
-//   deflate_host png  W H in.rgb out.png       8-bit RGB image -> PNG
+//   deflate_host png  W H in.raw out.png [bpp] raw image -> PNG; bpp 3 (default): 8-bit RGB,
+//                                              2: 16-bit grey, big-endian samples
+//   deflate_host zlen W H in.raw [bpp]         prints the length of that PNG's zlib stream
 //   deflate_host csv  W H in.f32 out.csv       float32 image -> "%.6f" text
 //   deflate_host huff maxbits freq...          code lengths of a histogram
 #include <stdio.h>
@@ -62,15 +66,18 @@ struct Bits {
   }
 };
 
+// The filtered stream of unit k of a row of rb raw bytes (filter Sub at
+// distance bpp; the filter-type byte leads unit 0).
 template <class F>
-static void row_stream(const uint8_t* row, uint32_t W, F&& push) {
-  push(1u);
-  for (uint32_t i = 0; i < 3 * W; ++i) push((uint32_t)(row[i] - (i >= 3 ? row[i - 3] : 0)) & 255u);
+static void unit_stream(const uint8_t* row, uint32_t rb, uint32_t bpp, uint32_t k, F&& push) {
+  if (k == 0) push(1u);
+  const uint32_t j1 = (k + 1) * kSegBytes < rb ? (k + 1) * kSegBytes : rb;
+  for (uint32_t j = k * kSegBytes; j < j1; ++j) push((uint32_t)(row[j] - (j >= bpp ? row[j - bpp] : 0)) & 255u);
 }
 
-static int png(uint32_t W, uint32_t H, const char* in, const char* outp) {
-  std::vector<uint8_t> img = read_file(in);
-  if (img.size() != (size_t)W * H * 3) return 2;
+// The zlib stream of the image (H rows of rb = bpp * W raw bytes).
+static std::vector<uint8_t> zlib_stream(const std::vector<uint8_t>& img, uint32_t W, uint32_t H, uint32_t bpp) {
+  const uint32_t rb = bpp * W, U = (rb + kSegBytes - 1) / kSegBytes;
   uint32_t hist[kLitCodes] = {0};
   auto lit_h = [&](uint32_t b) { ++hist[b]; };
   auto match_h = [&](uint32_t len) {
@@ -80,15 +87,17 @@ static int png(uint32_t W, uint32_t H, const char* in, const char* outp) {
   };
   uint32_t a = 1, b = 0;
   for (uint32_t r = 0; r < H; ++r) {
-    RunTokenizer<decltype(lit_h)&, decltype(match_h)&> tok{lit_h, match_h};
-    uint64_t ra = 0, rb = 0;
-    row_stream(&img[(size_t)r * W * 3], W, [&](uint32_t x) {
-      ra += x;
-      rb += ra;
-      tok.push(x);
-    });
-    tok.finish();
-    adler_cat(a, b, (uint32_t)(ra % kAdlerMod), (uint32_t)(rb % kAdlerMod), 3ull * W + 1);
+    uint64_t ra = 0, rs = 0;
+    for (uint32_t k = 0; k < U; ++k) {
+      RunTokenizer<decltype(lit_h)&, decltype(match_h)&> tok{lit_h, match_h};
+      unit_stream(&img[(size_t)r * rb], rb, bpp, k, [&](uint32_t x) {
+        ra += x;
+        rs += ra;
+        tok.push(x);
+      });
+      tok.finish();
+    }
+    adler_cat(a, b, (uint32_t)(ra % kAdlerMod), (uint32_t)(rs % kAdlerMod), (uint64_t)rb + 1);
   }
   hist[kEob] = 1;
   std::vector<uint16_t> sym;
@@ -136,15 +145,23 @@ static int png(uint32_t W, uint32_t H, const char* in, const char* outp) {
     z.put(ex, ne);
     z.put(0, 1);
   };
-  for (uint32_t r = 0; r < H; ++r) {
-    RunTokenizer<decltype(lit_e)&, decltype(match_e)&> t{lit_e, match_e};
-    row_stream(&img[(size_t)r * W * 3], W, [&](uint32_t x) { t.push(x); });
-    t.finish();
-  }
+  for (uint32_t r = 0; r < H; ++r)
+    for (uint32_t k = 0; k < U; ++k) {
+      RunTokenizer<decltype(lit_e)&, decltype(match_e)&> t{lit_e, match_e};
+      unit_stream(&img[(size_t)r * rb], rb, bpp, k, [&](uint32_t x) { t.push(x); });
+      t.finish();
+    }
   z.put(code[kEob] & 0xFFFFu, code[kEob] >> 16);
   z.align();
   const uint32_t adl = (b << 16) | a;
   for (int k = 3; k >= 0; --k) z.out.push_back((uint8_t)(adl >> (8 * k)));
+  return z.out;
+}
+
+static int png(uint32_t W, uint32_t H, const char* in, const char* outp, uint32_t bpp) {
+  std::vector<uint8_t> img = read_file(in);
+  if ((bpp != 2 && bpp != 3) || img.size() != (size_t)W * H * bpp) return 2;
+  const std::vector<uint8_t> zs = zlib_stream(img, W, H, bpp);
   // PNG container
   uint32_t T[256];
   for (uint32_t k = 0; k < 256; ++k) T[k] = crc_entry(k);
@@ -166,11 +183,12 @@ static int png(uint32_t W, uint32_t H, const char* in, const char* outp) {
     be(c ^ 0xFFFFFFFFu);
   };
   const uint8_t ihdr[13] = {(uint8_t)(W >> 24), (uint8_t)(W >> 16), (uint8_t)(W >> 8), (uint8_t)W,
-                            (uint8_t)(H >> 24), (uint8_t)(H >> 16), (uint8_t)(H >> 8), (uint8_t)H, 8, 2, 0, 0, 0};
+                            (uint8_t)(H >> 24), (uint8_t)(H >> 16), (uint8_t)(H >> 8), (uint8_t)H,
+                            (uint8_t)(bpp == 2 ? 16 : 8), (uint8_t)(bpp == 2 ? 0 : 2), 0, 0, 0};
   chunk("IHDR", ihdr, 13);
-  for (size_t o = 0; o < z.out.size(); o += kIdatBytes) {
-    const uint32_t n = (uint32_t)(z.out.size() - o < kIdatBytes ? z.out.size() - o : kIdatBytes);
-    chunk("IDAT", &z.out[o], n);
+  for (size_t o = 0; o < zs.size(); o += kIdatBytes) {
+    const uint32_t n = (uint32_t)(zs.size() - o < kIdatBytes ? zs.size() - o : kIdatBytes);
+    chunk("IDAT", &zs[o], n);
   }
   chunk("IEND", nullptr, 0);
   FILE* fo = fopen(outp, "wb");
@@ -199,7 +217,15 @@ static int csv(uint32_t W, uint32_t H, const char* in, const char* outp) {
 }
 
 int main(int argc, char** argv) {
-  if (argc >= 6 && !strcmp(argv[1], "png")) return png((uint32_t)atoi(argv[2]), (uint32_t)atoi(argv[3]), argv[4], argv[5]);
+  if (argc >= 6 && !strcmp(argv[1], "png"))
+    return png((uint32_t)atoi(argv[2]), (uint32_t)atoi(argv[3]), argv[4], argv[5], argc >= 7 ? (uint32_t)atoi(argv[6]) : 3u);
+  if (argc >= 5 && !strcmp(argv[1], "zlen")) {
+    const uint32_t W = (uint32_t)atoi(argv[2]), H = (uint32_t)atoi(argv[3]), bpp = argc >= 6 ? (uint32_t)atoi(argv[5]) : 3u;
+    const std::vector<uint8_t> img = read_file(argv[4]);
+    if ((bpp != 2 && bpp != 3) || img.size() != (size_t)W * H * bpp) return 2;
+    printf("%zu\n", zlib_stream(img, W, H, bpp).size());
+    return 0;
+  }
   if (argc >= 6 && !strcmp(argv[1], "csv")) return csv((uint32_t)atoi(argv[2]), (uint32_t)atoi(argv[3]), argv[4], argv[5]);
   if (argc >= 3 && !strcmp(argv[1], "huff")) {
     const int maxbits = atoi(argv[2]), n = argc - 3;
@@ -212,6 +238,6 @@ int main(int argc, char** argv) {
     for (int k = 0; k < n; ++k) printf("%d%c", len[k], k + 1 < n ? ' ' : '\n');
     return 0;
   }
-  fprintf(stderr, "usage: deflate_host png|csv W H in out | huff maxbits freq...\n");
+  fprintf(stderr, "usage: deflate_host png W H in out [bpp] | zlen W H in [bpp] | csv W H in out | huff maxbits freq...\n");
   return 1;
 }

@@ -157,7 +157,7 @@ def test_parse_outputs_and_kinds():
     assert {"pointcloud_ply", "depth16_png"} <= set(OUTPUTS) and parse_outputs("all") == OUTPUTS
     assert parse_outputs("reference") == REFERENCE_OUTPUTS == ("rgb", "mask", "depth_csv", "depth_png", "pointcloud")
     assert _lib.FILE_KINDS["pointcloud_ply"] == 16 and _lib.FILE_KINDS["depth16_png"] == 32
-    assert _lib.ABI_VERSION == 13
+    assert _lib.ABI_VERSION == 14
     # the generator lists a frame's encoded files in the ABI's bit order
     bits = [_lib.FILE_KINDS[k] for _, k in FILE_OF_OUTPUT]
     assert bits == sorted(bits) and len(bits) == len(_lib.FILE_KINDS)
@@ -185,7 +185,7 @@ def test_header_new_field_is_last():
         subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe], check=True)
         size, off, fsz, off_prev, sz_prev, ply, d16, abi = map(int, subprocess.run(
             [exe], check=True, capture_output=True, text=True).stdout.split())
-    assert (ply, d16, abi) == (16, 32, 13)
+    assert (ply, d16, abi) == (16, 32, 14)
     assert fsz == 4 and off == off_prev + sz_prev            # right behind the former last member
     assert off + fsz <= size < off + fsz + 8                 # and nothing but padding after it
     f = _lib.Outputs.depth16_counts_per_metre

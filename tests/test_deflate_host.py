@@ -7,12 +7,14 @@ does not bind."""
 import heapq
 import io
 import os
+import struct
 import subprocess
 
 import numpy as np
 import pytest
 
 from pngutil import decode_png
+from test_compact_files import decode_png16
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -45,6 +47,55 @@ def test_png_roundtrip(harness, k):
     img.tofile(src)
     subprocess.run([exe, "png", str(W), str(H), src, dst], check=True)
     assert np.array_equal(decode_png(open(dst, "rb").read()), img)
+
+
+def _idat_bytes(png):
+    pos, n_idat = 8, []
+    while pos < len(png):
+        n, typ = struct.unpack(">I4s", png[pos:pos + 8])
+        if typ == b"IDAT":
+            n_idat.append(n)
+        pos += 12 + n
+    return n_idat
+
+
+@pytest.mark.parametrize("W,H", [(1, 1), (255, 3), (256, 4), (257, 5), (600, 2)])
+def test_png_16bit_grey(harness, W, H):
+    """bpp 2: big-endian 16-bit samples, Sub at distance 2; rows of 510, 512,
+    514 and 1200 bytes (one unit, exactly one, two, three)."""
+    exe, d = harness
+    rng = np.random.default_rng(W)
+    img = rng.integers(0, 65536, (H, W)).astype(np.uint16)
+    img[H // 2] = 0x1234                                   # a run through every unit boundary of the row
+    src, dst = str(d / f"g{W}.raw"), str(d / f"g{W}.png")
+    img.astype(">u2").tofile(src)
+    subprocess.run([exe, "png", str(W), str(H), src, dst, "2"], check=True)
+    png = open(dst, "rb").read()
+    assert np.array_equal(decode_png16(png), img)
+    zlen = int(subprocess.run([exe, "zlen", str(W), str(H), src, "2"], check=True, capture_output=True,
+                              text=True).stdout)
+    assert sum(_idat_bytes(png)) == zlen
+
+
+@pytest.mark.parametrize("W", [170, 171, 342, 400])
+def test_png_rows_longer_than_a_unit(harness, W):
+    """Rows of 510, 513, 1026 and 1200 bytes, units tokenised on their own
+    (runs cut at the unit boundaries): the file still decodes to the input,
+    and every IDAT chunk but the last is full."""
+    exe, d = harness
+    rng = np.random.default_rng(W)
+    img = rng.integers(0, 256, (6, W, 3), dtype=np.uint8)
+    img[1] = 200                                           # runs cut at every unit boundary
+    img[3, :, 1] = 7
+    src, dst = str(d / f"u{W}.rgb"), str(d / f"u{W}.png")
+    img.tofile(src)
+    subprocess.run([exe, "png", str(W), "6", src, dst], check=True)
+    png = open(dst, "rb").read()
+    assert np.array_equal(decode_png(png), img)
+    n_idat = _idat_bytes(png)
+    assert all(n == 2048 for n in n_idat[:-1]) and 0 < n_idat[-1] <= 2048
+    zlen = int(subprocess.run([exe, "zlen", str(W), "6", src], check=True, capture_output=True, text=True).stdout)
+    assert sum(n_idat) == zlen
 
 
 def test_csv_matches_savetxt(harness):
