@@ -14,6 +14,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CSG_LIB") or os.path.join(PKG, "libcsg.so")
 ABI_VERSION = 14  # CSG_ABI_VERSION in include/csg_api.h
 KEEP_TEXTURE = -2  # CSG_KEEP_TEXTURE
+CROP_FILTERS = {"bilinear": 0, "area": 1}  # CSG_CROP_FILTER_*: the RGB filter of csg_crop_objects_filtered
 COVERED_UNKNOWN = 0x80000000  # csg_outputs.label_covered flag: a tile held more than 32 labels
 ERR_CAPACITY = -6  # CSG_ERR_CAPACITY
 # csg_outputs.file_kinds (CSG_FILE_*): files encoded on the GPU, one per kind per frame, in bit order
@@ -28,6 +29,7 @@ EXPORTED = (
     "csg_project_keypoints", "csg_timing_reset", "csg_timing_read", "csg_set_dr_light", "csg_set_dr_textures",
     "csg_instance_bounds", "csg_copy_files", "csg_host_alloc", "csg_host_free", "csg_size_work",
     "csg_get_work_info", "csg_host_id_bytes", "csg_set_object_frames", "csg_crop_objects", "csg_encode_files",
+    "csg_crop_objects_filtered",
 )
 
 
@@ -190,6 +192,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     lib.csg_size_work.argtypes = [vp, vp, u32, i32, C.c_float, C.POINTER(WorkInfo)]
     lib.csg_get_work_info.argtypes = [vp, C.POINTER(WorkInfo)]
     lib.csg_crop_objects.argtypes = [vp, C.POINTER(CropJob), u32, vp]
+    lib.csg_crop_objects_filtered.argtypes = [vp, C.POINTER(CropJob), u32, u32, vp]
     lib.csg_encode_files.argtypes = [vp, C.POINTER(EncodeJob)]
     if lib.csg_abi_version() != ABI_VERSION:
         raise CsgError(f"libcsg.so ABI {lib.csg_abi_version()} != binding ABI {ABI_VERSION}; rebuild")

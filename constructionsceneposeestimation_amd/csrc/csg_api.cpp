@@ -1928,14 +1928,22 @@ int csg_instance_bounds(csg_ctx* c, uint32_t set_id, float* out) {
 }
 
 // Object crops: a stand-alone pass over device arrays (no scene state, no
-// work buffers), so it only validates the job and enqueues the two kernels.
+// work buffers), so it only validates the job and enqueues the kernels.
 int csg_crop_objects(csg_ctx* c, const csg_crop_job* job, uint32_t n_frames, void* stream) {
+  return csg_crop_objects_filtered(c, job, CSG_CROP_FILTER_BILINEAR, n_frames, stream);
+}
+
+int csg_crop_objects_filtered(csg_ctx* c, const csg_crop_job* job, uint32_t rgb_filter, uint32_t n_frames,
+                              void* stream) {
   static_assert(sizeof(CropSlot) == sizeof(csg_crop_info) && sizeof(csg_crop_info) == 32, "csg_crop_info layout");
   static_assert(offsetof(CropSlot, side) == offsetof(csg_crop_info, side) &&
                 offsetof(CropSlot, frame) == offsetof(csg_crop_info, frame), "csg_crop_info layout");
   if (!c) return CSG_ERR_INVALID;
   if (!job) return c->fail(CSG_ERR_INVALID, "crop_objects: null job");
   if (n_frames == 0) return c->fail(CSG_ERR_INVALID, "crop_objects: no frames");
+  if (rgb_filter != CSG_CROP_FILTER_BILINEAR && rgb_filter != CSG_CROP_FILTER_AREA)
+    return c->fail(CSG_ERR_INVALID, "crop_objects: rgb_filter %u is neither CSG_CROP_FILTER_BILINEAR nor _AREA",
+                   rgb_filter);
   if (job->size < 16 || job->size > 512 || (job->size & 3u))
     return c->fail(CSG_ERR_INVALID, "crop_objects: size %u is not a multiple of 4 in 16..512", job->size);
   if (job->per_frame < 1 || job->per_frame > 64)
@@ -1966,6 +1974,7 @@ int csg_crop_objects(csg_ctx* c, const csg_crop_job* job, uint32_t n_frames, voi
   a.pad = job->pad;
   a.n_labels = job->n_labels;
   a.explicit_boxes = job->explicit_boxes ? 1 : 0;
+  a.rgb_filter = rgb_filter;
   a.rgb = job->rgb;
   a.instance = job->instance;
   a.obj_coords = job->obj_coords;
@@ -1979,6 +1988,7 @@ int csg_crop_objects(csg_ctx* c, const csg_crop_job* job, uint32_t n_frames, voi
   a.info = reinterpret_cast<CropSlot*>(job->info);
   if (!a.explicit_boxes) launch_crop_plan(a, n_frames, st);
   if (a.crop_rgb || a.crop_mask || a.crop_coords || a.crop_depth) launch_crop_sample(a, n_frames, st);
+  if (a.rgb_filter == CSG_CROP_FILTER_AREA && a.crop_rgb) launch_crop_area(a, n_frames, st);   // behind the plan
   HIP_TRY(c, hipGetLastError());
   return CSG_OK;
 }

@@ -1,5 +1,5 @@
 // csg_crops.h — host launchers of the object-crop kernels (csg_crops.hip),
-// called by csg_api.cpp for csg_crop_objects.
+// called by csg_api.cpp for csg_crop_objects and csg_crop_objects_filtered.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -23,6 +23,7 @@ struct CropArgs {
   float pad;
   uint32_t n_labels;
   int32_t explicit_boxes;
+  uint32_t rgb_filter;           // CSG_CROP_FILTER_*: 1 = area filter for the RGB of minified windows
   const uint8_t* rgb;            // [n][H][W][3]
   const int32_t* instance;       // [n][H][W]
   const uint16_t* obj_coords;    // [n][H][W][3]
@@ -38,7 +39,10 @@ struct CropArgs {
 
 // k_crop_plan: fills info [n][K] from the frames' label statistics.
 void launch_crop_plan(const CropArgs& a, uint32_t n, hipStream_t st);
-// k_crop_sample: resamples every slot of info into the requested images.
+// k_crop_sample: resamples every slot of info into the requested images
+// (under the area filter, all but the RGB of the slots k_crop_area makes).
 void launch_crop_sample(const CropArgs& a, uint32_t n, hipStream_t st);
+// k_crop_area: the box-filtered RGB of every minified slot (rgb_filter = 1, crop_rgb set).
+void launch_crop_area(const CropArgs& a, uint32_t n, hipStream_t st);
 
 }  // namespace csg

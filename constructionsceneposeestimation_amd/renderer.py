@@ -387,8 +387,8 @@ class Renderer:
                      instance: int, rgb: int = 0, obj_coords: int = 0, depth: int = 0, stats: int = 0,
                      eligible: int = 0, crop_rgb: int = 0, crop_mask: int = 0, crop_coords: int = 0,
                      crop_depth: int = 0, info: int, explicit: bool = False, stream: int = 0,
-                     n_labels: Optional[int] = None) -> None:
-        """Enqueue the crops of ``n`` frames (csg_crop_objects; raw device
+                     n_labels: Optional[int] = None, rgb_filter: str = "bilinear") -> None:
+        """Enqueue the crops of ``n`` frames (csg_crop_objects_filtered; raw device
         pointers, the counterpart of :meth:`render_into`): up to ``per_frame``
         windows per frame resampled to ``size`` x ``size`` from the arrays a
         render wrote (``instance`` always; ``rgb``, ``obj_coords``, ``depth``
@@ -399,17 +399,24 @@ class Renderer:
         the labels ``eligible`` allows (a uint8 table, 0 = all) and written to
         ``info`` (n, K) of ``crops.CROP_INFO_DTYPE``; with ``explicit`` they
         are read from ``info`` instead.  ``n_labels`` is the length of the
-        label tables (default: the scene's).  On the stream of the render no
+        label tables (default: the scene's).  ``rgb_filter`` is "bilinear", or
+        "area" for an exact box filter over the footprint of every crop pixel
+        of a minified window (more than one source pixel per crop pixel), which
+        the bilinear taps alias.  On the stream of the render no
         synchronisation is needed in between."""
+        if rgb_filter not in _lib.CROP_FILTERS:
+            raise ValueError(f"crop_objects: rgb_filter {rgb_filter!r} is not one of {sorted(_lib.CROP_FILTERS)}")
         job = _lib.CropJob(int(size), int(per_frame), int(min_pixels), float(pad), int(bool(explicit)),
                            self.n_labels if n_labels is None else int(n_labels), rgb or None, instance or None,
                            obj_coords or None, depth or None, stats or None, eligible or None, crop_rgb or None,
                            crop_mask or None, crop_coords or None, crop_depth or None, info or None)
-        self._check(self.lib.csg_crop_objects(self.ctx, C.byref(job), int(n), stream or None), "crop_objects")
+        self._check(self.lib.csg_crop_objects_filtered(self.ctx, C.byref(job), _lib.CROP_FILTERS[rgb_filter], int(n),
+                                                       stream or None), "crop_objects")
 
     def render_crops(self, frames: np.ndarray, size: int = 128, per_frame: int = 8, min_pixels: int = 64,
                      pad: float = 1.5, kinds: Sequence[str] = DYNAMIC_KINDS,
-                     want: Iterable[str] = ("rgb", "mask", "coords"), object_frames=None) -> Dict[str, np.ndarray]:
+                     want: Iterable[str] = ("rgb", "mask", "coords"), object_frames=None,
+                     rgb_filter: str = "bilinear") -> Dict[str, np.ndarray]:
         """Render ``frames`` and deliver only their object crops to the host:
         chunks of ``max_frames`` are rendered into device tensors (torch),
         cropped on the same stream, and the crops and their ``info`` copied to
@@ -419,12 +426,16 @@ class Renderer:
         ``crop_rgb`` / ``crop_mask`` / ``crop_coords`` / ``crop_depth`` (those
         wanted, shaped as :meth:`crop_objects` says), ``info`` (n, K) and
         ``intrinsics`` (n, K, 3, 3; :func:`crops.crop_intrinsics`).
+        ``rgb_filter`` as in :meth:`crop_objects` ("area" anti-aliases the RGB
+        of minified windows).
 
         "coords" crops the ``obj_coords`` output, which needs the object-frame
         table of every transform set the frames use (:meth:`set_object_frames`;
         without one the coordinates are 0).  ``object_frames`` = {set id:
         ``EpochState.object_frames``} uploads them first; otherwise nothing is
         uploaded here."""
+        if rgb_filter not in _lib.CROP_FILTERS:
+            raise ValueError(f"render_crops: rgb_filter {rgb_filter!r} is not one of {sorted(_lib.CROP_FILTERS)}")
         import torch
         frames = np.ascontiguousarray(frames, FRAME_DTYPE)
         n, S, K, H, W = frames.shape[0], int(size), int(per_frame), self.height, self.width
@@ -466,7 +477,7 @@ class Renderer:
                                   depth=ptr(src["depth"]), stats=ptr(src["stats"]), eligible=elig.data_ptr(),
                                   crop_rgb=ptr(d_out["crop_rgb"]), crop_mask=ptr(d_out["crop_mask"]),
                                   crop_coords=ptr(d_out["crop_coords"]), crop_depth=ptr(d_out["crop_depth"]),
-                                  info=ptr(d_out["info"]), stream=stream.cuda_stream)
+                                  info=ptr(d_out["info"]), stream=stream.cuda_stream, rgb_filter=rgb_filter)
                 for k, h in h_out.items():
                     h[s:e].copy_(d_out[k][:e - s], non_blocking=True)
         stream.synchronize()

@@ -51,6 +51,8 @@
  *                               coordinates, depth and the windows they were cut from),
  *                               the input of two-stage pose networks; the reference
  *                               produces none (its users crop whole frames on the host)
+ *   csg_crop_objects_filtered . the same with an exact area filter for the RGB of
+ *                               minified windows (CSG_CROP_FILTER_AREA)
  *   csg_last_error / csg_destroy
  *
  * Threading: several contexts may share a device (each has its own stream
@@ -448,7 +450,8 @@ int csg_host_id_bytes(const csg_ctx* ctx);
  * likewise, value = (top * (256 - wy) + bot * wy + 32768) >> 16.  Empty slots
  * write zeros to every requested image, +inf to the depth.  So a window with
  * integer x0, y0 and side == S copies the source window exactly; windows with
- * step > 1 alias (no area filter).
+ * step > 1 alias (no area filter): csg_crop_objects_filtered with
+ * CSG_CROP_FILTER_AREA, below, filters their RGB.
  *
  * No source value can make a kernel read or write outside the arrays described:
  * every tap is checked against the frame and every label against n_labels. */
@@ -490,6 +493,53 @@ typedef struct {
  * pad out of range, a missing source of a requested output, a misaligned
  * output, info NULL or n_frames == 0. */
 int csg_crop_objects(csg_ctx* ctx, const csg_crop_job* job, uint32_t n_frames, void* stream);
+
+/* csg_crop_objects with a choice of RGB filter.  CSG_CROP_FILTER_BILINEAR is
+ * csg_crop_objects itself, byte for byte; CSG_CROP_FILTER_AREA replaces the RGB
+ * of minified windows by an exact box filter (what a CPU pipeline's area
+ * resampling does), so that a crop pixel averages every source pixel it stands
+ * for.  Mask, coordinates and depth are the same under either filter (labels
+ * are not blended), and so is `info`.
+ *
+ * The area filter applies to the RGB of a live slot with step = side /
+ * (float)S > 1.0f (a float32 comparison) whose window also has side <= 32768
+ * and |x0|, |y0| <= 2^20 -- every live slot of explicit boxes does; a planned
+ * window beyond those bounds keeps its bilinear RGB.  Any other slot's RGB is
+ * the bilinear RGB above, bit for bit.  It is exact integer arithmetic on
+ * float32 edges, so the result does not depend on the order of summation:
+ *
+ * Edges (float32, each operation rounded once): ex_i = x0 + (float)i * step for
+ * i = 0..S, EX_i = (int32)floorf(ex_i * 256.0f); ey_j, EY_j likewise from y0.
+ * Crop pixel (i, j) stands for the source rectangle [EX_i, EX_{i+1}) x [EY_j,
+ * EY_{j+1}) in 1/256 of a source pixel: neighbours share an edge, so the
+ * footprints tile the window.  |E| < 2^29; DX = EX_{i+1} - EX_i and DY lie in
+ * [1, 2^19 + 64] (step <= 2048, an edge rounded by at most 1/16 pixel).
+ *
+ * Weights: source column p is [256 p, 256 (p + 1)) and has weight wx_i(p) =
+ * max(0, min(EX_{i+1}, 256 (p + 1)) - max(EX_i, 256 p)), an integer in 0..256;
+ * the weights of a footprint sum to DX.  wy_j(r) likewise for source row r.
+ *
+ * Value, per channel: acc = sum_r wy_j(r) * (sum_p wx_i(p) * c[r][p]) over the
+ * pixels of the footprint, where a pixel outside the frame contributes 0 and
+ * still counts in the denominator (as a bilinear tap outside the frame reads
+ * (0, 0, 0)); value = (acc + (D >> 1)) / D with D = DX * DY in unsigned 64-bit
+ * integers.  A row sum is below 2^27, acc below 2^47, the quotient at most
+ * 255.  A pixel with DX <= 0 or DY <= 0 (which no window within the bounds
+ * above produces) is (0, 0, 0).
+ *
+ * So an image that is constant over a footprint gives that constant; a window
+ * with integer x0, y0 and step == 2 gives (a + b + c + d + 2) >> 2 of each 2x2
+ * block; and towards step == 1 the box narrows to one source pixel, whose
+ * weights are the bilinear ones, so the two filters meet without a seam.
+ *
+ * Arguments are checked as csg_crop_objects checks them; any other rgb_filter
+ * is CSG_ERR_INVALID (nothing is enqueued or written).  CSG_CROP_FILTER_AREA
+ * with crop_rgb == NULL is valid and changes nothing.  The guarantee above
+ * holds: no window and no source value yields an address outside the arrays. */
+#define CSG_CROP_FILTER_BILINEAR 0u   /* csg_crop_objects' RGB, unchanged */
+#define CSG_CROP_FILTER_AREA     1u   /* exact box filter where step > 1 */
+int csg_crop_objects_filtered(csg_ctx* ctx, const csg_crop_job* job, uint32_t rgb_filter,
+                              uint32_t n_frames, void* stream);
 
 /* Stand-alone 3D->2D projection (host buffers): uv [n][2], vis [n] without a
  * depth test (1 = in front and inside the image, 0 otherwise). */

@@ -1,4 +1,5 @@
-"""Cost of the object crops (csg_crop_objects: k_crop_plan + k_crop_sample).
+"""Cost of the object crops (csg_crop_objects_filtered: k_crop_plan +
+k_crop_sample, and k_crop_area under --rgb-filter area).
 
 C3 at 1080p, device-resident batches of F frames (device frame records,
 device outputs, Renderer.render_into on the caller's stream), timed with HIP
@@ -24,7 +25,10 @@ The host leg delivers --host-frames frames to page-locked host memory two
 ways, alternated, wall clock, median of --host-reps after a warm-up: only the
 crops and `info` (Renderer.render_crops), and the whole frames a host-side
 cropper would need (rgb + instance + obj_coords through Renderer.render).
-Writes one JSON file.
+--rgb-filter chooses the RGB filter of every crop call (bilinear, or area: the
+box filter of minified windows, which reads every source pixel of such a
+window's RGB once per band of crop rows; `area_rgb_bytes` counts those pixels
+once, 3 B each, plus the 3 B per crop pixel written).  Writes one JSON file.
 
     python tools/crop_cost.py --frames 480 --out profiles/object_crops/cost.json
 """
@@ -51,6 +55,7 @@ def main():
     ap.add_argument("--host-reps", type=int, default=3)
     ap.add_argument("--width", type=int)
     ap.add_argument("--height", type=int)
+    ap.add_argument("--rgb-filter", choices=("bilinear", "area"), default="bilinear")
     ap.add_argument("--out", default=os.path.join("profiles", "object_crops", "cost.json"))
     a = ap.parse_args()
     import numpy as np
@@ -96,7 +101,7 @@ def main():
                            obj_coords=oc.data_ptr(), depth=depth.data_ptr(), stats=stats.data_ptr(),
                            eligible=elig.data_ptr(), crop_rgb=c_rgb.data_ptr(), crop_mask=c_mask.data_ptr(),
                            crop_coords=c_oc.data_ptr(), crop_depth=c_depth.data_ptr(), info=info.data_ptr(),
-                           stream=stream.cuda_stream)
+                           stream=stream.cuda_stream, rgb_filter=a.rgb_filter)
 
         variants = {"render": (render,), "with_crops": (render, crops), "crops_only": (crops,)}
 
@@ -143,7 +148,8 @@ def main():
 
         def host_crops():
             t0 = time.perf_counter()
-            out = r.render_crops(hfr, size=S, per_frame=K, want=("rgb", "mask", "coords", "depth"))
+            out = r.render_crops(hfr, size=S, per_frame=K, want=("rgb", "mask", "coords", "depth"),
+                                 rgb_filter=a.rgb_filter)
             dt = time.perf_counter() - t0
             crop_bytes[0] = sum(v.nbytes for k, v in out.items() if k != "intrinsics")
             return dt
@@ -167,6 +173,9 @@ def main():
     x1 = np.clip(np.ceil(slots["x0"].astype(np.float64) + slots["side"]), 0, W)
     y1 = np.clip(np.ceil(slots["y0"].astype(np.float64) + slots["side"]), 0, H)
     window_px = int(((x1 - x0) * (y1 - y0))[live].sum())
+    minified = live & (slots["side"] / np.float32(S) > 1)
+    # k_crop_area's own bytes: the in-frame RGB of every minified window read once, and its crop pixels written
+    area_rgb_bytes = int(((x1 - x0) * (y1 - y0))[minified].sum()) * 3 + int(minified.sum()) * S * S * 3
     written = n * K * (S * S * CROP_BYTES_PER_PIXEL + CROP_INFO_DTYPE.itemsize)
     own_bytes = written + window_px * SOURCE_BYTES_PER_PIXEL
     # what the samples themselves ask for: per sample of a live slot its id and four RGB taps, plus the
@@ -181,6 +190,7 @@ def main():
         return round(own_bytes / t / 1e12, 3) if t > 0 else None
 
     res = {"workload": "C3", "width": W, "height": H, "frames": n, "size": S, "per_frame": K, "min_pixels": 64, "pad": 1.5,
+           "rgb_filter": a.rgb_filter, "area_rgb_bytes": area_rgb_bytes,
            "method": f"HIP events around the enqueue on the caller's stream, device frame records and outputs, "
                      f"variants alternated, median of {a.reps} after one warm-up each",
            "render_s": round(med["render"], 6), "with_crops_s": round(med["with_crops"], 6),
