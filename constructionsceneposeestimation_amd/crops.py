@@ -2,7 +2,8 @@
 ``csg_crop_objects`` (include/csg_api.h), which labels may be cropped, and the
 geometry that goes with a crop -- its intrinsics and the keypoints in its
 pixels.  The crops themselves are made on the GPU
-(:meth:`renderer.Renderer.crop_objects`, :meth:`renderer.Renderer.render_crops`).
+(:meth:`renderer.Renderer.crop_objects`, :meth:`renderer.Renderer.render_crops`),
+and so are their amodal masks (:meth:`renderer.Renderer.crop_amodal`).
 
 A crop of side ``S`` samples the square source window ``x0, y0, side`` at
 ``x0 + (i + 0.5) * step``, ``step = side / S``: source pixel coordinate ``u``
@@ -37,6 +38,19 @@ def eligible_labels(scene: Scene, kinds: Sequence[str] = DYNAMIC_KINDS) -> np.nd
         if o.kind in kinds and o.inst_idx >= 0:
             t[o.inst_idx] = 1
     return t
+
+
+def visible_fraction(crop_mask: np.ndarray, crop_amodal: np.ndarray) -> np.ndarray:
+    """Per slot, the visible share of the object inside its crop: float64
+    ``crop_mask.sum() / crop_amodal.sum()`` over the S x S samples (set samples
+    counted, whatever non-zero value marks them), shaped like the leading
+    dimensions (..., S, S) -> (...).  NaN where the amodal mask is empty (an
+    empty slot, or an object wholly outside its window)."""
+    vis = np.count_nonzero(np.asarray(crop_mask), axis=(-2, -1)).astype(np.float64)
+    amo = np.count_nonzero(np.asarray(crop_amodal), axis=(-2, -1)).astype(np.float64)
+    out = np.full(amo.shape, np.nan, np.float64)
+    np.divide(vis, amo, out=out, where=amo > 0)
+    return out
 
 
 def _steps(info: np.ndarray, S: int):

@@ -227,6 +227,22 @@ struct csg_ctx {
   DevBuf<uint8_t> o_ids_n;              // [F][H][W] narrowed ids (device)
   uint8_t* h_ids_n = nullptr;           // ... their pinned host landing buffer
   size_t h_ids_n_bytes = 0;
+  // Amodal crop masks (csg_crop_amodal).  The label -> chunks table is built with the scene.  The pass has
+  // scratch of its own, grown to the job and never shared with a render: device copies of the frame
+  // records and the bit image, and a pinned staging ring for the host records (a slot is reused only
+  // after its H2D copy has completed).  am_done marks the end of the last pass: a pass on another
+  // stream waits for it on the device, a reallocation on the host.
+  DevBuf<uint32_t> lab_off, lab_chunks;   // [n_lab + 1], [chunks that carry a label >= 0]
+  uint32_t lab_max_chunks = 0;            // the most chunks one label has
+  DevBuf<FrameDev> am_frames;
+  DevBuf<uint32_t> am_bits;
+  FrameDev* am_stage[kStaging] = {};
+  size_t am_stage_n[kStaging] = {};
+  hipEvent_t am_stage_ev[kStaging] = {};
+  uint32_t am_stage_next = 0;
+  hipEvent_t am_done = nullptr;
+  hipStream_t am_stream = nullptr;
+  bool am_busy = false;
   // the last sizing pass (csg_size_work)
   uint32_t sized_frames = 0, sized_max_rec = 0, sized_max_bin = 0;
   double sized_mean_rec = 0.0, sized_mean_bin = 0.0;
@@ -391,6 +407,13 @@ void csg_destroy(csg_ctx* c) {
     if (c->h_stage[k]) (void)hipHostFree(c->h_stage[k]);
     if (c->stage_ev[k]) (void)hipEventDestroy(c->stage_ev[k]);
   }
+  if (c->am_busy) (void)hipEventSynchronize(c->am_done);   // a pass on a stream of the caller's
+  c->lab_off.release(); c->lab_chunks.release(); c->am_frames.release(); c->am_bits.release();
+  for (uint32_t k = 0; k < csg_ctx::kStaging; ++k) {
+    if (c->am_stage[k]) (void)hipHostFree(c->am_stage[k]);
+    if (c->am_stage_ev[k]) (void)hipEventDestroy(c->am_stage_ev[k]);
+  }
+  if (c->am_done) (void)hipEventDestroy(c->am_done);
   for (auto& e : c->ring)
     if (e) (void)hipEventDestroy(e);
   if (c->h_ids_n) (void)hipHostFree(c->h_ids_n);
@@ -413,6 +436,7 @@ int csg_upload_scene(csg_ctx* c, const csg_mesh* meshes, uint32_t n_meshes, cons
   {  // batches in flight read the scene and the work buffers this replaces
     const int rc = drain(c);
     if (rc) return rc;
+    if (c->am_busy) HIP_TRY(c, hipEventSynchronize(c->am_done));   // so does an amodal pass on any stream
   }
   std::vector<float> pos, uvs;
   std::vector<uint32_t> tris, uvt;
@@ -512,6 +536,25 @@ int csg_upload_scene(csg_ctx* c, const csg_mesh* meshes, uint32_t n_meshes, cons
     for (const InstDesc& d : idesc) { lo = std::min(lo, d.label); hi = std::max(hi, d.label); }
     c->ids_bytes = lo < -1 ? 4u : hi <= 254 ? 1u : hi <= 65534 ? 2u : 4u;
     c->n_lab = (uint32_t)std::max<int64_t>((int64_t)hi + 1, 1);
+  }
+  {   // label -> chunks (csg_crop_amodal): the chunk indices ordered by label, and each label's range
+    std::vector<uint32_t> off((size_t)c->n_lab + 1, 0u), list;
+    for (const Chunk& k : ch)
+      if (idesc[k.inst].label >= 0) ++off[(size_t)idesc[k.inst].label + 1];
+    uint32_t most = 0;
+    for (uint32_t l = 0; l < c->n_lab; ++l) {
+      most = std::max(most, off[l + 1]);
+      off[l + 1] += off[l];
+    }
+    list.resize(std::max<size_t>(off[c->n_lab], 1), 0u);
+    std::vector<uint32_t> at(off.begin(), off.end() - 1);
+    for (size_t k = 0; k < ch.size(); ++k)
+      if (idesc[ch[k].inst].label >= 0) list[at[(size_t)idesc[ch[k].inst].label]++] = (uint32_t)k;
+    HIP_TRY(c, c->lab_off.alloc(off.size()));
+    HIP_TRY(c, c->lab_chunks.alloc(list.size()));
+    HIP_TRY(c, hipMemcpy(c->lab_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->lab_chunks.p, list.data(), list.size() * 4, hipMemcpyHostToDevice));
+    c->lab_max_chunks = most;
   }
   c->iset.release();   // rebuilt for the new instances by the next sync_scene_state
   HIP_TRY(c, hipMemcpy(c->chunks.p, ch.data(), ch.size() * sizeof(Chunk), hipMemcpyHostToDevice));
@@ -699,6 +742,7 @@ static int sync_scene_state(csg_ctx* c) {
     // in flight still read them
     const int rc = drain(c);
     if (rc) return rc;
+    if (c->am_busy) HIP_TRY(c, hipEventSynchronize(c->am_done));   // so does an amodal pass, on any stream
   }
   const bool tex_changed = c->tex_dirty;
   const bool iset_dirty = c->tex_dirty || c->dr_dirty || c->n_table_sets != n_sets || !c->iset.p;
@@ -1990,6 +2034,80 @@ int csg_crop_objects_filtered(csg_ctx* c, const csg_crop_job* job, uint32_t rgb_
   if (a.crop_rgb || a.crop_mask || a.crop_coords || a.crop_depth) launch_crop_sample(a, n_frames, st);
   if (a.rgb_filter == CSG_CROP_FILTER_AREA && a.crop_rgb) launch_crop_area(a, n_frames, st);   // behind the plan
   HIP_TRY(c, hipGetLastError());
+  return CSG_OK;
+}
+
+// Amodal crop masks: reads the scene tables (synced here as a render syncs them) and the caller's
+// `info`; everything it writes besides the output is scratch of its own.
+int csg_crop_amodal(csg_ctx* c, const csg_amodal_job* job, uint32_t n_frames, void* stream) {
+  if (!c) return CSG_ERR_INVALID;
+  if (!job) return c->fail(CSG_ERR_INVALID, "crop_amodal: null job");
+  if (n_frames == 0) return c->fail(CSG_ERR_INVALID, "crop_amodal: no frames");
+  if (job->size < 16 || job->size > 512 || (job->size & 3u))
+    return c->fail(CSG_ERR_INVALID, "crop_amodal: size %u is not a multiple of 4 in 16..512", job->size);
+  if (job->per_frame < 1 || job->per_frame > 64)
+    return c->fail(CSG_ERR_INVALID, "crop_amodal: per_frame %u outside 1..64", job->per_frame);
+  if (!job->frames) return c->fail(CSG_ERR_INVALID, "crop_amodal: frames is NULL");
+  if (!job->info) return c->fail(CSG_ERR_INVALID, "crop_amodal: info is NULL");
+  if (!job->crop_amodal) return c->fail(CSG_ERR_INVALID, "crop_amodal: crop_amodal is NULL");
+  if (((uintptr_t)job->crop_amodal & 3u) || ((uintptr_t)job->info & 3u))
+    return c->fail(CSG_ERR_INVALID, "crop_amodal: crop_amodal and info must be 4-byte aligned");
+  if (!c->have_scene) return c->fail(CSG_ERR_INVALID, "crop_amodal: no scene uploaded");
+  for (uint32_t f = 0; f < n_frames; ++f)
+    if (job->frames[f].xform_set >= c->set_valid.size())
+      return c->fail(CSG_ERR_INVALID, "crop_amodal: frame %u: transform set %u is not resident (%u sets)", f,
+                     job->frames[f].xform_set, (unsigned)c->set_valid.size());
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+  int rc = sync_scene_state(c);
+  if (rc) return rc;
+  static_assert(sizeof(FrameDev) == sizeof(csg_frame), "frame layout");
+  const uint32_t S = job->size, K = job->per_frame, words = (S * S + 31u) / 32u;
+  const size_t n_bits = (size_t)n_frames * K * words;
+  if (!c->am_done) HIP_TRY(c, hipEventCreateWithFlags(&c->am_done, hipEventDisableTiming));
+  if (c->am_busy) {
+    if (c->am_frames.n < n_frames || c->am_bits.n < n_bits)
+      HIP_TRY(c, hipEventSynchronize(c->am_done));           // the last pass still reads what is freed below
+    else if (c->am_stream != st)
+      HIP_TRY(c, hipStreamWaitEvent(st, c->am_done, 0));     // ... or what this pass overwrites
+  }
+  HIP_TRY(c, c->am_frames.alloc(n_frames));
+  HIP_TRY(c, c->am_bits.alloc(n_bits));
+  const uint32_t ring = c->am_stage_next;
+  c->am_stage_next = (ring + 1) % csg_ctx::kStaging;
+  if (!c->am_stage_ev[ring]) HIP_TRY(c, hipEventCreateWithFlags(&c->am_stage_ev[ring], hipEventDisableTiming));
+  else HIP_TRY(c, hipEventSynchronize(c->am_stage_ev[ring]));   // the slot's last H2D copy is done
+  if (c->am_stage_n[ring] < n_frames) {
+    if (c->am_stage[ring]) HIP_TRY(c, hipHostFree(c->am_stage[ring]));
+    c->am_stage[ring] = nullptr;
+    c->am_stage_n[ring] = 0;
+    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->am_stage[ring]), sizeof(FrameDev) * n_frames));
+    c->am_stage_n[ring] = n_frames;
+  }
+  memcpy(c->am_stage[ring], job->frames, sizeof(FrameDev) * n_frames);
+  HIP_TRY(c, hipMemcpyAsync(c->am_frames.p, c->am_stage[ring], sizeof(FrameDev) * n_frames, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipEventRecord(c->am_stage_ev[ring], st));
+  HIP_TRY(c, hipMemsetAsync(c->am_bits.p, 0, n_bits * sizeof(uint32_t), st));
+  AmodalDev a{};
+  a.S = S;
+  a.K = K;
+  a.n_labels = c->n_lab;
+  a.n_sets = (uint32_t)c->set_valid.size();
+  a.words = words;
+  a.frames = c->am_frames.p;
+  a.info = reinterpret_cast<const CropSlot*>(job->info);
+  a.lab_off = c->lab_off.p;
+  a.lab_chunks = c->lab_chunks.p;
+  a.chunks = c->chunks.p;
+  a.models = c->models.p;
+  a.iset = c->iset.p;
+  a.bits = c->am_bits.p;
+  a.out = job->crop_amodal;
+  launch_crop_amodal(scene_dev(c), a, n_frames, c->lab_max_chunks, st);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipEventRecord(c->am_done, st));
+  c->am_stream = st;
+  c->am_busy = true;
   return CSG_OK;
 }
 

@@ -37,6 +37,27 @@ struct CropArgs {
   CropSlot* info;                // [n][K]
 };
 
+#ifdef __HIPCC__
+// The sampling arithmetic of the crop spec (include/csg_api.h), shared by every
+// kernel that must land on the same source pixels: k_crop_sample, k_crop_area
+// and the amodal pass of csg_kernels.hip.  float32, each operation rounded once.
+//
+// The liveness rule of a slot whose window is an input (NaN fails every comparison).
+__device__ __forceinline__ bool crop_label_live(const CropSlot& sl, uint32_t n_labels) {
+  return sl.label >= 0 && (uint32_t)sl.label < n_labels;
+}
+__device__ __forceinline__ bool crop_window_live(const CropSlot& sl) {
+  return sl.side > 0.0f && sl.side <= 32768.0f && fabsf(sl.x0) <= 1048576.0f && fabsf(sl.y0) <= 1048576.0f;
+}
+__device__ __forceinline__ float crop_step(const CropSlot& sl, uint32_t S) { return sl.side / (float)S; }
+// sx of output column i (sy of row j with y0): the sample's position in source pixels
+__device__ __forceinline__ float crop_sample_pos(float origin, uint32_t i, float step) {
+  return origin + ((float)i + 0.5f) * step;
+}
+// `inside` along one axis: floorf(s) lies in [0, extent)
+__device__ __forceinline__ bool crop_sample_in(float s, float extent) { return s >= 0.0f && s < extent; }
+#endif
+
 // k_crop_plan: fills info [n][K] from the frames' label statistics.
 void launch_crop_plan(const CropArgs& a, uint32_t n, hipStream_t st);
 // k_crop_sample: resamples every slot of info into the requested images

@@ -29,9 +29,8 @@ constexpr uint32_t kAreaRows = 8;      // crop rows of a workgroup's band
 
 // A live slot's liveness, as the spec of csg_api.h words it (NaN fails every comparison).
 __device__ __forceinline__ bool slot_live(const CropArgs& a, const CropSlot& sl) {
-  bool live = sl.label >= 0 && (uint32_t)sl.label < a.n_labels;
-  if (a.explicit_boxes)
-    live = live && sl.side > 0.0f && sl.side <= 32768.0f && fabsf(sl.x0) <= 1048576.0f && fabsf(sl.y0) <= 1048576.0f;
+  bool live = crop_label_live(sl, a.n_labels);
+  if (a.explicit_boxes) live = live && crop_window_live(sl);
   return live;
 }
 
@@ -152,9 +151,9 @@ __global__ __launch_bounds__(kCropBlock) void k_crop_sample(CropArgs a, uint32_t
   const float fW = (float)W, fH = (float)H;
   const size_t fpx = (size_t)f * W * H;             // the frame's first pixel
   const uint32_t j = q / qrow, i0 = (q - j * qrow) * 4u;
-  const float step = sl.side / (float)S;
-  const float sy = sl.y0 + ((float)j + 0.5f) * step;
-  const bool yin = sy >= 0.0f && sy < fH;           // floorf(sy) in [0, H)
+  const float step = crop_step(sl, S);
+  const float sy = crop_sample_pos(sl.y0, j, step);
+  const bool yin = crop_sample_in(sy, fH);          // floorf(sy) in [0, H)
   const uint32_t py = yin ? (uint32_t)floorf(sy) : 0u;
   const float ty = sy - 0.5f;
   const bool yv = ty >= -1.0f && ty < fH;           // a tap row may lie in the frame
@@ -166,8 +165,8 @@ __global__ __launch_bounds__(kCropBlock) void k_crop_sample(CropArgs a, uint32_t
   float d[4];
 #pragma unroll
   for (uint32_t t = 0; t < 4; ++t) {
-    const float sx = sl.x0 + ((float)(i0 + t) + 0.5f) * step;
-    const bool in = yin && sx >= 0.0f && sx < fW;
+    const float sx = crop_sample_pos(sl.x0, i0 + t, step);
+    const bool in = yin && crop_sample_in(sx, fW);
     const size_t at = fpx + (size_t)py * W + (in ? (uint32_t)floorf(sx) : 0u);
     const bool hit = in && a.instance[at] == sl.label;
     m |= hit ? (255u << (8 * t)) : 0u;

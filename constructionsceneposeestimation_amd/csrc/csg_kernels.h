@@ -231,6 +231,27 @@ void launch_inst_bounds(const SceneDev& s, const Chunk* chunks, uint32_t n_chunk
                         uint32_t* out, hipStream_t st);
 void launch_project(const float* pts, uint32_t n, const float* pv12, float W, float H, float near_clip,
                     float* uv, int32_t* vis, hipStream_t st);
+// Amodal crop masks (csg_crop_amodal): k_amodal ORs, per slot, the samples some triangle of the slot's
+// label covers into `bits` (zeroed by the caller), k_amodal_expand writes them as 255 / 0 bytes.  The pass
+// reads the scene tables and its own copies of the frame records, never the render's work buffers.
+struct CropSlot;   // csg_crops.h
+struct AmodalDev {
+  uint32_t S, K;                 // crop side (multiple of 4, <= 512), slots per frame
+  uint32_t n_labels;             // label-table length: lab_off has n_labels + 1 entries
+  uint32_t n_sets;               // transform sets in models / iset
+  uint32_t words;                // 32-bit words of one slot's bit image, (S * S + 31) / 32
+  const FrameDev* frames;        // [n]
+  const CropSlot* info;          // [n][K]
+  const uint32_t* lab_off;       // [n_labels + 1] label -> range of lab_chunks
+  const uint32_t* lab_chunks;    // chunk indices ordered by their instance's label
+  const Chunk* chunks;
+  const float* models;           // [n_sets][I][16]
+  const InstSetDev* iset;        // [n_sets][I]
+  uint32_t* bits;                // [n][K][words]
+  uint8_t* out;                  // [n][K][S][S]
+};
+// max_chunks: the largest number of chunks one label has (k_amodal's grid x; 0: no label has any)
+void launch_crop_amodal(const SceneDev& s, const AmodalDev& a, uint32_t n, uint32_t max_chunks, hipStream_t st);
 // ids [lo, hi) of the int32 instance image as (id + 1) in `bytes` (1 or 2) bytes (the host wire)
 void launch_narrow_ids(const int32_t* src, size_t lo, size_t hi, uint32_t bytes, void* dst, hipStream_t st);
 

@@ -32,6 +32,7 @@
 
 #include <type_traits>
 
+#include "csg_crops.h"
 #include "csg_kernels.h"
 
 namespace csg {
@@ -2622,6 +2623,310 @@ void launch_narrow_ids(const int32_t* src, size_t lo, size_t hi, uint32_t bytes,
   const size_t groups = (hi - (lo & ~(size_t)3) + 3) / 4;
   if (!groups) return;
   hipLaunchKernelGGL(k_narrow_ids, dim3((uint32_t)((groups + 255) / 256)), dim3(256), 0, st, src, lo, hi, bytes, dst);
+}
+
+// ---------------------------------------------------------------------------
+// Amodal crop masks (csg_crop_amodal): for each crop slot the
+// samples of its window that SOME triangle of the slot's label covers, with
+// the depth range and the alpha test but without a depth test and without the
+// per-tile label cap of k_raster<true>'s coverage table -- spec §3.11 for one
+// label, at the crop's own sample positions.
+//
+// k_amodal, grid (chunk of the label, slot, frame): the slot's label is only
+// known on the device (`info` may still be in flight), so the grid spans the
+// largest per-label chunk count and blocks past their label's count leave.  A
+// block takes one chunk (<= 256 triangles of one instance), one triangle per
+// thread through k_setup's arithmetic -- clip rows P * (V * M) in spec order,
+// frustum rejects, near-clip fan, make_rec's fixed point, hom_setup and the
+// planes -- then, per raster sub-triangle, intersects the record's pixel box
+// with the window: sample column i lands on source pixel colpx[i], which is
+// nondecreasing in i (so is rowpy[j]), so the samples whose nearest pixel lies
+// in the box are a rectangle [i0, i1) x [j0, j1) found by binary search in LDS.
+// Only those are tested: exact 64-bit edge functions with the top-left bias at
+// the pixel's centre, 1/W in [1/far, 1/near], the alpha test of fragment().
+// A sub-triangle with at most kAmSerial samples is finished by its own lane; a
+// larger one (up to the whole window) is queued in LDS and its samples are
+// spread over the block, kAmQueue records per round, so one lane never walks a
+// window alone.  Hits are ORed into an S x S bit image in LDS; the block's
+// non-zero words go by atomicOr into the pass's zeroed global bit image, and
+// k_amodal_expand turns bits into 255 / 0 bytes, writing every byte of the
+// output.  OR is order-free, so the result is deterministic.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kAmSerial = 16;   // samples a lane tests itself
+constexpr uint32_t kAmQueue = 64;    // larger sub-triangles queued per round
+constexpr int32_t kAmPast = 0x7FFFFFFF;   // colpx / rowpy of a sample past the frame's far edge
+
+struct AmTri {   // what the sample test needs of one raster sub-triangle
+  int32_t x[3], y[3];          // 24.8 fixed point, positive orientation (make_rec)
+  float D[3], U[3], V[3];      // planes of the original triangle
+  uint32_t atex, wh, thr;      // alpha test (kNoAlpha: none)
+  uint32_t i0, ni, j0, nj;     // sample rectangle
+};
+
+// Spec §3.3 / §3.5 / §3.6 at the centre of pixel (px, py): covered, in the depth range, alpha passed.
+__device__ __forceinline__ bool amodal_hit(const SceneDev& s, const AmTri& t, int32_t px, int32_t py) {
+  const int32_t cx = px * 256 + 128, cy = py * 256 + 128;
+  const int ea[3] = {1, 2, 0}, eb[3] = {2, 0, 1};
+  bool in = true;
+#pragma unroll
+  for (int e = 0; e < 3; ++e) {
+    const int32_t dx = t.x[eb[e]] - t.x[ea[e]], dy = t.y[eb[e]] - t.y[ea[e]];
+    const int32_t bias = (dy < 0 || (dy == 0 && dx > 0)) ? 0 : -1;
+    in &= (int64_t)dx * (cy - t.y[ea[e]]) - (int64_t)dy * (cx - t.x[ea[e]]) + bias >= 0;
+  }
+  if (!in) return false;
+  const float fx = (float)px + 0.5f, fy = (float)py + 0.5f;
+  const float invw = plane_at(t.D[0], t.D[1], t.D[2], fx, fy);
+  if (!(invw >= s.inv_far && invw <= s.inv_near)) return false;
+  if (t.atex == kNoAlpha) return true;
+  const float r = rcp_ieee(invw);   // invw in [1/far, 1/near]
+  const float u = plane_at(t.U[0], t.U[1], t.U[2], fx, fy) * r, v = plane_at(t.V[0], t.V[1], t.V[2], fx, fy) * r;
+  return alpha_pass(s.aquad, s.acls, t.atex, t.wh, (int)t.thr, u, v);
+}
+
+// first index in [0, n) with tab[index] >= v (tab nondecreasing), n if none
+__device__ __forceinline__ uint32_t am_lower(const int32_t* tab, uint32_t n, int32_t v) {
+  uint32_t lo = 0, hi = n;
+#pragma clang loop unroll(disable)
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (tab[mid] < v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(kBlock) void k_amodal(SceneDev s, AmodalDev a, uint32_t f0) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t am_bits[];   // [a.words] the slot's samples as bits
+  __shared__ int32_t colpx[512], rowpy[512];
+  __shared__ float clipm[12];
+  __shared__ AmTri queue[kAmQueue];
+  __shared__ uint32_t qn;
+  const uint32_t k = blockIdx.y, f = f0 + blockIdx.z, S = a.S;
+  const size_t slot = (size_t)f * a.K + k;
+  const CropSlot sl = a.info[slot];
+  // block-uniform exits: dead slot (its bits stay zero), no such chunk, a set the tables do not hold
+  if (!crop_label_live(sl, a.n_labels) || !crop_window_live(sl)) return;
+  const uint32_t c0 = a.lab_off[sl.label], cn = a.lab_off[sl.label + 1] - c0;
+  if (blockIdx.x >= cn) return;
+  const FrameDev& fr = a.frames[f];
+  const uint32_t set = fr.xform_set;
+  if (set >= a.n_sets) return;
+  const Chunk& ch = a.chunks[a.lab_chunks[c0 + blockIdx.x]];
+  const uint32_t inst = ch.inst;
+  const int tid = threadIdx.x;
+
+  const float step = crop_step(sl, S);
+  for (uint32_t t = tid; t < S; t += kBlock) {
+    const float sx = crop_sample_pos(sl.x0, t, step), sy = crop_sample_pos(sl.y0, t, step);
+    colpx[t] = crop_sample_in(sx, (float)s.W) ? (int32_t)floorf(sx) : (sx < 0.0f ? -1 : kAmPast);
+    rowpy[t] = crop_sample_in(sy, (float)s.H) ? (int32_t)floorf(sy) : (sy < 0.0f ? -1 : kAmPast);
+  }
+  for (uint32_t w = tid; w < a.words; w += kBlock) am_bits[w] = 0u;
+  if (tid == 0) {   // the instance's clip rows, as k_clip forms them
+    const float* M = a.models + ((size_t)set * s.n_inst + inst) * 16;
+    float m[16], vm[16], c[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) m[q] = M[q];
+    mat4_mul(fr.view, m, vm);
+    mat4_mul(fr.proj, vm, c);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      clipm[q] = c[q];
+      clipm[4 + q] = c[4 + q];
+      clipm[8 + q] = c[12 + q];
+    }
+  }
+  __syncthreads();
+
+  auto mark = [&](uint32_t i, uint32_t j) {
+    const uint32_t p = j * S + i;
+    atomicOr(&am_bits[p >> 5], 1u << (p & 31u));
+  };
+
+  // k_setup's per-triangle arithmetic (setup_chunk), kept in the same order
+  AmTri t0 = {}, t1 = {};
+  int nrec = 0;
+  if ((uint32_t)tid < ch.count) {
+    const uint32_t g = ch.soup + tid;
+    Cv3 v[3];
+    float c[12];
+#pragma unroll
+    for (int q = 0; q < 12; ++q) c[q] = clipm[q];
+    const float* tp = s.tri_pos + (size_t)g * 9;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      const float px = tp[3 * q], py = tp[3 * q + 1], pz = tp[3 * q + 2];
+      v[q].x = dot4(c + 0, px, py, pz);
+      v[q].y = dot4(c + 4, px, py, pz);
+      v[q].w = dot4(c + 8, px, py, pz);
+    }
+    const float nearc = s.near_clip, farc = s.far_clip;
+    const float Wf = (float)s.W, Hf = (float)s.H;
+    bool on = true, of = true, ol = true, orr = true, ot = true, ob = true;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      on &= v[q].w < nearc;
+      of &= v[q].w > farc;
+      ol &= v[q].x < 0.0f;
+      orr &= v[q].x > Wf * v[q].w;
+      ot &= v[q].y < 0.0f;
+      ob &= v[q].y > Hf * v[q].w;
+    }
+    if (!(on | of | ol | orr | ot | ob)) {
+      Cv3 q0 = v[0], q1 = v[1], q2 = v[2], q3 = v[2];
+      int nq = 3;
+      const bool in0 = v[0].w >= nearc, in1 = v[1].w >= nearc, in2 = v[2].w >= nearc;
+      if (!(in0 && in1 && in2)) {
+        auto cross_pt = [&](const Cv3& p, const Cv3& bb) {
+          const float tt = (nearc - p.w) / (bb.w - p.w);
+          Cv3 rr;
+          rr.x = p.x + tt * (bb.x - p.x);
+          rr.y = p.y + tt * (bb.y - p.y);
+          rr.w = nearc;
+          return rr;
+        };
+        auto sel = [](bool cnd, const Cv3& p, const Cv3& bb) {
+          Cv3 rr;
+          rr.x = cnd ? p.x : bb.x;
+          rr.y = cnd ? p.y : bb.y;
+          rr.w = cnd ? p.w : bb.w;
+          return rr;
+        };
+        const Cv3 I01 = cross_pt(v[0], v[1]), I12 = cross_pt(v[1], v[2]), I20 = cross_pt(v[2], v[0]);
+        const int code = (int)in0 | ((int)in1 << 1) | ((int)in2 << 2);
+        q0 = sel(code == 2 || code == 6, I01, sel(code == 4, I12, v[0]));
+        q1 = sel(code == 1 || code == 5, I01, sel(code == 4, v[2], v[1]));
+        q2 = sel(code == 1 || code == 4, I20, sel(code == 6, v[2], I12));
+        q3 = sel(code == 3 || code == 6, I20, v[2]);
+        nq = (code == 1 || code == 2 || code == 4) ? 3 : 4;
+      }
+      // a sub-triangle's record, then the samples of the window inside its pixel box
+      auto emit_tri = [&](const Cv3& p, const Cv3& bb, const Cv3& cc) {
+        const float ra = rcp_w(p.w), rb = rcp_w(bb.w), rc = rcp_w(cc.w);
+        float su[3], sv[3];
+        su[0] = p.x * ra; sv[0] = p.y * ra;
+        su[1] = bb.x * rb; sv[1] = bb.y * rb;
+        su[2] = cc.x * rc; sv[2] = cc.y * rc;
+        SubRec rr;
+        if (!make_rec(s, su, sv, rr)) return;
+        const int32_t bx0 = (int32_t)(rr.g1.z & 0xFFFFu), by0 = (int32_t)(rr.g1.z >> 16);
+        const int32_t bx1 = (int32_t)(rr.g1.w & 0xFFFFu), by1 = (int32_t)(rr.g1.w >> 16);
+        const uint32_t i0 = am_lower(colpx, S, bx0), i1 = am_lower(colpx, S, bx1 + 1);
+        if (i0 >= i1) return;
+        const uint32_t j0 = am_lower(rowpy, S, by0), j1 = am_lower(rowpy, S, by1 + 1);
+        if (j0 >= j1) return;
+        // into t0, then t1: selects on named structs, never a runtime-chosen one (as k_setup's r0, r1)
+        const bool first = nrec == 0;
+        auto put = [](AmTri& d, bool on, const SubRec& r, uint32_t a0, uint32_t an, uint32_t b0, uint32_t bn) {
+          d.x[0] = on ? (int32_t)r.g0.x : d.x[0]; d.x[1] = on ? (int32_t)r.g0.y : d.x[1];
+          d.x[2] = on ? (int32_t)r.g0.z : d.x[2]; d.y[0] = on ? (int32_t)r.g0.w : d.y[0];
+          d.y[1] = on ? (int32_t)r.g1.x : d.y[1]; d.y[2] = on ? (int32_t)r.g1.y : d.y[2];
+          d.i0 = on ? a0 : d.i0; d.ni = on ? an : d.ni; d.j0 = on ? b0 : d.j0; d.nj = on ? bn : d.nj;
+        };
+        put(t0, first, rr, i0, i1 - i0, j0, j1 - j0);
+        put(t1, !first, rr, i0, i1 - i0, j0, j1 - j0);
+        ++nrec;
+      };
+      if (nq >= 3) emit_tri(q0, q1, q2);
+      if (nq >= 4) emit_tri(q0, q2, q3);
+      if (nrec > 0) {
+        Hom h;
+        hom_setup(v, h);
+        const InstSetDev is = a.iset[(size_t)set * s.n_inst + inst];
+        // as k_setup: no record without a determinant, none under a threshold of 255
+        if (!h.ok || (is.atex != kNoAlpha && is.athr >= 255u)) {
+          nrec = 0;
+        } else {
+          float D[3], U[3] = {0.0f, 0.0f, 0.0f}, V[3] = {0.0f, 0.0f, 0.0f};
+          depth_plane(h.A, h.B, h.C, h.invdet, D);
+          if (is.alpha_uv) {
+            const float* tu = s.tri_uv + (size_t)g * 6;
+            float uv[6];
+#pragma unroll
+            for (int q = 0; q < 6; ++q) uv[q] = tu[q];
+            uv_planes(h.A, h.B, h.C, h.invdet, uv, U, V);
+          }
+#pragma unroll
+          for (int q = 0; q < 3; ++q) {
+            t0.D[q] = t1.D[q] = D[q];
+            t0.U[q] = t1.U[q] = U[q];
+            t0.V[q] = t1.V[q] = V[q];
+          }
+          t0.atex = t1.atex = is.atex;
+          t0.wh = t1.wh = is.atex_wh;
+          t0.thr = t1.thr = is.athr;
+        }
+      }
+    }
+  }
+  // small sample rectangles: the lane's own loop
+  auto serial = [&](const AmTri& t) {
+#pragma clang loop unroll(disable)
+    for (uint32_t q = 0; q < t.ni * t.nj; ++q) {
+      const uint32_t jj = small_div(q, t.ni), ii = q - jj * t.ni;
+      const uint32_t i = t.i0 + ii, j = t.j0 + jj;
+      if (amodal_hit(s, t, colpx[i], rowpy[j])) mark(i, j);
+    }
+  };
+  bool p0 = nrec > 0 && t0.ni * t0.nj > kAmSerial, p1 = nrec > 1 && t1.ni * t1.nj > kAmSerial;
+  if (nrec > 0 && !p0) serial(t0);
+  if (nrec > 1 && !p1) serial(t1);
+  // large ones: queued, their samples spread over the block (block-uniform loop)
+  for (;;) {
+    if (tid == 0) qn = 0u;
+    __syncthreads();
+    if (p0) {
+      const uint32_t at = atomicAdd(&qn, 1u);
+      if (at < kAmQueue) { queue[at] = t0; p0 = false; }
+    }
+    if (p1) {
+      const uint32_t at = atomicAdd(&qn, 1u);
+      if (at < kAmQueue) { queue[at] = t1; p1 = false; }
+    }
+    __syncthreads();
+    const uint32_t n = min(qn, kAmQueue);
+    for (uint32_t e = 0; e < n; ++e) {
+      const AmTri& t = queue[e];
+      const uint32_t ni = t.ni, cnt = ni * t.nj;
+      for (uint32_t q = tid; q < cnt; q += kBlock) {
+        const uint32_t jj = small_div(q, ni), ii = q - jj * ni;
+        const uint32_t i = t.i0 + ii, j = t.j0 + jj;
+        if (amodal_hit(s, t, colpx[i], rowpy[j])) mark(i, j);
+      }
+    }
+    if (!__syncthreads_or((int)(p0 || p1))) break;   // also orders this round's queue reads before the next writes
+  }
+  // (the closing barrier above ordered every mark before these reads)
+  uint32_t* gb = a.bits + slot * a.words;
+  for (uint32_t w = tid; w < a.words; w += kBlock) {
+    const uint32_t v = am_bits[w];
+    if (v) atomicOr(&gb[w], v);
+  }
+}
+
+// bits -> 255 / 0: one thread expands 4 consecutive samples (S * S is a multiple
+// of 16, so they share a word and a slot) into one 4-B store.  Grid (quads of
+// a slot / 256, K, frames): every byte of every slot is written, dead ones from
+// the zeros the bit image was cleared to.
+__global__ __launch_bounds__(256) void k_amodal_expand(AmodalDev a, uint32_t f0) {
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  if (q >= a.S * a.S / 4u) return;
+  const size_t slot = (size_t)(f0 + blockIdx.z) * a.K + blockIdx.y;
+  const uint32_t p = q * 4u;
+  const uint32_t b = a.bits[slot * a.words + (p >> 5)] >> (p & 31u);
+  const uint32_t m = ((b & 1u) ? 0xFFu : 0u) | ((b & 2u) ? 0xFF00u : 0u) | ((b & 4u) ? 0xFF0000u : 0u) |
+                     ((b & 8u) ? 0xFF000000u : 0u);
+  __builtin_nontemporal_store(m, reinterpret_cast<uint32_t*>(a.out + slot * a.S * a.S + p));
+}
+
+void launch_crop_amodal(const SceneDev& s, const AmodalDev& a, uint32_t n, uint32_t max_chunks, hipStream_t st) {
+  const uint32_t quads = a.S * a.S / 4u;
+  for (uint32_t f0 = 0; f0 < n; f0 += 65535u) {   // grid z limit
+    const uint32_t nf = n - f0 < 65535u ? n - f0 : 65535u;
+    if (max_chunks)
+      hipLaunchKernelGGL(k_amodal, dim3(max_chunks, a.K, nf), dim3(kBlock), a.words * sizeof(uint32_t), st, s, a, f0);
+    hipLaunchKernelGGL(k_amodal_expand, dim3((quads + 255u) / 256u, a.K, nf), dim3(256), 0, st, a, f0);
+  }
 }
 
 }  // namespace csg

@@ -413,6 +413,22 @@ class Renderer:
         self._check(self.lib.csg_crop_objects_filtered(self.ctx, C.byref(job), _lib.CROP_FILTERS[rgb_filter], int(n),
                                                        stream or None), "crop_objects")
 
+    def crop_amodal(self, frames: np.ndarray, *, size: int, per_frame: int, info: int, crop_amodal: int,
+                    stream: int = 0) -> None:
+        """Enqueue the amodal masks of the crops of ``frames`` (csg_crop_amodal;
+        raw device pointers, like :meth:`crop_objects`): for each slot of
+        ``info`` (n, K) the samples of its window that the slot's object
+        covers with every other object taken out of the scene, into
+        ``crop_amodal`` (n, K, S, S) uint8 255 / 0.  ``frames`` are the HOST
+        records (``FRAME_DTYPE``) the crops were cut from; they are copied
+        before the call returns.  Behind :meth:`crop_objects` on the same
+        stream no synchronisation is needed in between.  ``n`` is not bound
+        by ``max_frames``."""
+        frames = np.ascontiguousarray(frames, FRAME_DTYPE)
+        job = _lib.AmodalJob(int(size), int(per_frame), frames.ctypes.data, info or None, crop_amodal or None)
+        self._check(self.lib.csg_crop_amodal(self.ctx, C.byref(job), int(frames.shape[0]), stream or None),
+                    "crop_amodal")
+
     def render_crops(self, frames: np.ndarray, size: int = 128, per_frame: int = 8, min_pixels: int = 64,
                      pad: float = 1.5, kinds: Sequence[str] = DYNAMIC_KINDS,
                      want: Iterable[str] = ("rgb", "mask", "coords"), object_frames=None,
@@ -421,7 +437,9 @@ class Renderer:
         chunks of ``max_frames`` are rendered into device tensors (torch),
         cropped on the same stream, and the crops and their ``info`` copied to
         page-locked host arrays; whole frames never cross PCIe.  ``want``
-        chooses among "rgb", "mask", "coords", "depth"; ``kinds`` the object
+        chooses among "rgb", "mask", "coords", "depth" and "amodal" (the
+        unoccluded mask of :meth:`crop_amodal`, as ``crop_amodal`` (n, K, S, S)
+        uint8, made behind the crops of each chunk); ``kinds`` the object
         kinds that may be cropped (:func:`crops.eligible_labels`).  Returns
         ``crop_rgb`` / ``crop_mask`` / ``crop_coords`` / ``crop_depth`` (those
         wanted, shaped as :meth:`crop_objects` says), ``info`` (n, K) and
@@ -440,8 +458,9 @@ class Renderer:
         frames = np.ascontiguousarray(frames, FRAME_DTYPE)
         n, S, K, H, W = frames.shape[0], int(size), int(per_frame), self.height, self.width
         want = set(want)
-        if not want or want - {"rgb", "mask", "coords", "depth"}:
-            raise CsgError(f"render_crops: want {sorted(want)} must be a non-empty subset of rgb, mask, coords, depth")
+        if not want or want - {"rgb", "mask", "coords", "depth", "amodal"}:
+            raise CsgError(f"render_crops: want {sorted(want)} must be a non-empty subset of rgb, mask, coords, depth, "
+                           "amodal")
         for set_id, of in (object_frames or {}).items():
             self.set_object_frames(int(set_id), of)
         dev = torch.device("cuda", self.device)
@@ -459,6 +478,7 @@ class Renderer:
                "stats": dbuf(True, (m, self.n_labels, 5), torch.int32)}
         shapes = {"crop_rgb": ("rgb", (K, S, S, 3), torch.uint8), "crop_mask": ("mask", (K, S, S), torch.uint8),
                   "crop_coords": ("coords", (K, S, S, 3), torch.int16), "crop_depth": ("depth", (K, S, S), torch.float32),
+                  "crop_amodal": ("amodal", (K, S, S), torch.uint8),
                   "info": (None, (K, CROP_INFO_DTYPE.itemsize), torch.uint8)}
         d_out = {k: dbuf(w is None or w in want, (m,) + sh, dt) for k, (w, sh, dt) in shapes.items()}
         h_out = {k: torch.empty((n,) + sh, dtype=dt, pin_memory=True)
@@ -478,6 +498,9 @@ class Renderer:
                                   crop_rgb=ptr(d_out["crop_rgb"]), crop_mask=ptr(d_out["crop_mask"]),
                                   crop_coords=ptr(d_out["crop_coords"]), crop_depth=ptr(d_out["crop_depth"]),
                                   info=ptr(d_out["info"]), stream=stream.cuda_stream, rgb_filter=rgb_filter)
+                if "amodal" in want:
+                    self.crop_amodal(frames[s:e], size=S, per_frame=K, info=ptr(d_out["info"]),
+                                     crop_amodal=ptr(d_out["crop_amodal"]), stream=stream.cuda_stream)
                 for k, h in h_out.items():
                     h[s:e].copy_(d_out[k][:e - s], non_blocking=True)
         stream.synchronize()

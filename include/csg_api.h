@@ -53,6 +53,11 @@
  *                               produces none (its users crop whole frames on the host)
  *   csg_crop_objects_filtered . the same with an exact area filter for the RGB of
  *                               minified windows (CSG_CROP_FILTER_AREA)
+ *   csg_crop_amodal ........... (new) the amodal mask of each crop: the object's full
+ *                               silhouette as if nothing stood in front of it (BOP's
+ *                               `mask` next to `mask_visib`), rasterised from the scene
+ *                               at the crop's own sample positions; the reference
+ *                               would render the frame once more per object
  *   csg_last_error / csg_destroy
  *
  * Threading: several contexts may share a device (each has its own stream
@@ -540,6 +545,62 @@ int csg_crop_objects(csg_ctx* ctx, const csg_crop_job* job, uint32_t n_frames, v
 #define CSG_CROP_FILTER_AREA     1u   /* exact box filter where step > 1 */
 int csg_crop_objects_filtered(csg_ctx* ctx, const csg_crop_job* job, uint32_t rgb_filter,
                               uint32_t n_frames, void* stream);
+
+/* Amodal crop masks: for each slot of `info`, the samples of its window that the
+ * slot's object covers when every other object is taken out of the scene --
+ * BOP's `mask`, where crop_mask is `mask_visib`.  Unlike the crops this pass
+ * reads the uploaded scene (geometry, the frames' transform sets and their
+ * materials) and no rendered array; it is the per-pixel form of label_covered
+ * (occlusionRatio), without that counter's limit of 32 labels per tile.
+ *
+ * Live slot: a slot is live under the rule csg_crop_objects applies to an
+ * `info` it reads: 0 <= label < the scene's label-table length (largest inst_idx
+ * + 1), side finite with 0 < side <= 32768, |x0|, |y0| finite and <= 2^20.
+ * Every other slot -- an empty one, a planned window beyond those bounds --
+ * writes zeros.  Slot [f][k] belongs to frames[f].
+ *
+ * Sample (i, j) of a live slot with label L has the px, py and `inside` of
+ * csg_crop_objects (the same float32 expressions).  crop_amodal = 255 iff the
+ * sample is inside and some instance with inst_idx == L has a triangle that, at
+ * pixel (px, py) of frame f, passes all of:
+ *   - one of its raster sub-triangles (after the near clip; fixed point, exact
+ *     edge functions, top-left rule) covers the pixel centre under the models
+ *     of transform set frames[f].xform_set and the frame's view and proj;
+ *   - its 1/W at the centre lies in [1/far_clip, 1/near_clip];
+ *   - the alpha test with the material that set gives the instance (texture
+ *     swaps of csg_set_dr_textures applied).
+ * There is no depth test and no per-tile label cap: the pixel is one that is not
+ * -1 in a render of the frame from which every instance of another label is
+ * removed.  A set inside the range that was never uploaded has zero models and
+ * draws nothing, so its slots are all zero; so are those of a label no
+ * instance carries.
+ *
+ * So: wherever crop_mask of the same slot is 255, crop_amodal is 255; every
+ * byte of crop_amodal is written; and no `info` value -- NaN, infinite, far
+ * away, any label -- yields an address outside the arrays described.
+ *
+ * Enqueues on `stream` (NULL = the context's stream) and returns; `frames` are
+ * copied before it returns.  Behind csg_crop_objects on the same stream it needs
+ * no synchronisation.  csg_synchronize waits for it under the rule for the
+ * crops.  The pass has scratch of its own, grown to the job (n_frames is not
+ * bound by max_frames), and never touches the render's work buffers: a render on
+ * another stream may run beside it.  Pending scene changes (transforms,
+ * textures) are uploaded first, as by a render.
+ *
+ * CSG_ERR_INVALID, nothing enqueued or written: job, frames, info or crop_amodal
+ * NULL; n_frames == 0; size or per_frame out of range; crop_amodal or info
+ * misaligned; no scene uploaded; a frames[f].xform_set that is not resident
+ * (>= the largest set id uploaded + 1). */
+typedef struct {
+  uint32_t size;               /* S, as csg_crop_job: multiple of 4, 16..512 */
+  uint32_t per_frame;          /* K, 1..64 */
+  const csg_frame* frames;     /* HOST records [n]: view, proj, xform_set of the frames the crops were cut
+                                  from; copied before the call returns (the caller may reuse them at once) */
+  const csg_crop_info* info;   /* DEVICE [n][K], read only: what csg_crop_objects wrote or read; slot [f][k]
+                                  belongs to frames[f] (its `frame` and `pixels` fields are ignored) */
+  uint8_t* crop_amodal;        /* DEVICE [n][K][S][S], 255 / 0, 4-B aligned */
+} csg_amodal_job;
+int csg_crop_amodal(csg_ctx* ctx, const csg_amodal_job* job, uint32_t n_frames, void* stream);
 
 /* Stand-alone 3D->2D projection (host buffers): uv [n][2], vis [n] without a
  * depth test (1 = in front and inside the image, 0 otherwise). */

@@ -28,7 +28,12 @@ cropper would need (rgb + instance + obj_coords through Renderer.render).
 --rgb-filter chooses the RGB filter of every crop call (bilinear, or area: the
 box filter of minified windows, which reads every source pixel of such a
 window's RGB once per band of crop rows; `area_rgb_bytes` counts those pixels
-once, 3 B each, plus the 3 B per crop pixel written).  Writes one JSON file.
+once, 3 B each, plus the 3 B per crop pixel written).  --amodal adds the amodal
+masks (csg_crop_amodal) behind render + crops on the same stream, as variant
+`with_amodal`, and alone on the `info` the last crops left, `amodal_only`:
+`with_amodal - with_crops` is what the pass adds to a frame, and its yardstick is
+`render`, the frame rendered once more (what an amodal mask cost without the
+pass, per object).  Writes one JSON file.
 
     python tools/crop_cost.py --frames 480 --out profiles/object_crops/cost.json
 """
@@ -56,6 +61,7 @@ def main():
     ap.add_argument("--width", type=int)
     ap.add_argument("--height", type=int)
     ap.add_argument("--rgb-filter", choices=("bilinear", "area"), default="bilinear")
+    ap.add_argument("--amodal", action="store_true", help="also time csg_crop_amodal behind render + crops")
     ap.add_argument("--out", default=os.path.join("profiles", "object_crops", "cost.json"))
     a = ap.parse_args()
     import numpy as np
@@ -103,7 +109,15 @@ def main():
                            crop_coords=c_oc.data_ptr(), crop_depth=c_depth.data_ptr(), info=info.data_ptr(),
                            stream=stream.cuda_stream, rgb_filter=a.rgb_filter)
 
+        c_amodal = torch.empty((n, K, S, S), dtype=torch.uint8, device=dev) if a.amodal else None
+
+        def amodal():   # host frame records: the pass copies them itself
+            r.crop_amodal(fr, size=S, per_frame=K, info=info.data_ptr(), crop_amodal=c_amodal.data_ptr(),
+                          stream=stream.cuda_stream)
+
         variants = {"render": (render,), "with_crops": (render, crops), "crops_only": (crops,)}
+        if a.amodal:
+            variants.update({"with_amodal": (render, crops, amodal), "amodal_only": (amodal,)})
 
         def once(steps):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -123,6 +137,8 @@ def main():
                 times[k].append(once(steps))
         slots = info.cpu().numpy().view(CROP_INFO_DTYPE).reshape(n, K)
         mask_share = float((c_mask != 0).float().mean().item())
+        amodal_share = float((c_amodal != 0).float().mean().item()) if a.amodal else None
+        del c_amodal
 
         del rgb, inst, depth, oc, c_rgb, c_mask, c_oc, c_depth
         torch.cuda.empty_cache()
@@ -222,6 +238,14 @@ def main():
                         "speedup": round(hmed["whole_frames"] / hmed["crops"], 3),
                         "whole_host_bytes_per_frame": whole_bytes // hn, "instance_id_wire_bytes": id_wire,
                         "crops_host_bytes_per_frame": crop_bytes[0] // hn}}
+    if a.amodal:
+        added = med["with_amodal"] - med["with_crops"]
+        res["amodal"] = {"with_amodal_s": round(med["with_amodal"], 6), "amodal_only_s": round(med["amodal_only"], 6),
+                         "render_us_per_frame": round(med["render"] / n * 1e6, 2),
+                         "added_behind_crops_us_per_frame": round(added / n * 1e6, 2),
+                         "amodal_only_us_per_frame": round(med["amodal_only"] / n * 1e6, 2),
+                         "added_over_one_render": round(added / med["render"], 4),
+                         "amodal_pixel_share": round(amodal_share, 4)}
     if os.path.dirname(a.out):
         os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
