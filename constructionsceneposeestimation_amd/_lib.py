@@ -29,7 +29,7 @@ EXPORTED = (
     "csg_project_keypoints", "csg_timing_reset", "csg_timing_read", "csg_set_dr_light", "csg_set_dr_textures",
     "csg_instance_bounds", "csg_copy_files", "csg_host_alloc", "csg_host_free", "csg_size_work",
     "csg_get_work_info", "csg_host_id_bytes", "csg_set_object_frames", "csg_crop_objects", "csg_encode_files",
-    "csg_crop_objects_filtered", "csg_crop_amodal",
+    "csg_crop_objects_filtered", "csg_crop_amodal", "csg_crop_amodal_geometry",
 )
 
 
@@ -123,6 +123,12 @@ class AmodalJob(C.Structure):
                 ("crop_amodal", C.c_void_p)]
 
 
+class AmodalGeometryJob(C.Structure):
+    """csg_amodal_geometry_job (csg_crop_amodal_geometry)."""
+    _fields_ = [("size", C.c_uint32), ("per_frame", C.c_uint32), ("frames", C.c_void_p), ("info", C.c_void_p),
+                ("crop_amodal", C.c_void_p), ("crop_amodal_depth", C.c_void_p), ("crop_amodal_coords", C.c_void_p)]
+
+
 class EncodeJob(C.Structure):
     """csg_encode_job (csg_encode_files)."""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n_frames", C.c_uint32), ("file_kinds", C.c_uint32),
@@ -200,6 +206,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     lib.csg_crop_objects.argtypes = [vp, C.POINTER(CropJob), u32, vp]
     lib.csg_crop_objects_filtered.argtypes = [vp, C.POINTER(CropJob), u32, u32, vp]
     lib.csg_crop_amodal.argtypes = [vp, C.POINTER(AmodalJob), u32, vp]
+    lib.csg_crop_amodal_geometry.argtypes = [vp, C.POINTER(AmodalGeometryJob), u32, vp]
     lib.csg_encode_files.argtypes = [vp, C.POINTER(EncodeJob)]
     if lib.csg_abi_version() != ABI_VERSION:
         raise CsgError(f"libcsg.so ABI {lib.csg_abi_version()} != binding ABI {ABI_VERSION}; rebuild")

@@ -3,7 +3,8 @@
 geometry that goes with a crop -- its intrinsics and the keypoints in its
 pixels.  The crops themselves are made on the GPU
 (:meth:`renderer.Renderer.crop_objects`, :meth:`renderer.Renderer.render_crops`),
-and so are their amodal masks (:meth:`renderer.Renderer.crop_amodal`).
+and so are their amodal masks (:meth:`renderer.Renderer.crop_amodal`) and the
+amodal depth and object coordinates (:meth:`renderer.Renderer.crop_amodal_geometry`).
 
 A crop of side ``S`` samples the square source window ``x0, y0, side`` at
 ``x0 + (i + 0.5) * step``, ``step = side / S``: source pixel coordinate ``u``
@@ -51,6 +52,15 @@ def visible_fraction(crop_mask: np.ndarray, crop_amodal: np.ndarray) -> np.ndarr
     out = np.full(amo.shape, np.nan, np.float64)
     np.divide(vis, amo, out=out, where=amo > 0)
     return out
+
+
+def hidden_mask(crop_mask: np.ndarray, crop_amodal: np.ndarray) -> np.ndarray:
+    """The hidden samples of each crop, bool, shaped like the masks: on the
+    object (``crop_amodal`` set) and not visible (``crop_mask`` clear) -- where
+    ``crop_amodal_depth`` and ``crop_amodal_coords``
+    (:meth:`renderer.Renderer.crop_amodal_geometry`) say what ``crop_depth``
+    and ``crop_coords`` cannot."""
+    return (np.asarray(crop_amodal) != 0) & (np.asarray(crop_mask) == 0)
 
 
 def _steps(info: np.ndarray, S: int):

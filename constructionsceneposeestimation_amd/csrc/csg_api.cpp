@@ -236,6 +236,7 @@ struct csg_ctx {
   uint32_t lab_max_chunks = 0;            // the most chunks one label has
   DevBuf<FrameDev> am_frames;
   DevBuf<uint32_t> am_bits;
+  DevBuf<uint32_t> am_keys;               // csg_crop_amodal_geometry without a depth output: the key image
   FrameDev* am_stage[kStaging] = {};
   size_t am_stage_n[kStaging] = {};
   hipEvent_t am_stage_ev[kStaging] = {};
@@ -408,7 +409,7 @@ void csg_destroy(csg_ctx* c) {
     if (c->stage_ev[k]) (void)hipEventDestroy(c->stage_ev[k]);
   }
   if (c->am_busy) (void)hipEventSynchronize(c->am_done);   // a pass on a stream of the caller's
-  c->lab_off.release(); c->lab_chunks.release(); c->am_frames.release(); c->am_bits.release();
+  c->lab_off.release(); c->lab_chunks.release(); c->am_frames.release(); c->am_bits.release(); c->am_keys.release();
   for (uint32_t k = 0; k < csg_ctx::kStaging; ++k) {
     if (c->am_stage[k]) (void)hipHostFree(c->am_stage[k]);
     if (c->am_stage_ev[k]) (void)hipEventDestroy(c->am_stage_ev[k]);
@@ -855,6 +856,7 @@ static int sync_object_frames(csg_ctx* c) {
   if (!c->of_dirty && c->of_table_sets == n_sets && c->of.p) return CSG_OK;
   const int rc = drain(c);   // batches in flight read the table this rewrites
   if (rc) return rc;
+  if (c->am_busy) HIP_TRY(c, hipEventSynchronize(c->am_done));   // so does an amodal geometry pass, on any stream
   const size_t per = (size_t)c->n_lab * 12;
   std::vector<float> t((size_t)n_sets * per, 0.f);
   const size_t have = std::min<size_t>(c->of_sets, n_sets) * per;
@@ -2037,6 +2039,51 @@ int csg_crop_objects_filtered(csg_ctx* c, const csg_crop_job* job, uint32_t rgb_
   return CSG_OK;
 }
 
+}  // extern "C"
+
+// The shared front of the amodal passes (csg_crop_amodal, csg_crop_amodal_geometry): orders this pass
+// behind the last one, grows the pass's scratch (device frame records, n_bits words of bit image, n_keys
+// keys) and copies the caller's frame records through the pinned ring to am_frames on `st`.
+static int am_begin(csg_ctx* c, const csg_frame* frames, uint32_t n_frames, size_t n_bits, size_t n_keys,
+                    hipStream_t st) {
+  static_assert(sizeof(FrameDev) == sizeof(csg_frame), "frame layout");
+  if (!c->am_done) HIP_TRY(c, hipEventCreateWithFlags(&c->am_done, hipEventDisableTiming));
+  if (c->am_busy) {
+    if (c->am_frames.n < n_frames || c->am_bits.n < n_bits || c->am_keys.n < n_keys)
+      HIP_TRY(c, hipEventSynchronize(c->am_done));           // the last pass still reads what is freed below
+    else if (c->am_stream != st)
+      HIP_TRY(c, hipStreamWaitEvent(st, c->am_done, 0));     // ... or what this pass overwrites
+  }
+  HIP_TRY(c, c->am_frames.alloc(n_frames));
+  HIP_TRY(c, c->am_bits.alloc(n_bits));
+  HIP_TRY(c, c->am_keys.alloc(n_keys));
+  const uint32_t ring = c->am_stage_next;
+  c->am_stage_next = (ring + 1) % csg_ctx::kStaging;
+  if (!c->am_stage_ev[ring]) HIP_TRY(c, hipEventCreateWithFlags(&c->am_stage_ev[ring], hipEventDisableTiming));
+  else HIP_TRY(c, hipEventSynchronize(c->am_stage_ev[ring]));   // the slot's last H2D copy is done
+  if (c->am_stage_n[ring] < n_frames) {
+    if (c->am_stage[ring]) HIP_TRY(c, hipHostFree(c->am_stage[ring]));
+    c->am_stage[ring] = nullptr;
+    c->am_stage_n[ring] = 0;
+    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->am_stage[ring]), sizeof(FrameDev) * n_frames));
+    c->am_stage_n[ring] = n_frames;
+  }
+  memcpy(c->am_stage[ring], frames, sizeof(FrameDev) * n_frames);
+  HIP_TRY(c, hipMemcpyAsync(c->am_frames.p, c->am_stage[ring], sizeof(FrameDev) * n_frames, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipEventRecord(c->am_stage_ev[ring], st));
+  return CSG_OK;
+}
+
+// ... and their end: am_done marks the pass's completion on `st`.
+static int am_end(csg_ctx* c, hipStream_t st) {
+  HIP_TRY(c, hipEventRecord(c->am_done, st));
+  c->am_stream = st;
+  c->am_busy = true;
+  return CSG_OK;
+}
+
+extern "C" {
+
 // Amodal crop masks: reads the scene tables (synced here as a render syncs them) and the caller's
 // `info`; everything it writes besides the output is scratch of its own.
 int csg_crop_amodal(csg_ctx* c, const csg_amodal_job* job, uint32_t n_frames, void* stream) {
@@ -2061,32 +2108,10 @@ int csg_crop_amodal(csg_ctx* c, const csg_amodal_job* job, uint32_t n_frames, vo
   hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
   int rc = sync_scene_state(c);
   if (rc) return rc;
-  static_assert(sizeof(FrameDev) == sizeof(csg_frame), "frame layout");
   const uint32_t S = job->size, K = job->per_frame, words = (S * S + 31u) / 32u;
   const size_t n_bits = (size_t)n_frames * K * words;
-  if (!c->am_done) HIP_TRY(c, hipEventCreateWithFlags(&c->am_done, hipEventDisableTiming));
-  if (c->am_busy) {
-    if (c->am_frames.n < n_frames || c->am_bits.n < n_bits)
-      HIP_TRY(c, hipEventSynchronize(c->am_done));           // the last pass still reads what is freed below
-    else if (c->am_stream != st)
-      HIP_TRY(c, hipStreamWaitEvent(st, c->am_done, 0));     // ... or what this pass overwrites
-  }
-  HIP_TRY(c, c->am_frames.alloc(n_frames));
-  HIP_TRY(c, c->am_bits.alloc(n_bits));
-  const uint32_t ring = c->am_stage_next;
-  c->am_stage_next = (ring + 1) % csg_ctx::kStaging;
-  if (!c->am_stage_ev[ring]) HIP_TRY(c, hipEventCreateWithFlags(&c->am_stage_ev[ring], hipEventDisableTiming));
-  else HIP_TRY(c, hipEventSynchronize(c->am_stage_ev[ring]));   // the slot's last H2D copy is done
-  if (c->am_stage_n[ring] < n_frames) {
-    if (c->am_stage[ring]) HIP_TRY(c, hipHostFree(c->am_stage[ring]));
-    c->am_stage[ring] = nullptr;
-    c->am_stage_n[ring] = 0;
-    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->am_stage[ring]), sizeof(FrameDev) * n_frames));
-    c->am_stage_n[ring] = n_frames;
-  }
-  memcpy(c->am_stage[ring], job->frames, sizeof(FrameDev) * n_frames);
-  HIP_TRY(c, hipMemcpyAsync(c->am_frames.p, c->am_stage[ring], sizeof(FrameDev) * n_frames, hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipEventRecord(c->am_stage_ev[ring], st));
+  rc = am_begin(c, job->frames, n_frames, n_bits, 0, st);
+  if (rc) return rc;
   HIP_TRY(c, hipMemsetAsync(c->am_bits.p, 0, n_bits * sizeof(uint32_t), st));
   AmodalDev a{};
   a.S = S;
@@ -2105,10 +2130,83 @@ int csg_crop_amodal(csg_ctx* c, const csg_amodal_job* job, uint32_t n_frames, vo
   a.out = job->crop_amodal;
   launch_crop_amodal(scene_dev(c), a, n_frames, c->lab_max_chunks, st);
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipEventRecord(c->am_done, st));
-  c->am_stream = st;
-  c->am_busy = true;
-  return CSG_OK;
+  return am_end(c, st);
+}
+
+// Amodal depth and object coordinates: the same pass keeping, per sample, the largest 1/W instead of a
+// bit.  The keys (4 B per sample) live in crop_amodal_depth when it is given -- the finish pass converts
+// them in place --, else in scratch of the pass's own, bounded at kAmKeyCap bytes: the job then runs as
+// frame ranges on the stream, each zeroing, filling and finishing the same scratch.
+int csg_crop_amodal_geometry(csg_ctx* c, const csg_amodal_geometry_job* job, uint32_t n_frames, void* stream) {
+  constexpr size_t kAmKeyCap = 64u << 20;
+  if (!c) return CSG_ERR_INVALID;
+  if (!job) return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: null job");
+  if (n_frames == 0) return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: no frames");
+  if (job->size < 16 || job->size > 512 || (job->size & 3u))
+    return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: size %u is not a multiple of 4 in 16..512", job->size);
+  if (job->per_frame < 1 || job->per_frame > 64)
+    return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: per_frame %u outside 1..64", job->per_frame);
+  if (!job->frames) return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: frames is NULL");
+  if (!job->info) return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: info is NULL");
+  if (!job->crop_amodal && !job->crop_amodal_depth && !job->crop_amodal_coords)
+    return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: crop_amodal, crop_amodal_depth and crop_amodal_coords "
+                                    "are all NULL");
+  if (((uintptr_t)job->crop_amodal & 3u) || ((uintptr_t)job->info & 3u) || ((uintptr_t)job->crop_amodal_depth & 15u) ||
+      ((uintptr_t)job->crop_amodal_coords & 7u))
+    return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: crop_amodal and info must be 4-byte aligned, "
+                                    "crop_amodal_coords 8-byte, crop_amodal_depth 16-byte");
+  if (!c->have_scene) return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: no scene uploaded");
+  for (uint32_t f = 0; f < n_frames; ++f)
+    if (job->frames[f].xform_set >= c->set_valid.size())
+      return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: frame %u: transform set %u is not resident (%u sets)", f,
+                     job->frames[f].xform_set, (unsigned)c->set_valid.size());
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+  int rc = sync_scene_state(c);
+  if (rc) return rc;
+  if (job->crop_amodal_coords) {
+    rc = sync_object_frames(c);
+    if (rc) return rc;
+  }
+  const uint32_t S = job->size, K = job->per_frame;
+  const size_t per_frame = (size_t)K * S * S;   // samples, and keys, of one frame
+  uint32_t range = n_frames;                    // frames per range; the depth output holds every key
+  if (!job->crop_amodal_depth) {
+    size_t cap = kAmKeyCap;
+    if (const char* e = getenv("CSG_AMODAL_KEY_CAP")) cap = (size_t)strtoull(e, nullptr, 10);   // (tests: bytes)
+    range = (uint32_t)std::min<size_t>(n_frames, std::max<size_t>(1, cap / (per_frame * sizeof(uint32_t))));
+  }
+  rc = am_begin(c, job->frames, n_frames, 0, job->crop_amodal_depth ? 0 : (size_t)range * per_frame, st);
+  if (rc) return rc;
+  AmodalDev a{};
+  a.S = S;
+  a.K = K;
+  a.n_labels = c->n_lab;
+  a.n_sets = (uint32_t)c->set_valid.size();
+  a.words = S * S;
+  a.lab_off = c->lab_off.p;
+  a.lab_chunks = c->lab_chunks.p;
+  a.chunks = c->chunks.p;
+  a.models = c->models.p;
+  a.iset = c->iset.p;
+  AmodalGeomOut g{};
+  g.W = c->cfg.width;
+  g.H = c->cfg.height;
+  g.table = c->of.p;
+  for (uint32_t f0 = 0; f0 < n_frames; f0 += range) {   // every array from the range's first frame
+    const uint32_t nf = std::min(range, n_frames - f0);
+    const size_t at = (size_t)f0 * per_frame;
+    a.frames = c->am_frames.p + f0;
+    a.info = reinterpret_cast<const CropSlot*>(job->info) + (size_t)f0 * K;
+    g.mask = job->crop_amodal ? job->crop_amodal + at : nullptr;
+    g.depth = job->crop_amodal_depth ? job->crop_amodal_depth + at : nullptr;
+    g.coords = job->crop_amodal_coords ? job->crop_amodal_coords + at * 3 : nullptr;
+    a.bits = g.depth ? reinterpret_cast<uint32_t*>(g.depth) : c->am_keys.p;
+    HIP_TRY(c, hipMemsetAsync(a.bits, 0, (size_t)nf * per_frame * sizeof(uint32_t), st));
+    launch_crop_amodal_geometry(scene_dev(c), a, g, nf, c->lab_max_chunks, st);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return am_end(c, st);
 }
 
 }  // extern "C"

@@ -252,6 +252,18 @@ struct AmodalDev {
 };
 // max_chunks: the largest number of chunks one label has (k_amodal's grid x; 0: no label has any)
 void launch_crop_amodal(const SceneDev& s, const AmodalDev& a, uint32_t n, uint32_t max_chunks, hipStream_t st);
+// Amodal depth and object coordinates (csg_crop_amodal_geometry): the depth-keeping k_amodal maxes the
+// bits of each hit's 1/W into a key image -- a.bits as [n][K][S * S] keys with a.words = S * S, zeroed by
+// the caller; a.out is unused -- and k_amodal_geom_expand writes the requested outputs from the keys.
+struct AmodalGeomOut {
+  uint32_t W, H;                 // source frames
+  uint8_t* mask;                 // [n][K][S][S] or null
+  float* depth;                  // [n][K][S][S] or null; may be the key image itself
+  uint16_t* coords;              // [n][K][S][S][3] or null
+  const float* table;            // [a.n_sets][a.n_labels][12] world -> unit box (needed with coords)
+};
+void launch_crop_amodal_geometry(const SceneDev& s, const AmodalDev& a, const AmodalGeomOut& g, uint32_t n,
+                                 uint32_t max_chunks, hipStream_t st);
 // ids [lo, hi) of the int32 instance image as (id + 1) in `bytes` (1 or 2) bytes (the host wire)
 void launch_narrow_ids(const int32_t* src, size_t lo, size_t hi, uint32_t bytes, void* dst, hipStream_t st);
 

@@ -2651,6 +2651,16 @@ void launch_narrow_ids(const int32_t* src, size_t lo, size_t hi, uint32_t bytes,
 // non-zero words go by atomicOr into the pass's zeroed global bit image, and
 // k_amodal_expand turns bits into 255 / 0 bytes, writing every byte of the
 // output.  OR is order-free, so the result is deterministic.
+//
+// k_amodal_depth (csg_crop_amodal_geometry) is the same pass
+// keeping depth: same grid, arithmetic, sample rectangles and load balance
+// (amodal_pass<true>), but a hit raises its sample's key -- the bits of its 1/W,
+// positive floats, so the unsigned order is the value order -- in a zeroed
+// global key image [n][K][S * S] by a device-scope atomicMax behind a plain read
+// that skips a hit which cannot win.  No LDS image: 4 B per sample do not fit
+// (S = 512: 1 MB), and the variant that maxed a block's sample rectangle in LDS
+// first measured slower (§13.3).  Max is order-free too.  k_amodal_geom_expand
+// turns the keys into mask, depth and object coordinates.
 // ---------------------------------------------------------------------------
 constexpr uint32_t kAmSerial = 16;   // samples a lane tests itself
 constexpr uint32_t kAmQueue = 64;    // larger sub-triangles queued per round
@@ -2664,7 +2674,9 @@ struct AmTri {   // what the sample test needs of one raster sub-triangle
 };
 
 // Spec §3.3 / §3.5 / §3.6 at the centre of pixel (px, py): covered, in the depth range, alpha passed.
-__device__ __forceinline__ bool amodal_hit(const SceneDev& s, const AmTri& t, int32_t px, int32_t py) {
+// With kKey a hit also leaves the bits of the fragment's 1/W in `key` (>= 1/far > 0, so never 0).
+template <bool kKey>
+__device__ __forceinline__ bool amodal_hit(const SceneDev& s, const AmTri& t, int32_t px, int32_t py, uint32_t& key) {
   const int32_t cx = px * 256 + 128, cy = py * 256 + 128;
   const int ea[3] = {1, 2, 0}, eb[3] = {2, 0, 1};
   bool in = true;
@@ -2678,6 +2690,7 @@ __device__ __forceinline__ bool amodal_hit(const SceneDev& s, const AmTri& t, in
   const float fx = (float)px + 0.5f, fy = (float)py + 0.5f;
   const float invw = plane_at(t.D[0], t.D[1], t.D[2], fx, fy);
   if (!(invw >= s.inv_far && invw <= s.inv_near)) return false;
+  if constexpr (kKey) key = __float_as_uint(invw);
   if (t.atex == kNoAlpha) return true;
   const float r = rcp_ieee(invw);   // invw in [1/far, 1/near]
   const float u = plane_at(t.U[0], t.U[1], t.U[2], fx, fy) * r, v = plane_at(t.V[0], t.V[1], t.V[2], fx, fy) * r;
@@ -2695,8 +2708,9 @@ __device__ __forceinline__ uint32_t am_lower(const int32_t* tab, uint32_t n, int
   return lo;
 }
 
-__global__ __launch_bounds__(kBlock) void k_amodal(SceneDev s, AmodalDev a, uint32_t f0) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t am_bits[];   // [a.words] the slot's samples as bits
+template <bool kGeom>
+__device__ __forceinline__ void amodal_pass(const SceneDev& s, const AmodalDev& a, uint32_t f0) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t am_bits[];   // mask: [a.words] the slot's samples as bits
   __shared__ int32_t colpx[512], rowpy[512];
   __shared__ float clipm[12];
   __shared__ AmTri queue[kAmQueue];
@@ -2721,7 +2735,9 @@ __global__ __launch_bounds__(kBlock) void k_amodal(SceneDev s, AmodalDev a, uint
     colpx[t] = crop_sample_in(sx, (float)s.W) ? (int32_t)floorf(sx) : (sx < 0.0f ? -1 : kAmPast);
     rowpy[t] = crop_sample_in(sy, (float)s.H) ? (int32_t)floorf(sy) : (sy < 0.0f ? -1 : kAmPast);
   }
-  for (uint32_t w = tid; w < a.words; w += kBlock) am_bits[w] = 0u;
+  if constexpr (!kGeom) {
+    for (uint32_t w = tid; w < a.words; w += kBlock) am_bits[w] = 0u;
+  }
   if (tid == 0) {   // the instance's clip rows, as k_clip forms them
     const float* M = a.models + ((size_t)set * s.n_inst + inst) * 16;
     float m[16], vm[16], c[16];
@@ -2738,9 +2754,20 @@ __global__ __launch_bounds__(kBlock) void k_amodal(SceneDev s, AmodalDev a, uint
   }
   __syncthreads();
 
-  auto mark = [&](uint32_t i, uint32_t j) {
-    const uint32_t p = j * S + i;
-    atomicOr(&am_bits[p >> 5], 1u << (p & 31u));
+  // kGeom: the slot's key image (a.bits, a.words = S * S keys): a hit raises its sample's key to the bits
+  // of its 1/W.  The plain read in front may be stale, which only ever shows a smaller key: it can cost
+  // an atomic, never drop a hit.  Device scope: the blocks of a slot run on different XCDs.
+  auto raise = [&](uint32_t p, uint32_t key) {
+    uint32_t* g = a.bits + slot * a.words + p;
+    if (*g < key) atomicMax(g, key);
+  };
+  auto mark = [&](uint32_t i, uint32_t j, uint32_t key) {
+    if constexpr (!kGeom) {
+      const uint32_t p = j * S + i;
+      atomicOr(&am_bits[p >> 5], 1u << (p & 31u));
+    } else {
+      raise(j * S + i, key);
+    }
   };
 
   // k_setup's per-triangle arithmetic (setup_chunk), kept in the same order
@@ -2865,7 +2892,8 @@ __global__ __launch_bounds__(kBlock) void k_amodal(SceneDev s, AmodalDev a, uint
     for (uint32_t q = 0; q < t.ni * t.nj; ++q) {
       const uint32_t jj = small_div(q, t.ni), ii = q - jj * t.ni;
       const uint32_t i = t.i0 + ii, j = t.j0 + jj;
-      if (amodal_hit(s, t, colpx[i], rowpy[j])) mark(i, j);
+      uint32_t key = 0u;
+      if (amodal_hit<kGeom>(s, t, colpx[i], rowpy[j], key)) mark(i, j, key);
     }
   };
   bool p0 = nrec > 0 && t0.ni * t0.nj > kAmSerial, p1 = nrec > 1 && t1.ni * t1.nj > kAmSerial;
@@ -2891,17 +2919,27 @@ __global__ __launch_bounds__(kBlock) void k_amodal(SceneDev s, AmodalDev a, uint
       for (uint32_t q = tid; q < cnt; q += kBlock) {
         const uint32_t jj = small_div(q, ni), ii = q - jj * ni;
         const uint32_t i = t.i0 + ii, j = t.j0 + jj;
-        if (amodal_hit(s, t, colpx[i], rowpy[j])) mark(i, j);
+        uint32_t key = 0u;
+        if (amodal_hit<kGeom>(s, t, colpx[i], rowpy[j], key)) mark(i, j, key);
       }
     }
     if (!__syncthreads_or((int)(p0 || p1))) break;   // also orders this round's queue reads before the next writes
   }
   // (the closing barrier above ordered every mark before these reads)
-  uint32_t* gb = a.bits + slot * a.words;
-  for (uint32_t w = tid; w < a.words; w += kBlock) {
-    const uint32_t v = am_bits[w];
-    if (v) atomicOr(&gb[w], v);
+  if constexpr (!kGeom) {
+    uint32_t* gb = a.bits + slot * a.words;
+    for (uint32_t w = tid; w < a.words; w += kBlock) {
+      const uint32_t v = am_bits[w];
+      if (v) atomicOr(&gb[w], v);
+    }
   }
+}
+
+__global__ __launch_bounds__(kBlock) void k_amodal(SceneDev s, AmodalDev a, uint32_t f0) {
+  amodal_pass<false>(s, a, f0);
+}
+__global__ __launch_bounds__(kBlock) void k_amodal_depth(SceneDev s, AmodalDev a, uint32_t f0) {
+  amodal_pass<true>(s, a, f0);
 }
 
 // bits -> 255 / 0: one thread expands 4 consecutive samples (S * S is a multiple
@@ -2919,6 +2957,70 @@ __global__ __launch_bounds__(256) void k_amodal_expand(AmodalDev a, uint32_t f0)
   __builtin_nontemporal_store(m, reinterpret_cast<uint32_t*>(a.out + slot * a.S * a.S + p));
 }
 
+// keys -> mask, depth and object coordinates (csg_crop_amodal_geometry): one thread
+// finishes 4 consecutive samples of a crop row from one 16-B load of their keys (a.bits, a.words = S * S)
+// and writes the mask as one dword, the depth as one 16-B store and the coordinates as three 8-B stores,
+// all non-temporal, as k_crop_sample and k_obj_coords store theirs.  g.depth may be the key image itself:
+// a thread reads its keys before it writes them over.  A key is the largest 1/W of the sample's fragments,
+// so 1 / key by the resolve's reciprocal is the depth the raster would write for the object alone, and
+// obj_coord at the sample's source pixel with that depth is k_obj_coords' value.  Dead slots (block-
+// uniform) only write the empty values; the frame's camera constants are formed once per block.
+__global__ __launch_bounds__(256) void k_amodal_geom_expand(AmodalDev a, AmodalGeomOut g, uint32_t f0) {
+  __shared__ float cam[kCamFloats];
+  const uint32_t S = a.S, qrow = S >> 2;
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  const uint32_t f = f0 + blockIdx.z;
+  const size_t slot = (size_t)f * a.K + blockIdx.y;
+  const CropSlot sl = a.info[slot];
+  const size_t o = slot * S * S + 4u * (size_t)q;   // the thread's first sample
+  const bool mine = q < qrow * S;
+  const FrameDev& fr = a.frames[f];
+  const uint32_t set = fr.xform_set;
+  if (!crop_label_live(sl, a.n_labels) || !crop_window_live(sl) || set >= a.n_sets) {   // (its keys are zero)
+    if (!mine) return;
+    if (g.mask) __builtin_nontemporal_store(0u, reinterpret_cast<uint32_t*>(g.mask + o));
+    if (g.coords) {
+#pragma unroll
+      for (int t = 0; t < 3; ++t)
+        __builtin_nontemporal_store(v2u32{0u, 0u}, reinterpret_cast<v2u32*>(g.coords + o * 3 + 4 * t));
+    }
+    if (g.depth)
+      __builtin_nontemporal_store(v4f32{INFINITY, INFINITY, INFINITY, INFINITY}, reinterpret_cast<v4f32*>(g.depth + o));
+    return;
+  }
+  if (g.coords && threadIdx.x == 0) frame_camera(fr.view, fr.proj, cam);
+  __syncthreads();
+  if (!mine) return;
+  const v4u32 kv = *reinterpret_cast<const v4u32*>(a.bits + o);
+  const uint32_t key[4] = {kv.x, kv.y, kv.z, kv.w};
+  const uint32_t j = q / qrow, i0 = (q - j * qrow) * 4u;
+  const float step = crop_step(sl, S);
+  const float sy = crop_sample_pos(sl.y0, j, step);
+  const bool yin = crop_sample_in(sy, (float)g.H);
+  const int py = yin ? (int)floorf(sy) : 0;
+  const float* tab = g.coords ? g.table + (size_t)set * a.n_labels * 12 : nullptr;   // set < a.n_sets
+  uint32_t m = 0u, h[12];
+  float d[4];
+#pragma unroll
+  for (uint32_t t = 0; t < 4; ++t) {
+    const float sx = crop_sample_pos(sl.x0, i0 + t, step);
+    // (k_amodal tests inside samples only: a key outside the frame does not occur)
+    const bool hit = key[t] != 0u && yin && crop_sample_in(sx, (float)g.W);
+    m |= hit ? (255u << (8 * t)) : 0u;
+    d[t] = hit ? rcp_ieee(__uint_as_float(key[t])) : INFINITY;   // key in [1/far, 1/near]
+    h[3 * t] = h[3 * t + 1] = h[3 * t + 2] = 0u;
+    if (g.coords && hit) obj_coord(tab, a.n_labels, cam, (int)floorf(sx), py, sl.label, d[t], h + 3 * t);
+  }
+  if (g.mask) __builtin_nontemporal_store(m, reinterpret_cast<uint32_t*>(g.mask + o));
+  if (g.coords) {
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+      __builtin_nontemporal_store(v2u32{h[4 * t] | (h[4 * t + 1] << 16), h[4 * t + 2] | (h[4 * t + 3] << 16)},
+                                  reinterpret_cast<v2u32*>(g.coords + o * 3 + 4 * t));
+  }
+  if (g.depth) __builtin_nontemporal_store(v4f32{d[0], d[1], d[2], d[3]}, reinterpret_cast<v4f32*>(g.depth + o));
+}
+
 void launch_crop_amodal(const SceneDev& s, const AmodalDev& a, uint32_t n, uint32_t max_chunks, hipStream_t st) {
   const uint32_t quads = a.S * a.S / 4u;
   for (uint32_t f0 = 0; f0 < n; f0 += 65535u) {   // grid z limit
@@ -2926,6 +3028,16 @@ void launch_crop_amodal(const SceneDev& s, const AmodalDev& a, uint32_t n, uint3
     if (max_chunks)
       hipLaunchKernelGGL(k_amodal, dim3(max_chunks, a.K, nf), dim3(kBlock), a.words * sizeof(uint32_t), st, s, a, f0);
     hipLaunchKernelGGL(k_amodal_expand, dim3((quads + 255u) / 256u, a.K, nf), dim3(256), 0, st, a, f0);
+  }
+}
+
+void launch_crop_amodal_geometry(const SceneDev& s, const AmodalDev& a, const AmodalGeomOut& g, uint32_t n,
+                                 uint32_t max_chunks, hipStream_t st) {
+  const uint32_t quads = a.S * a.S / 4u;
+  for (uint32_t f0 = 0; f0 < n; f0 += 65535u) {   // grid z limit
+    const uint32_t nf = n - f0 < 65535u ? n - f0 : 65535u;
+    if (max_chunks) hipLaunchKernelGGL(k_amodal_depth, dim3(max_chunks, a.K, nf), dim3(kBlock), 0, st, s, a, f0);
+    hipLaunchKernelGGL(k_amodal_geom_expand, dim3((quads + 255u) / 256u, a.K, nf), dim3(256), 0, st, a, g, f0);
   }
 }
 

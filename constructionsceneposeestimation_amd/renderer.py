@@ -429,6 +429,23 @@ class Renderer:
         self._check(self.lib.csg_crop_amodal(self.ctx, C.byref(job), int(frames.shape[0]), stream or None),
                     "crop_amodal")
 
+    def crop_amodal_geometry(self, frames: np.ndarray, *, size: int, per_frame: int, info: int, crop_amodal: int = 0,
+                             crop_amodal_depth: int = 0, crop_amodal_coords: int = 0, stream: int = 0) -> None:
+        """Enqueue the amodal geometry of the crops of ``frames``
+        (csg_crop_amodal_geometry; arguments as :meth:`crop_amodal`): the
+        object's own depth and object coordinates over its whole silhouette,
+        hidden parts included, into ``crop_amodal_depth`` (n, K, S, S) float32
+        (+inf off the object) and ``crop_amodal_coords`` (n, K, S, S, 3) uint16
+        (0 off the object; they need the object-frame tables of
+        :meth:`set_object_frames`), and the amodal mask of :meth:`crop_amodal`
+        into ``crop_amodal``.  Any of the three may be 0, not all.  Under
+        ``crop_mask`` the two equal ``crop_depth`` and ``crop_coords``."""
+        frames = np.ascontiguousarray(frames, FRAME_DTYPE)
+        job = _lib.AmodalGeometryJob(int(size), int(per_frame), frames.ctypes.data, info or None, crop_amodal or None,
+                                     crop_amodal_depth or None, crop_amodal_coords or None)
+        self._check(self.lib.csg_crop_amodal_geometry(self.ctx, C.byref(job), int(frames.shape[0]), stream or None),
+                    "crop_amodal_geometry")
+
     def render_crops(self, frames: np.ndarray, size: int = 128, per_frame: int = 8, min_pixels: int = 64,
                      pad: float = 1.5, kinds: Sequence[str] = DYNAMIC_KINDS,
                      want: Iterable[str] = ("rgb", "mask", "coords"), object_frames=None,
@@ -437,9 +454,14 @@ class Renderer:
         chunks of ``max_frames`` are rendered into device tensors (torch),
         cropped on the same stream, and the crops and their ``info`` copied to
         page-locked host arrays; whole frames never cross PCIe.  ``want``
-        chooses among "rgb", "mask", "coords", "depth" and "amodal" (the
+        chooses among "rgb", "mask", "coords", "depth", "amodal" (the
         unoccluded mask of :meth:`crop_amodal`, as ``crop_amodal`` (n, K, S, S)
-        uint8, made behind the crops of each chunk); ``kinds`` the object
+        uint8, made behind the crops of each chunk), "amodal_depth" and
+        "amodal_coords" (``crop_amodal_depth`` float32 and
+        ``crop_amodal_coords`` uint16 of :meth:`crop_amodal_geometry`, one
+        geometry pass per chunk, which also makes the amodal mask when that is
+        wanted with them; the coordinates need the tables "coords" needs);
+        ``kinds`` the object
         kinds that may be cropped (:func:`crops.eligible_labels`).  Returns
         ``crop_rgb`` / ``crop_mask`` / ``crop_coords`` / ``crop_depth`` (those
         wanted, shaped as :meth:`crop_objects` says), ``info`` (n, K) and
@@ -458,9 +480,9 @@ class Renderer:
         frames = np.ascontiguousarray(frames, FRAME_DTYPE)
         n, S, K, H, W = frames.shape[0], int(size), int(per_frame), self.height, self.width
         want = set(want)
-        if not want or want - {"rgb", "mask", "coords", "depth", "amodal"}:
+        if not want or want - {"rgb", "mask", "coords", "depth", "amodal", "amodal_depth", "amodal_coords"}:
             raise CsgError(f"render_crops: want {sorted(want)} must be a non-empty subset of rgb, mask, coords, depth, "
-                           "amodal")
+                           "amodal, amodal_depth, amodal_coords")
         for set_id, of in (object_frames or {}).items():
             self.set_object_frames(int(set_id), of)
         dev = torch.device("cuda", self.device)
@@ -479,6 +501,8 @@ class Renderer:
         shapes = {"crop_rgb": ("rgb", (K, S, S, 3), torch.uint8), "crop_mask": ("mask", (K, S, S), torch.uint8),
                   "crop_coords": ("coords", (K, S, S, 3), torch.int16), "crop_depth": ("depth", (K, S, S), torch.float32),
                   "crop_amodal": ("amodal", (K, S, S), torch.uint8),
+                  "crop_amodal_depth": ("amodal_depth", (K, S, S), torch.float32),
+                  "crop_amodal_coords": ("amodal_coords", (K, S, S, 3), torch.int16),
                   "info": (None, (K, CROP_INFO_DTYPE.itemsize), torch.uint8)}
         d_out = {k: dbuf(w is None or w in want, (m,) + sh, dt) for k, (w, sh, dt) in shapes.items()}
         h_out = {k: torch.empty((n,) + sh, dtype=dt, pin_memory=True)
@@ -498,7 +522,13 @@ class Renderer:
                                   crop_rgb=ptr(d_out["crop_rgb"]), crop_mask=ptr(d_out["crop_mask"]),
                                   crop_coords=ptr(d_out["crop_coords"]), crop_depth=ptr(d_out["crop_depth"]),
                                   info=ptr(d_out["info"]), stream=stream.cuda_stream, rgb_filter=rgb_filter)
-                if "amodal" in want:
+                if want & {"amodal_depth", "amodal_coords"}:   # (makes the mask too when it is wanted)
+                    self.crop_amodal_geometry(frames[s:e], size=S, per_frame=K, info=ptr(d_out["info"]),
+                                              crop_amodal=ptr(d_out["crop_amodal"]),
+                                              crop_amodal_depth=ptr(d_out["crop_amodal_depth"]),
+                                              crop_amodal_coords=ptr(d_out["crop_amodal_coords"]),
+                                              stream=stream.cuda_stream)
+                elif "amodal" in want:
                     self.crop_amodal(frames[s:e], size=S, per_frame=K, info=ptr(d_out["info"]),
                                      crop_amodal=ptr(d_out["crop_amodal"]), stream=stream.cuda_stream)
                 for k, h in h_out.items():
@@ -506,8 +536,9 @@ class Renderer:
         stream.synchronize()
         self.synchronize()
         out = {k: h.numpy() for k, h in h_out.items()}
-        if "crop_coords" in out:
-            out["crop_coords"] = out["crop_coords"].view(np.uint16)
+        for k in ("crop_coords", "crop_amodal_coords"):
+            if k in out:
+                out[k] = out[k].view(np.uint16)
         info = out["info"].view(CROP_INFO_DTYPE).reshape(n, K)
         # (the kernel numbers frames within a chunk: here they index `frames`)
         info["frame"] = np.where(info["label"] >= 0, np.arange(n, dtype=np.uint32)[:, None], np.uint32(0))

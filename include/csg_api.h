@@ -58,6 +58,8 @@
  *                               `mask` next to `mask_visib`), rasterised from the scene
  *                               at the crop's own sample positions; the reference
  *                               would render the frame once more per object
+ *   csg_crop_amodal_geometry .. (new) the amodal depth and object coordinates of each
+ *                               crop (and its amodal mask) from one pass of the same kind
  *   csg_last_error / csg_destroy
  *
  * Threading: several contexts may share a device (each has its own stream
@@ -601,6 +603,49 @@ typedef struct {
   uint8_t* crop_amodal;        /* DEVICE [n][K][S][S], 255 / 0, 4-B aligned */
 } csg_amodal_job;
 int csg_crop_amodal(csg_ctx* ctx, const csg_amodal_job* job, uint32_t n_frames, void* stream);
+
+/* Amodal depth and object coordinates of the crops: the geometry that belongs
+ * to the amodal mask, made by the same pass.  For sample (i, j) of a live slot
+ * with label L (px, py and `inside` as above) let H be the set of fragments
+ * csg_crop_amodal counts at pixel (px, py): triangles of instances with
+ * inst_idx == L, covered, 1/W in [1/far_clip, 1/near_clip], alpha passed under the
+ * frame's transform set; no depth test against other objects.
+ *   crop_amodal         255 iff the sample is inside and H is not empty: byte for
+ *                       byte what csg_crop_amodal writes.
+ *   crop_amodal_depth   1 / w*, w* = the largest 1/W over H (compared as float32
+ *                       bits: all are positive, so the bit order is the value
+ *                       order), by the resolve's correctly rounded reciprocal;
+ *                       +inf where H is empty.  It is the depth of a render of
+ *                       the frame with every instance of another label removed,
+ *                       and depends only on the maximum, not on the triangle that
+ *                       supplied it.
+ *   crop_amodal_coords  the object coordinates (csg_outputs.obj_coords) of pixel
+ *                       (px, py) with that depth and label L: the frame's camera
+ *                       constants and the object-frame table of its transform
+ *                       set (csg_set_object_frames); (0, 0, 0) where H is empty
+ *                       and for a set without a table.
+ * Dead slots write 0, +inf and (0, 0, 0); every byte of every requested output
+ * is written; no `info` value yields an address outside the arrays.  So wherever
+ * crop_mask of the same slot is 255, crop_amodal_depth and crop_amodal_coords
+ * equal crop_depth and crop_coords bit for bit, and at an inside sample where
+ * only crop_amodal is 255 the amodal depth is >= the frame's depth at (px, py).
+ *
+ * At least one output is non-NULL.  Argument rules, slot liveness, stream and
+ * ownership semantics are csg_crop_amodal's (messages start with
+ * "crop_amodal_geometry:"); pending scene changes and, when coordinates are
+ * asked for, the object-frame table are brought up to date first, as by a render.
+ * Scratch: 4 bytes per sample while the pass runs.  crop_amodal_depth, when
+ * given, holds them itself; otherwise the pass has a bounded buffer of its own
+ * and runs the job as frame ranges on the stream. */
+typedef struct {
+  uint32_t size, per_frame;          /* as csg_amodal_job */
+  const csg_frame* frames;           /* HOST [n], copied before the call returns */
+  const csg_crop_info* info;         /* DEVICE [n][K], read only */
+  uint8_t* crop_amodal;              /* DEVICE [n][K][S][S] 255 / 0, 4-B aligned, or NULL */
+  float* crop_amodal_depth;          /* DEVICE [n][K][S][S], 16-B aligned, or NULL */
+  uint16_t* crop_amodal_coords;      /* DEVICE [n][K][S][S][3], 8-B aligned, or NULL */
+} csg_amodal_geometry_job;
+int csg_crop_amodal_geometry(csg_ctx* ctx, const csg_amodal_geometry_job* job, uint32_t n_frames, void* stream);
 
 /* Stand-alone 3D->2D projection (host buffers): uv [n][2], vis [n] without a
  * depth test (1 = in front and inside the image, 0 otherwise). */

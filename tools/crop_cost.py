@@ -33,7 +33,11 @@ masks (csg_crop_amodal) behind render + crops on the same stream, as variant
 `with_amodal`, and alone on the `info` the last crops left, `amodal_only`:
 `with_amodal - with_crops` is what the pass adds to a frame, and its yardstick is
 `render`, the frame rendered once more (what an amodal mask cost without the
-pass, per object).  Writes one JSON file.
+pass, per object).  --amodal-geometry (implies --amodal) adds
+csg_crop_amodal_geometry with all three outputs the same two ways, as
+`with_amodal_geometry` and `amodal_geometry_only`, beside the mask-only pass in
+the same alternation: what the geometry pass adds to a frame, its ratio to the
+mask-only pass and to `render`.  Writes one JSON file.
 
     python tools/crop_cost.py --frames 480 --out profiles/object_crops/cost.json
 """
@@ -62,8 +66,11 @@ def main():
     ap.add_argument("--height", type=int)
     ap.add_argument("--rgb-filter", choices=("bilinear", "area"), default="bilinear")
     ap.add_argument("--amodal", action="store_true", help="also time csg_crop_amodal behind render + crops")
+    ap.add_argument("--amodal-geometry", action="store_true",
+                    help="also time csg_crop_amodal_geometry (mask, depth and coordinates); implies --amodal")
     ap.add_argument("--out", default=os.path.join("profiles", "object_crops", "cost.json"))
     a = ap.parse_args()
+    a.amodal = a.amodal or a.amodal_geometry
     import numpy as np
     import torch
     from constructionsceneposeestimation_amd.crops import CROP_INFO_DTYPE, eligible_labels
@@ -115,9 +122,22 @@ def main():
             r.crop_amodal(fr, size=S, per_frame=K, info=info.data_ptr(), crop_amodal=c_amodal.data_ptr(),
                           stream=stream.cuda_stream)
 
+        if a.amodal_geometry:
+            g_mask = torch.empty((n, K, S, S), dtype=torch.uint8, device=dev)
+            g_depth = torch.empty((n, K, S, S), dtype=torch.float32, device=dev)
+            g_oc = torch.empty((n, K, S, S, 3), dtype=torch.int16, device=dev)
+
+        def geometry():
+            r.crop_amodal_geometry(fr, size=S, per_frame=K, info=info.data_ptr(), crop_amodal=g_mask.data_ptr(),
+                                   crop_amodal_depth=g_depth.data_ptr(), crop_amodal_coords=g_oc.data_ptr(),
+                                   stream=stream.cuda_stream)
+
         variants = {"render": (render,), "with_crops": (render, crops), "crops_only": (crops,)}
         if a.amodal:
             variants.update({"with_amodal": (render, crops, amodal), "amodal_only": (amodal,)})
+
+        if a.amodal_geometry:
+            variants.update({"with_amodal_geometry": (render, crops, geometry), "amodal_geometry_only": (geometry,)})
 
         def once(steps):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -138,6 +158,14 @@ def main():
         slots = info.cpu().numpy().view(CROP_INFO_DTYPE).reshape(n, K)
         mask_share = float((c_mask != 0).float().mean().item())
         amodal_share = float((c_amodal != 0).float().mean().item()) if a.amodal else None
+        if a.amodal_geometry:   # the last geometry pass agrees with the last mask pass and the crops
+            geometry_checks = {"mask_equals_crop_amodal": bool(torch.equal(g_mask, c_amodal)),
+                               "depth_equals_crop_depth_under_crop_mask":
+                                   bool(torch.equal(g_depth[c_mask != 0], c_depth[c_mask != 0])),
+                               "coords_equal_crop_coords_under_crop_mask":
+                                   bool(torch.equal(g_oc[c_mask != 0], c_oc[c_mask != 0])),
+                               "hidden_sample_share": float(((g_mask != 0) & (c_mask == 0)).float().mean().item())}
+            del g_mask, g_depth, g_oc
         del c_amodal
 
         del rgb, inst, depth, oc, c_rgb, c_mask, c_oc, c_depth
@@ -246,6 +274,20 @@ def main():
                          "amodal_only_us_per_frame": round(med["amodal_only"] / n * 1e6, 2),
                          "added_over_one_render": round(added / med["render"], 4),
                          "amodal_pixel_share": round(amodal_share, 4)}
+    if a.amodal_geometry:
+        added = med["with_amodal_geometry"] - med["with_crops"]
+        mask_added = med["with_amodal"] - med["with_crops"]
+        only = med["amodal_geometry_only"]
+        res["amodal_geometry"] = {
+            "with_amodal_geometry_s": round(med["with_amodal_geometry"], 6), "amodal_geometry_only_s": round(only, 6),
+            "added_behind_crops_us_per_frame": round(added / n * 1e6, 2),
+            "amodal_geometry_only_us_per_frame": round(only / n * 1e6, 2),
+            "added_over_mask_pass_added": round(added / mask_added, 3) if mask_added > 0 else None,
+            "only_over_amodal_only": round(only / med["amodal_only"], 3),
+            "added_over_one_render": round(added / med["render"], 4),
+            "only_over_one_render": round(only / med["render"], 4),
+            "written_bytes_per_frame": K * S * S * (1 + 4 + 6), "key_bytes_per_frame": K * S * S * 4,
+            "checks": geometry_checks}
     if os.path.dirname(a.out):
         os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
