@@ -17,6 +17,7 @@ KEEP_TEXTURE = -2  # CSG_KEEP_TEXTURE
 CROP_FILTERS = {"bilinear": 0, "area": 1}  # CSG_CROP_FILTER_*: the RGB filter of csg_crop_objects_filtered
 COVERED_UNKNOWN = 0x80000000  # csg_outputs.label_covered flag: a tile held more than 32 labels
 ERR_CAPACITY = -6  # CSG_ERR_CAPACITY
+SPAN_MAX_LABELS = 256  # CSG_SPAN_MAX_LABELS: the most labels csg_mask_spans takes
 # csg_outputs.file_kinds (CSG_FILE_*): files encoded on the GPU, one per kind per frame, in bit order
 FILE_KINDS = {"rgb_png": 1, "depth_csv": 2, "depth_png": 4, "pointcloud_txt": 8, "pointcloud_ply": 16,
               "depth16_png": 32}
@@ -29,7 +30,8 @@ EXPORTED = (
     "csg_project_keypoints", "csg_timing_reset", "csg_timing_read", "csg_set_dr_light", "csg_set_dr_textures",
     "csg_instance_bounds", "csg_copy_files", "csg_host_alloc", "csg_host_free", "csg_size_work",
     "csg_get_work_info", "csg_host_id_bytes", "csg_set_object_frames", "csg_crop_objects", "csg_encode_files",
-    "csg_crop_objects_filtered", "csg_crop_amodal", "csg_crop_amodal_geometry",
+    "csg_crop_objects_filtered", "csg_crop_amodal", "csg_crop_amodal_geometry", "csg_mask_spans",
+    "csg_keep_instance", "csg_last_instance",
 )
 
 
@@ -129,6 +131,12 @@ class AmodalGeometryJob(C.Structure):
                 ("crop_amodal", C.c_void_p), ("crop_amodal_depth", C.c_void_p), ("crop_amodal_coords", C.c_void_p)]
 
 
+class SpanJob(C.Structure):
+    """csg_span_job (csg_mask_spans)."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n_labels", C.c_uint32), ("capacity", C.c_uint32),
+                ("instance", C.c_void_p), ("spans", C.c_void_p), ("span_offsets", C.c_void_p)]
+
+
 class EncodeJob(C.Structure):
     """csg_encode_job (csg_encode_files)."""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n_frames", C.c_uint32), ("file_kinds", C.c_uint32),
@@ -208,6 +216,9 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     lib.csg_crop_amodal.argtypes = [vp, C.POINTER(AmodalJob), u32, vp]
     lib.csg_crop_amodal_geometry.argtypes = [vp, C.POINTER(AmodalGeometryJob), u32, vp]
     lib.csg_encode_files.argtypes = [vp, C.POINTER(EncodeJob)]
+    lib.csg_mask_spans.argtypes = [vp, C.POINTER(SpanJob), u32, vp]
+    lib.csg_keep_instance.argtypes = [vp, i32]
+    lib.csg_last_instance.argtypes = [vp, C.POINTER(vp), C.POINTER(u32)]
     if lib.csg_abi_version() != ABI_VERSION:
         raise CsgError(f"libcsg.so ABI {lib.csg_abi_version()} != binding ABI {ABI_VERSION}; rebuild")
     _lib = lib

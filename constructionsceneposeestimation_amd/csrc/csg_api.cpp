@@ -23,6 +23,7 @@
 #include "csg_crops.h"
 #include "csg_encode.h"
 #include "csg_kernels.h"
+#include "csg_spans.h"
 #include "csg_widen.h"
 
 using namespace csg;
@@ -244,6 +245,16 @@ struct csg_ctx {
   hipEvent_t am_done = nullptr;
   hipStream_t am_stream = nullptr;
   bool am_busy = false;
+  // Mask spans (csg_mask_spans): the pass's own scratch, the span counts [n][L][groups of 64 columns],
+  // grown to the job; ms_done orders passes on different streams as am_done does the amodal passes.
+  DevBuf<uint32_t> ms_cnt;
+  hipEvent_t ms_done = nullptr;
+  hipStream_t ms_stream = nullptr;
+  bool ms_busy = false;
+  // csg_keep_instance / csg_last_instance: host-output batches keep their ids on the device
+  bool keep_ids = false;
+  const int32_t* last_inst = nullptr;
+  uint32_t last_inst_frames = 0;
   // the last sizing pass (csg_size_work)
   uint32_t sized_frames = 0, sized_max_rec = 0, sized_max_bin = 0;
   double sized_mean_rec = 0.0, sized_mean_bin = 0.0;
@@ -415,6 +426,9 @@ void csg_destroy(csg_ctx* c) {
     if (c->am_stage_ev[k]) (void)hipEventDestroy(c->am_stage_ev[k]);
   }
   if (c->am_done) (void)hipEventDestroy(c->am_done);
+  if (c->ms_busy) (void)hipEventSynchronize(c->ms_done);   // a span pass on a stream of the caller's
+  c->ms_cnt.release();
+  if (c->ms_done) (void)hipEventDestroy(c->ms_done);
   for (auto& e : c->ring)
     if (e) (void)hipEventDestroy(e);
   if (c->h_ids_n) (void)hipHostFree(c->h_ids_n);
@@ -1089,7 +1103,7 @@ static int enqueue_batch(csg_ctx* c, const csg_frame* frames, uint32_t F, int fr
     b.kp_vis = out->keypoints_vis;
   } else {
     if (out->rgb) { HIP_TRY(c, c->o_rgb.alloc(F * npx * 3)); b.rgb = c->o_rgb.p; }
-    if (out->instance) { HIP_TRY(c, c->o_inst.alloc(F * npx)); b.inst = c->o_inst.p; }
+    if (out->instance || c->keep_ids) { HIP_TRY(c, c->o_inst.alloc(F * npx)); b.inst = c->o_inst.p; }
     if (out->depth) { HIP_TRY(c, c->o_depth.alloc(F * npx)); b.depth = c->o_depth.p; }
     if (out->normals) { HIP_TRY(c, c->o_normals.alloc(F * npx * 3)); b.normals = c->o_normals.p; }
     if (out->points) { HIP_TRY(c, c->o_points.alloc(F * npx * 3)); b.points = c->o_points.p; }
@@ -1318,6 +1332,8 @@ static int enqueue_batch(csg_ctx* c, const csg_frame* frames, uint32_t F, int fr
   c->last_depth = b.depth;
   c->last_points = b.points;
   c->last_dvis = dvis;
+  c->last_inst = dev ? nullptr : b.inst;
+  c->last_inst_frames = c->last_inst ? F : 0;
   if (!dev) {   // the batch's stream orders everything after it (and csg_synchronize) behind the copies
     if (narrow) {   // ... and behind the widening of every chain's ids
       auto* l = new std::shared_ptr<WidenLatch>(latch);
@@ -2036,6 +2052,68 @@ int csg_crop_objects_filtered(csg_ctx* c, const csg_crop_job* job, uint32_t rgb_
   if (a.crop_rgb || a.crop_mask || a.crop_coords || a.crop_depth) launch_crop_sample(a, n_frames, st);
   if (a.rgb_filter == CSG_CROP_FILTER_AREA && a.crop_rgb) launch_crop_area(a, n_frames, st);   // behind the plan
   HIP_TRY(c, hipGetLastError());
+  return CSG_OK;
+}
+
+// Mask spans: a stand-alone pass over a device id image (no scene state, no work buffers); validates
+// the job, grows the pass's own count scratch and enqueues count, scan and emit.
+int csg_mask_spans(csg_ctx* c, const csg_span_job* job, uint32_t n_frames, void* stream) {
+  static_assert(sizeof(SpanRec) == sizeof(csg_span) && sizeof(csg_span) == 8, "csg_span layout");
+  static_assert(kSpanMaxLabels == CSG_SPAN_MAX_LABELS, "label limit");
+  if (!c) return CSG_ERR_INVALID;
+  if (!job) return c->fail(CSG_ERR_INVALID, "mask_spans: null job");
+  if (n_frames == 0) return c->fail(CSG_ERR_INVALID, "mask_spans: no frames");
+  if (!job->instance || !job->spans || !job->span_offsets)
+    return c->fail(CSG_ERR_INVALID, "mask_spans: instance, spans and span_offsets must not be NULL");
+  if (job->width < 1 || job->width > 8192 || job->height < 1 || job->height > 8192)
+    return c->fail(CSG_ERR_INVALID, "mask_spans: frame %u x %u outside 1..8192", job->width, job->height);
+  if (job->capacity == 0) return c->fail(CSG_ERR_INVALID, "mask_spans: capacity must be at least 1");
+  if (job->n_labels == 0) return c->fail(CSG_ERR_INVALID, "mask_spans: n_labels must be at least 1");
+  if (job->n_labels > CSG_SPAN_MAX_LABELS)
+    return c->fail(CSG_ERR_LIMIT, "mask_spans: n_labels %u above CSG_SPAN_MAX_LABELS %u", job->n_labels,
+                   CSG_SPAN_MAX_LABELS);
+  if (((uintptr_t)job->spans & 7u) || ((uintptr_t)job->span_offsets & 3u))
+    return c->fail(CSG_ERR_INVALID, "mask_spans: spans must be 8-byte aligned, span_offsets 4-byte");
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+  SpanArgs a{};
+  a.W = job->width;
+  a.H = job->height;
+  a.L = job->n_labels;
+  a.G = (job->width + 63u) / 64u;
+  a.C = job->capacity;
+  a.instance = job->instance;
+  a.spans = reinterpret_cast<SpanRec*>(job->spans);
+  a.offsets = job->span_offsets;
+  const size_t n_cnt = (size_t)n_frames * a.L * a.G;
+  if (!c->ms_done) HIP_TRY(c, hipEventCreateWithFlags(&c->ms_done, hipEventDisableTiming));
+  if (c->ms_busy) {
+    if (c->ms_cnt.n < n_cnt) HIP_TRY(c, hipEventSynchronize(c->ms_done));         // the last pass still reads what is freed below
+    else if (c->ms_stream != st) HIP_TRY(c, hipStreamWaitEvent(st, c->ms_done, 0));   // ... or what this pass overwrites
+  }
+  HIP_TRY(c, c->ms_cnt.alloc(n_cnt));
+  a.cnt = c->ms_cnt.p;
+  launch_span_count(a, n_frames, st);
+  launch_span_scan(a, n_frames, st);
+  launch_span_emit(a, n_frames, st);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipEventRecord(c->ms_done, st));
+  c->ms_stream = st;
+  c->ms_busy = true;
+  return CSG_OK;
+}
+
+int csg_keep_instance(csg_ctx* c, int32_t keep) {
+  if (!c) return CSG_ERR_INVALID;
+  c->keep_ids = keep != 0;
+  return CSG_OK;
+}
+
+int csg_last_instance(csg_ctx* c, const int32_t** instance, uint32_t* n_frames) {
+  if (!c) return CSG_ERR_INVALID;
+  if (!instance || !n_frames) return c->fail(CSG_ERR_INVALID, "last_instance: null argument");
+  *instance = c->last_inst;
+  *n_frames = c->last_inst_frames;
   return CSG_OK;
 }
 

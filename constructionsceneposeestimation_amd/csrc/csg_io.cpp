@@ -367,4 +367,154 @@ int csgio_write_label_json(const char* path, const csgio_label* L) {
   return f.close();
 }
 
+int csgio_spans_to_rle(const uint32_t* spans, const uint32_t* offsets, uint32_t n_labels, uint32_t height,
+                       uint32_t width, uint32_t* counts, uint64_t counts_cap, uint64_t* counts_off, char* str,
+                       uint64_t str_cap, uint64_t* str_off) {
+  if (!offsets || !counts_off || !str_off || height == 0 || width == 0) return -EINVAL;
+  const uint64_t npx = (uint64_t)height * width;
+  if (npx > 0xFFFFFFFFull || offsets[0] != 0 || (offsets[n_labels] && !spans)) return -EINVAL;
+  uint64_t nc = 0, ns = 0;
+  bool fits = true;
+  counts_off[0] = str_off[0] = 0;
+  for (uint32_t l = 0; l < n_labels; ++l) {
+    const uint32_t lo = offsets[l], hi = offsets[l + 1];
+    if (hi < lo) return -EINVAL;
+    // the two counts before the one being made (c[i-2] feeds the string's delta), and how many were made
+    uint32_t run = 0, before[2] = {0, 0};
+    uint64_t made = 0, end = 0;
+    auto emit = [&](uint32_t c) {   // one finished count: store it, append its characters
+      if (nc < counts_cap && counts) counts[nc] = c;
+      else if (counts) fits = false;
+      ++nc;
+      int64_t x = (int64_t)c - (made > 2 ? (int64_t)before[0] : 0);
+      bool more = true;
+      while (more) {
+        int ch = (int)(x & 0x1f);
+        x >>= 5;   // arithmetic
+        more = (ch & 0x10) ? x != -1 : x != 0;
+        if (more) ch |= 0x20;
+        if (ns < str_cap && str) str[ns] = (char)(ch + 48);
+        else if (str) fits = false;
+        ++ns;
+      }
+      before[0] = before[1];
+      before[1] = c;
+      ++made;
+    };
+    for (uint32_t k = lo; k < hi; ++k) {
+      const uint64_t start = spans[2 * (uint64_t)k], len = spans[2 * (uint64_t)k + 1];
+      if (len == 0 || start + len > npx || (k > lo && start < end)) return -EINVAL;
+      if (k > lo && start == end) {
+        run += (uint32_t)len;   // continues the run of ones (across a column boundary)
+      } else {
+        if (k > lo) emit(run);
+        emit((uint32_t)(start - end));   // zeros; the first may be 0
+        run = (uint32_t)len;
+      }
+      end = start + len;
+    }
+    if (hi > lo) {
+      emit(run);
+      if (end < npx) emit((uint32_t)(npx - end));
+    }
+    counts_off[l + 1] = nc;
+    str_off[l + 1] = ns;
+  }
+  return fits ? 0 : -ENOSPC;
+}
+
+int csgio_write_coco_fragment(const char* path, const csgio_coco* F) {
+  if (!path || !F || !F->span_offsets || (F->n_objects && (!F->obj_label || !F->obj_class || !F->obj_path)) ||
+      (F->n_labels && !F->inst_stats) || (F->n_kp && (!F->kp_uv || !F->kp_vis || !F->obj_kp_off || !F->obj_kp)))
+    return -EINVAL;
+  const uint32_t L = F->n_labels;
+  const uint64_t n_counts = 2 * (uint64_t)F->span_offsets[L] + L + 1;
+  std::vector<char> text(6 * n_counts);
+  std::vector<uint64_t> c_off(L + 1), s_off(L + 1);
+  const int rc = csgio_spans_to_rle(F->spans, F->span_offsets, L, F->height, F->width, nullptr, 0, c_off.data(),
+                                    text.data(), text.size(), s_off.data());
+  if (rc) return rc;
+  std::string o;
+  o.reserve(65536 + (size_t)s_off[L]);
+  char num[48];
+  auto put_int = [&](long long v) { o.append(num, std::to_chars(num, num + sizeof num, v).ptr); };
+  auto put_dbl = [&](double v) {
+    if (std::isnan(v)) o += "NaN";
+    else if (std::isinf(v)) o += v > 0 ? "Infinity" : "-Infinity";
+    else o.append(num, csg::repr_double(num, v));
+  };
+  char name[32];
+  std::snprintf(name, sizeof name, "%06u", F->frame_id);
+  o += "{\"image\":{\"id\":";
+  put_int(F->frame_id);
+  o += ",\"file_name\":\"rgb/rgb_";
+  o += name;
+  o += ".png\",\"height\":";
+  put_int(F->height);
+  o += ",\"width\":";
+  put_int(F->width);
+  o += "},\"annotations\":[";
+  bool first = true;
+  for (uint32_t j = 0; j < F->n_objects; ++j) {
+    const int32_t lab = F->obj_label[j];
+    if (lab < 0 || (uint32_t)lab >= L) continue;
+    const uint32_t* st = F->inst_stats + (size_t)lab * 5;
+    if (st[0] == 0) continue;
+    if (s_off[lab + 1] == s_off[lab]) return -EINVAL;   // pixels and no spans: not this frame's spans
+    o += first ? "{\"id\":" : ",{\"id\":";
+    first = false;
+    put_int((long long)F->frame_id * 65536 + lab);
+    o += ",\"image_id\":";
+    put_int(F->frame_id);
+    o += ",\"category_id\":";
+    put_int(F->obj_class[j]);
+    o += ",\"bbox\":[";
+    put_int(st[1]);
+    o += ',';
+    put_int(st[2]);
+    o += ',';
+    put_int((long long)st[3] - st[1] + 1);
+    o += ',';
+    put_int((long long)st[4] - st[2] + 1);
+    o += "],\"area\":";
+    put_int(st[0]);
+    o += ",\"iscrowd\":0,\"segmentation\":{\"size\":[";
+    put_int(F->height);
+    o += ',';
+    put_int(F->width);
+    o += "],\"counts\":\"";
+    for (uint64_t k = s_off[lab]; k < s_off[lab + 1]; ++k) {   // characters 48..111: only the backslash needs escaping
+      if (text[k] == '\\') o += '\\';
+      o += text[k];
+    }
+    o += "\"},\"inst_idx\":";
+    put_int(lab);
+    o += ",\"prim_path\":";
+    o += F->obj_path[j];
+    if (F->n_kp && F->obj_kp_off[j + 1] > F->obj_kp_off[j]) {
+      o += ",\"keypoints\":[";
+      uint32_t seen = 0;
+      for (uint32_t q = F->obj_kp_off[j]; q < F->obj_kp_off[j + 1]; ++q) {
+        const uint32_t k = F->obj_kp[q];
+        if (k >= F->n_kp) return -EINVAL;
+        if (q > F->obj_kp_off[j]) o += ',';
+        put_dbl((double)F->kp_uv[2 * k]);
+        o += ',';
+        put_dbl((double)F->kp_uv[2 * k + 1]);
+        o += ',';
+        put_int(F->kp_vis[k]);
+        seen += F->kp_vis[k] > 0;
+      }
+      o += "],\"num_keypoints\":";
+      put_int(seen);
+    }
+    o += '}';
+  }
+  o += "]}";
+  File f(path);
+  if (!f.f) return -errno;
+  if (!f.write(o.data(), o.size())) return -EIO;
+  return f.close();
+}
+
 }  // extern "C"

@@ -13,6 +13,11 @@ same files:
                                     bbox_2d, pixel_count; + occlusion_ratio with
                                     --occlusion)
   labels/instance_mask_%06d.npy    (:2066-2069; real ids here, -1 background)
+  coco/coco_%06d.json              (optional "mask_rle": the frame's COCO image record and one annotation
+                                    per visible object -- bbox, area, keypoints and the object's mask as a
+                                    COCO run-length string made from the GPU's mask spans; no reference
+                                    counterpart.  ``python -m constructionsceneposeestimation_amd.masks
+                                    merge RUN_DIR`` joins them into coco/instances.json)
   depth/depth_%06d.csv             (:1687-1688)
   depth/depth_%06d.png             (:1690-1709, JET colour map made on the GPU)
   depth/depth_%06d.npy             (optional)
@@ -53,6 +58,7 @@ from typing import List, Optional
 import numpy as np
 
 from . import camera_math as cm
+from . import masks
 from . import prep_pool
 from .labels import OBJECT_LISTS, in_frustum, label_record, object_box, object_poses
 from .quality_log import QualityLog
@@ -60,7 +66,7 @@ from .renderer import Renderer, make_frames, output_spec, scene_labels
 from .shard import shard_of_range
 from .workload import Workload
 from .writer_pool import WriterPool
-from .writers import LabelWriter
+from .writers import FragmentWriter, LabelWriter
 from .writer_pool import _write_png  # noqa: F401  (the generator's PNG settings; tools/gen_bench.py)
 
 
@@ -81,7 +87,7 @@ def _log_done(log: QualityLog, fut, log_args: dict, points: bool) -> None:
 
 
 OUTPUTS = ("rgb", "mask", "depth_csv", "depth_png", "depth_npy", "pointcloud", "normals", "obj_coords",
-           "pointcloud_ply", "depth16_png")
+           "pointcloud_ply", "depth16_png", "mask_rle")
 # What the reference writes for every frame (GDP:1668-1771, 2055-2072): RGB PNG, depth CSV and
 # JET depth PNG, point-cloud TXT, instance mask .npy; the label JSON is always written (it is the
 # resume marker).
@@ -168,6 +174,11 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
     that fails them all is logged failed and writes no files (GDP:1662-1666).
     ``depth16_counts_per_metre``: the scale of the "depth16_png" output
     (default 250: 4 mm steps, 262.1 m range; recorded in depth/depth16.json).
+    ``outputs`` with "mask_rle": each frame's per-object masks as COCO
+    run-length strings in coco/coco_%06d.json (masks.coco_fragment).  The ids
+    stay on the GPU (csg_keep_instance) and only their spans cross PCIe
+    (Renderer.mask_spans_host, behind each batch; the dense ids are copied
+    only when "mask" is asked for as well).
     ``prep_workers``: processes that prepare batches ahead (epoch layouts,
     object poses, cameras; prep_pool.py), so that numpy work does not hold
     this process's GIL; -1 = two for runs of at least 20 batches, else none."""
@@ -194,6 +205,8 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                          "lo": box[0].tolist() if box else None, "hi": box[1].tolist() if box else None})
         with open(os.path.join(out_dir, "obj_coords", "objects.json"), "w") as fh:
             json.dump({"objects": objs}, fh, indent=2)
+    if "mask_rle" in outs:
+        os.makedirs(os.path.join(out_dir, "coco"), exist_ok=True)
     if "depth16_png" in outs:   # what a reader needs to turn the samples back into metres
         s16 = float(depth16_counts_per_metre)
         if not (np.isfinite(s16) and s16 > 0):
@@ -239,6 +252,13 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                       n_writers, n_slots=2 + n_rend, mode=writer_mode, sink=sink)
     rends = [Renderer(wl.scene, wl.width, wl.height, max_frames=batch, device=device) for _ in range(n_rend)]
     r = rends[0]
+    want_rle = "mask_rle" in outs
+    span_cap = {}   # renderer -> the span capacity its last batch needed (mask_spans_host grows it)
+    fw = None       # thread mode: the native fragment writer (writers.FragmentWriter), made with the first poses
+    kp_by_obj = masks.keypoints_by_object(wl.kp_table) if want_rle and not gpu_files else None
+    if want_rle:    # host-output batches keep their ids on the device for the span pass
+        for x in rends:
+            x.keep_instance(True)
     if gpu_files:   # page-locked slots, and buffers for the encoded files (an estimate, grown on demand)
         npx = wl.width * wl.height
         est = {"rgb_png": 2 * npx, "depth_csv": 10 * npx, "depth_png": npx, "pointcloud_txt": 48 * npx,
@@ -317,6 +337,15 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
         tr = time.time()
         sets = [set_of[f // 10] for f in fb]
 
+        rle = [None]   # the batch's (offsets, spans) per frame, with "mask_rle"
+
+        def spans_of_batch() -> int:
+            ids, nf = r.last_instance()
+            if not ids or nf != len(fb):
+                raise RuntimeError(f"mask_rle: the batch kept {nf} id images, {len(fb)} frames rendered")
+            rle[0], span_cap[id(r)] = r.mask_spans_host(len(fb), ids, capacity=span_cap.get(id(r), 0))
+            return sum(o.nbytes + sp.nbytes for o, sp in rle[0])
+
         def run(views, projs):
             fr = make_frames(views, projs, sets, fb)
             if kinds:
@@ -327,10 +356,10 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                     offsets = r.copy_files(pool.grow_files(slot, need + need // 4, alloc=r.host_buffer,
                                                            free=r.free_host_buffer), len(fb) * nk)
                 arrays["file_offsets"] = offsets
-                d2h.append(int(offsets[-1]) + wire_bytes(out))
+                d2h.append(int(offsets[-1]) + wire_bytes(out) + (spans_of_batch() if want_rle else 0))
             else:
                 out = r.render(fr, want=want, out={k: v[:len(fb)] for k, v in arrays.items()})
-                d2h.append(wire_bytes(out))
+                d2h.append(wire_bytes(out) + (spans_of_batch() if want_rle else 0))
             return out
 
         out = run(views, projs)
@@ -356,7 +385,7 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                 out = run(*wl.frame_params(fb, attempts))
                 check = again
         te = time.time()
-        return fb, slot, out, (te - tr, tp - tw, tr - tp), attempts, checks, failed
+        return fb, slot, out, (te - tr, tp - tw, tr - tp), attempts, checks, failed, rle[0]
 
     ahead = ThreadPoolExecutor(max_workers=n_rend)
     prep = ThreadPoolExecutor(max_workers=max(1, n_prep))
@@ -372,7 +401,7 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
         queued = [ahead.submit(render_batch, b) for b in range(min(n_rend, len(starts)))]
         for b in range(len(starts)):
             tq = time.time()
-            fb, slot, out, (dt, dwait, dprep), attempts, checks, failed = queued.pop(0).result()
+            fb, slot, out, (dt, dwait, dprep), attempts, checks, failed, rle = queued.pop(0).result()
             t_main_wait += time.time() - tq
             t_render += dt
             t_slot_wait += dwait
@@ -421,6 +450,20 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                     files.append((file_path(out_dir, "rgb", f), "png", ("rgb",)))
                 if "mask" in outs:
                     files.append((os.path.join(out_dir, "labels", f"instance_mask_{f:06d}.npy"), "npy", ("instance",)))
+                if want_rle:   # written by the job itself, before the label file
+                    kp_k = {"kp_uv": out["keypoints_uv"][k] if "keypoints_uv" in out else None,
+                            "kp_vis": out["keypoints_vis"][k] if "keypoints_vis" in out else None}
+                    if gpu_files:   # natively, without the GIL
+                        if fw is None:
+                            fw = FragmentWriter(pose_cache[f // 10], wl.kp_table, wl.height, wl.width)
+                        job = partial(fw.write, frame_id=f, inst_stats=out["inst_stats"][k], spans=rle[k][1],
+                                      offsets=rle[k][0], **kp_k)
+                    else:           # writer processes: the same bytes from masks.coco_fragment (picklable)
+                        job = partial(masks.write_fragment, frame_id=f, height=wl.height, width=wl.width,
+                                      poses=pose_cache[f // 10], inst_stats=out["inst_stats"][k].copy(),
+                                      spans=rle[k][1], offsets=rle[k][0], kp_by_obj=kp_by_obj,
+                                      **{n: (v.copy() if v is not None else None) for n, v in kp_k.items()})
+                    files.append((masks.fragment_path(out_dir, f), "call", (job,)))
                 if "depth_npy" in outs:
                     files.append((os.path.join(out_dir, "depth", f"depth_{f:06d}.npy"), "npy", ("depth",)))
                 if "depth_csv" in outs and not kinds:

@@ -1,0 +1,256 @@
+"""Per-object run-length masks: from the GPU's mask spans to COCO annotations.
+
+``Renderer.mask_spans`` (csg_mask_spans, include/csg_api.h) turns an instance
+image into *spans*: per label, the maximal vertical runs of its pixels as
+``(start, len)`` with ``start = x * H + y0``, COCO's column-major pixel index,
+ordered by label, then start.  This module is the host side:
+
+* the readers, in NumPy, for users of the files (pycocotools is not needed):
+  :func:`spans_to_counts`, :func:`counts_to_string`, :func:`string_to_counts`,
+  :func:`decode`, :func:`spans_to_mask`;
+* :func:`coco_fragment`, the per-frame ``coco/coco_%06d.json`` the generator
+  writes for ``--outputs mask_rle`` (its run-length strings come from the native
+  ``writers.spans_to_rle``, which these functions restate);
+* :func:`merge`, which joins the fragments of all shards of a run into one
+  ``coco/instances.json``::
+
+    python -m constructionsceneposeestimation_amd.masks merge RUN_DIR
+
+A COCO run-length mask of an H x W image is the list of run lengths of the
+column-major pixel sequence, starting with a run of zeros (which may be
+empty); its compressed string is pycocotools' ``rleToString``.
+"""
+from __future__ import annotations
+
+import glob
+import json
+import os
+import sys
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+ANN_ID_STRIDE = 65536   # annotation id = frame_id * ANN_ID_STRIDE + inst_idx
+
+
+def label_spans(spans: np.ndarray, offsets: np.ndarray, label: int) -> np.ndarray:
+    """The (k, 2) spans of ``label`` in one frame's ``spans`` / ``offsets``."""
+    return np.asarray(spans).reshape(-1, 2)[int(offsets[label]):int(offsets[label + 1])]
+
+
+def spans_to_counts(size: Tuple[int, int], spans: np.ndarray) -> np.ndarray:
+    """Uncompressed COCO counts (uint32) of ONE label's spans ((k, 2) uint32
+    ``start``, ``len``, ordered by start) in an image of ``size`` = (H, W): the
+    first count is the first start (it may be 0), then ones and zeros
+    alternate; a span that starts where the previous one ended (a mask running
+    from the bottom of one column into the top of the next) continues its run;
+    a last run of zeros appears only when the last span ends before H * W.  No
+    spans: the single count H * W."""
+    H, W = int(size[0]), int(size[1])
+    sp = np.asarray(spans, np.int64).reshape(-1, 2)
+    if sp.shape[0] == 0:
+        return np.array([H * W], np.uint32)
+    start, end = sp[:, 0], sp[:, 0] + sp[:, 1]
+    if (sp[:, 1] <= 0).any() or (start[1:] < end[:-1]).any() or end[-1] > H * W:
+        raise ValueError("spans_to_counts: spans are empty, out of order, overlapping or beyond the image")
+    first = np.concatenate([[True], start[1:] != end[:-1]])      # spans that open a run of ones
+    last = np.concatenate([first[1:], [True]])                   # ... and those that close one
+    s, e = start[first], end[last]
+    c = np.empty(2 * s.shape[0], np.int64)
+    c[0::2] = s - np.concatenate([[0], e[:-1]])
+    c[1::2] = e - s
+    if e[-1] < H * W:
+        c = np.concatenate([c, [H * W - e[-1]]])
+    return c.astype(np.uint32)
+
+
+def counts_to_string(counts: Sequence[int]) -> str:
+    """pycocotools' ``rleToString``: count i is written as itself (i <= 2) or
+    as its difference to count i - 2, five bits at a time from the low end, as
+    the character ``chr(48 + bits)`` with bit 0x20 set while more follow."""
+    c = [int(v) for v in np.asarray(counts).reshape(-1)]
+    out = []
+    for i, v in enumerate(c):
+        x = v - c[i - 2] if i > 2 else v
+        more = True
+        while more:
+            b = x & 0x1f
+            x >>= 5                      # arithmetic
+            more = (x != -1) if (b & 0x10) else (x != 0)
+            if more:
+                b |= 0x20
+            out.append(chr(b + 48))
+    return "".join(out)
+
+
+def string_to_counts(s) -> np.ndarray:
+    """The inverse of :func:`counts_to_string` (pycocotools' ``rleFrString``)."""
+    if isinstance(s, str):
+        s = s.encode("ascii")
+    counts: List[int] = []
+    p, n = 0, len(s)
+    while p < n:
+        x, k, more = 0, 0, True
+        while more:
+            if p >= n:
+                raise ValueError("string_to_counts: the string ends inside a count")
+            b = s[p] - 48
+            x |= (b & 0x1f) << (5 * k)
+            more = bool(b & 0x20)
+            p += 1
+            k += 1
+            if not more and (b & 0x10):
+                x |= -1 << (5 * k)
+        if len(counts) > 2:
+            x += counts[-2]
+        counts.append(x)
+    return np.array(counts, np.int64).astype(np.uint32)
+
+
+def decode(size: Tuple[int, int], counts_or_string) -> np.ndarray:
+    """The (H, W) bool mask of a COCO run-length mask of ``size`` = (H, W),
+    given as counts or as the compressed string."""
+    H, W = int(size[0]), int(size[1])
+    c = string_to_counts(counts_or_string) if isinstance(counts_or_string, (str, bytes)) else \
+        np.asarray(counts_or_string, np.int64).reshape(-1)
+    c = c.astype(np.int64)
+    if (c < 0).any() or int(c.sum()) != H * W:
+        raise ValueError(f"decode: the counts sum to {int(c.sum())}, the image has {H * W} pixels")
+    bits = np.zeros(c.shape[0], bool)
+    bits[1::2] = True
+    return np.repeat(bits, c).reshape(W, H).T
+
+
+def spans_to_mask(size: Tuple[int, int], spans: np.ndarray) -> np.ndarray:
+    """The (H, W) bool mask one label's spans cover."""
+    H, W = int(size[0]), int(size[1])
+    sp = np.asarray(spans, np.int64).reshape(-1, 2)
+    d = np.zeros(H * W + 1, np.int64)
+    np.add.at(d, sp[:, 0], 1)
+    np.add.at(d, sp[:, 0] + sp[:, 1], -1)
+    return (np.cumsum(d[:-1]) > 0).reshape(W, H).T
+
+
+# -- the generator's per-frame fragment ---------------------------------------------------
+def keypoints_by_object(kp_table) -> Dict[int, List[int]]:
+    """object index -> indices of its keypoints, in table order (Workload.kp_table)."""
+    by: Dict[int, List[int]] = {}
+    for k, (j, _) in enumerate(kp_table):
+        by.setdefault(j, []).append(k)
+    return by
+
+
+def image_record(frame_id: int, height: int, width: int) -> dict:
+    return {"id": int(frame_id), "file_name": f"rgb/rgb_{int(frame_id):06d}.png", "height": int(height),
+            "width": int(width)}
+
+
+def coco_fragment(frame_id: int, height: int, width: int, poses: List[dict], inst_stats: np.ndarray,
+                  spans: np.ndarray, offsets: np.ndarray, kp_by_obj: Optional[Dict[int, List[int]]] = None,
+                  kp_uv: Optional[np.ndarray] = None, kp_vis: Optional[np.ndarray] = None) -> dict:
+    """One frame's COCO ``image`` record and ``annotations``: one per object of
+    ``poses`` (labels.object_poses) with visible pixels.  ``bbox`` = [x, y, w,
+    h] and ``area`` come from the GPU's ``inst_stats`` (pixels, inclusive box),
+    the mask from the frame's ``spans`` / ``offsets`` through the native
+    ``writers.spans_to_rle``; ``keypoints`` are the object's label keypoints as
+    [u, v, vis, ...] with the label file's visibility codes.  Ids are
+    deterministic: ``image_id = frame_id``, ``id = frame_id * 65536 + inst_idx``."""
+    from . import writers
+    off = np.asarray(offsets, np.uint32).reshape(-1)
+    L = off.shape[0] - 1
+    _, _, text, s_off = writers.spans_to_rle(spans, off, height, width)
+    s_off = s_off.tolist()
+    stats = np.asarray(inst_stats).tolist()
+    uv = kp_uv.tolist() if kp_uv is not None else None
+    vis = kp_vis.tolist() if kp_vis is not None else None
+    anns = []
+    for j, p in enumerate(poses):
+        i = int(p["inst_idx"])
+        if i < 0 or i >= len(stats) or stats[i][0] == 0:
+            continue
+        if i >= L or s_off[i + 1] == s_off[i]:
+            raise ValueError(f"coco_fragment: frame {frame_id}: label {i} has {stats[i][0]} pixels and no spans")
+        px, x0, y0, x1, y1 = stats[i]
+        a = {"id": int(frame_id) * ANN_ID_STRIDE + i, "image_id": int(frame_id), "category_id": int(p["class_id"]),
+             "bbox": [x0, y0, x1 - x0 + 1, y1 - y0 + 1], "area": px, "iscrowd": 0,
+             "segmentation": {"size": [int(height), int(width)],
+                              "counts": text[int(s_off[i]):int(s_off[i + 1])].decode("ascii")},
+             "inst_idx": i, "prim_path": p["prim_path"]}
+        ks = kp_by_obj.get(j) if kp_by_obj is not None and uv is not None else None
+        if ks:
+            flat = []
+            for k in ks:
+                flat += [uv[k][0], uv[k][1], vis[k]]
+            a["keypoints"] = flat
+            a["num_keypoints"] = sum(1 for k in ks if vis[k] > 0)
+        anns.append(a)
+    return {"image": image_record(frame_id, height, width), "annotations": anns}
+
+
+def fragment_bytes(fragment: dict) -> bytes:
+    return json.dumps(fragment, separators=(",", ":"), ensure_ascii=False).encode("utf-8")
+
+
+def write_fragment(path: str, *args, **kw) -> None:
+    """:func:`coco_fragment` of the arguments, written to ``path``."""
+    data = fragment_bytes(coco_fragment(*args, **kw))
+    with open(path, "wb") as fh:
+        fh.write(data)
+
+
+def fragment_path(out_dir: str, frame_id: int) -> str:
+    return os.path.join(out_dir, "coco", f"coco_{int(frame_id):06d}.json")
+
+
+# -- merge ---------------------------------------------------------------------------------
+def categories() -> List[dict]:
+    """COCO categories from identity.CONSTRUCTION_CLASS: one per class id, named
+    by the first name that maps to it."""
+    from .identity import CONSTRUCTION_CLASS
+    seen: Dict[int, str] = {}
+    for name, cid in CONSTRUCTION_CLASS.items():
+        seen.setdefault(int(cid), name)
+    return [{"id": cid, "name": seen[cid]} for cid in sorted(seen)]
+
+
+def merge(run_dir: str, out_path: Optional[str] = None) -> str:
+    """Join ``coco/coco_*.json`` of ``run_dir`` and of its ``shard_*``
+    directories into ``run_dir/coco/instances.json`` (``images`` sorted by
+    frame, ``annotations`` by id, ``categories``).  Pure host Python; the
+    result does not depend on how the frames were split over shards."""
+    paths = sorted(glob.glob(os.path.join(run_dir, "coco", "coco_*.json")) +
+                   glob.glob(os.path.join(run_dir, "shard_*", "coco", "coco_*.json")))
+    images, anns = {}, {}
+    for p in paths:
+        with open(p, "rb") as fh:
+            frag = json.loads(fh.read().decode("utf-8"))
+        img = frag["image"]
+        if img["id"] in images:
+            raise ValueError(f"merge: frame {img['id']} appears twice ({p})")
+        images[img["id"]] = img
+        for a in frag["annotations"]:
+            if a["id"] in anns:
+                raise ValueError(f"merge: annotation id {a['id']} appears twice ({p})")
+            anns[a["id"]] = a
+    out = {"images": [images[k] for k in sorted(images)], "annotations": [anns[k] for k in sorted(anns)],
+           "categories": categories()}
+    out_path = out_path or os.path.join(run_dir, "coco", "instances.json")
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    tmp = out_path + ".tmp"
+    with open(tmp, "wb") as fh:
+        fh.write(fragment_bytes(out))
+    os.replace(tmp, out_path)
+    return out_path
+
+
+def main(argv=None) -> int:
+    argv = sys.argv[1:] if argv is None else list(argv)
+    if len(argv) != 2 or argv[0] != "merge":
+        print("usage: python -m constructionsceneposeestimation_amd.masks merge RUN_DIR", file=sys.stderr)
+        return 2
+    print(merge(argv[1]))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -30,6 +30,13 @@ assert FRAME_DTYPE.itemsize == C.sizeof(_lib.Frame)
 OUTPUT_KINDS = ("rgb", "instance", "depth", "keypoints", "stats", "normals", "points", "depth_vis", "depth_range",
                 "covered", "depth_stats", "obj_coords")
 
+# Span records per frame that Renderer.mask_spans_host starts with (it doubles on overflow).  C3 at
+# 1080p has 27.8 thousand spans per frame on average, 53.7 thousand at the 99th percentile and 59.5
+# thousand at most over 480 frames (profiles/mask_rle/cost.json; leaves that pass the alpha test are
+# most of them): the largest count plus three eighths, 640 KiB of device memory per frame of a batch.
+# Only the records in use are copied to the host.
+DEFAULT_SPAN_CAPACITY = 81920
+
 
 def make_frames(views: np.ndarray, projs: np.ndarray, sets: Sequence[int], frame_ids: Sequence[int]) -> np.ndarray:
     n = len(frame_ids)
@@ -545,6 +552,98 @@ class Renderer:
         out["info"] = info
         out["intrinsics"] = crop_intrinsics(self.intr, info, S)
         return out
+
+    # -- per-object run-length masks ----------------------------------------------
+    def mask_spans(self, n: int, *, instance: int, spans: int, span_offsets: int, capacity: int,
+                   n_labels: Optional[int] = None, height: Optional[int] = None, width: Optional[int] = None,
+                   stream: int = 0) -> None:
+        """Enqueue the mask spans of ``n`` frames (csg_mask_spans; raw device
+        pointers, like :meth:`crop_objects`): the vertical runs of every label
+        of ``instance`` (n, H, W) int32 as (start = x * H + y0, len) records in
+        ``spans`` (n, capacity, 2) uint32, ordered by label then start, and
+        ``span_offsets`` (n, L + 1) uint32 (label l's records of frame f are
+        ``[off[f, l], off[f, l + 1])``).  ``off[f, L]`` is the frame's total
+        whether or not it fits: the call is asynchronous, so a caller reads it
+        after the stream completes and, where it exceeds ``capacity`` (that
+        frame's records are then unspecified), repeats the pass with a larger
+        one.  ``n_labels`` defaults to the scene's, ``height`` / ``width`` to
+        the renderer's.  On the stream of the render that wrote ``instance`` no
+        synchronisation is needed in between."""
+        job = _lib.SpanJob(self.width if width is None else int(width), self.height if height is None else int(height),
+                           self.n_labels if n_labels is None else int(n_labels), int(capacity), instance or None,
+                           spans or None, span_offsets or None)
+        self._check(self.lib.csg_mask_spans(self.ctx, C.byref(job), int(n), stream or None), "mask_spans")
+
+    def mask_spans_host(self, n: int, instance: int, *, capacity: int = 0, n_labels: Optional[int] = None,
+                        height: Optional[int] = None, width: Optional[int] = None, stream: int = 0):
+        """:meth:`mask_spans` of a device id image (pointer ``instance``),
+        delivered to the host: returns ``(frames, capacity)`` where ``frames``
+        is a list of ``n`` pairs ``(offsets (L + 1,) uint32, spans (total, 2)
+        uint32)`` and ``capacity`` the per-frame capacity that was enough.  The
+        pass starts at ``capacity`` (0: ``DEFAULT_SPAN_CAPACITY``) and is
+        repeated with the capacity doubled (at least the largest total seen)
+        until every frame fits.  Only the offsets and the records in use cross
+        PCIe: the pass runs on a stream of the wrapper's own, the offsets
+        follow it into page-locked memory, and the frames' records are packed
+        on the device and copied once (two waits in all, however many frames).
+        ``stream`` (a raw handle, 0: none) is the stream still writing
+        ``instance``, if any: it is waited for first.  Synchronous."""
+        import torch
+        n = int(n)
+        L = self.n_labels if n_labels is None else int(n_labels)
+        cap = int(capacity) or DEFAULT_SPAN_CAPACITY
+        dev = torch.device("cuda", self.device)
+        if stream:
+            torch.cuda.ExternalStream(stream, device=dev).synchronize()
+        else:
+            self.synchronize()
+        if getattr(self, "_span_stream", None) is None:
+            self._span_stream, self._span_pin = torch.cuda.Stream(dev), {}
+        st = self._span_stream
+
+        def pinned(name: str, count: int):   # a page-locked int32 staging tensor, grown by doubling and kept
+            t = self._span_pin.get(name)
+            if t is None or t.numel() < count:
+                t = torch.empty(max(count, 2 * (t.numel() if t is not None else 0), 1024), dtype=torch.int32,
+                                pin_memory=True)
+                self._span_pin[name] = t
+            return t[:count]
+
+        with torch.cuda.stream(st):
+            d_off = torch.empty((n, L + 1), dtype=torch.int32, device=dev)
+            h_off = pinned("offsets", n * (L + 1)).view(n, L + 1)
+            while True:
+                d_sp = torch.empty((n, cap, 2), dtype=torch.int32, device=dev)
+                self.mask_spans(n, instance=instance, spans=d_sp.data_ptr(), span_offsets=d_off.data_ptr(),
+                                capacity=cap, n_labels=L, height=height, width=width, stream=st.cuda_stream)
+                h_off.copy_(d_off, non_blocking=True)
+                st.synchronize()
+                off = h_off.numpy().view(np.uint32).copy()
+                top = int(off[:, L].max())
+                if top <= cap:
+                    break
+                cap = max(2 * cap, top)
+            totals = off[:, L].astype(np.int64)
+            ends = np.cumsum(totals)
+            packed = torch.cat([d_sp[f, :int(totals[f])] for f in range(n)])   # the records in use, and no more
+            h_sp = pinned("spans", 2 * int(ends[-1])).view(int(ends[-1]), 2)
+            h_sp.copy_(packed, non_blocking=True)
+            st.synchronize()
+            sp = h_sp.numpy().view(np.uint32).copy()
+        return [(off[f], sp[int(ends[f] - totals[f]):int(ends[f])]) for f in range(n)], cap
+
+    def keep_instance(self, keep: bool = True) -> None:
+        """Host-output batches (:meth:`render`, :meth:`render_files`) keep their
+        instance ids on the device even when "instance" is not among the host
+        outputs (csg_keep_instance): :meth:`last_instance` then finds them."""
+        self._check(self.lib.csg_keep_instance(self.ctx, int(bool(keep))), "keep_instance")
+
+    def last_instance(self):
+        """``(device pointer, frames)`` of the last host-output batch's id image
+        (csg_last_instance), valid until the next batch; (0, 0) when it made none."""
+        p, nf = C.c_void_p(), C.c_uint32()
+        self._check(self.lib.csg_last_instance(self.ctx, C.byref(p), C.byref(nf)), "last_instance")
+        return int(p.value or 0), int(nf.value)
 
     def instance_bounds(self, set_id: int = 0) -> np.ndarray:
         """(I, 2, 3) float32 world-space AABB of every instance under a transform set (GPU reduction)."""

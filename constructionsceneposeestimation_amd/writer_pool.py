@@ -77,13 +77,17 @@ def write_frame(arrays: Dict[str, np.ndarray], k: int, files: List[Tuple[str, st
     """Every file of frame ``k`` of a batch, then its label JSON (the resume
     marker, GDP:1357-1367 scans labels/).  ``files`` = (path, kind, array
     names[, a parameter of the kind: the counts per metre of "depth16"]); kind "encoded" names the file index j in the batch's files
-    encoded on the GPU (arrays "files" + "file_offsets"); ``label`` is the
+    encoded on the GPU (arrays "files" + "file_offsets"), kind "call" a callable that writes the
+    file to the path it is given; ``label`` is the
     label dict, or a callable that writes the label file to the path it is
     given (writers.LabelWriter); returns the frame's depth counts for the
     quality log.  ``sink`` "discard": every file goes to /dev/null."""
     from . import writers as fileio
     from .labels import label_json_bytes
     for path, kind, keys, *param in files:
+        if kind == "call":   # a job that writes the file itself: keys[0](path) (the COCO fragment)
+            _atomic(path, keys[0], sink=sink)
+            continue
         if kind in ("encoded", "encoded_pointcloud", "encoded_ply"):
             off = arrays["file_offsets"]
             j = keys[0]

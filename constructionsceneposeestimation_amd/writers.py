@@ -16,9 +16,10 @@ import numpy as np
 
 from .build import IO_LIB, build_io, needs_build, IO_DEPS
 
-ABI_VERSION = 4  # CSGIO_ABI_VERSION in include/csg_io.h
+ABI_VERSION = 5  # CSGIO_ABI_VERSION in include/csg_io.h
 EXPORTED = ("csgio_abi_version", "csgio_write_png_rgb", "csgio_write_npy", "csgio_write_depth_csv",
-            "csgio_write_pointcloud_txt", "csgio_depth_stats", "csgio_write_label_json")
+            "csgio_write_pointcloud_txt", "csgio_depth_stats", "csgio_write_label_json", "csgio_spans_to_rle",
+            "csgio_write_coco_fragment")
 PNG_STRATEGY = {"default": 0, "rle": 1, "huffman": 2}
 _lib: Optional[C.CDLL] = None
 
@@ -35,6 +36,14 @@ class Label(C.Structure):   # csgio_label
                 ("obj_kp", C.c_void_p), ("inst_stats", C.c_void_p), ("covered", C.c_void_p),
                 ("kp_uv", C.c_void_p), ("kp_vis", C.c_void_p), ("kp_name", C.c_void_p),
                 ("obj_listed", C.c_void_p)]
+
+
+class Coco(C.Structure):   # csgio_coco
+    _fields_ = [("frame_id", C.c_uint32), ("height", C.c_uint32), ("width", C.c_uint32),
+                ("n_objects", C.c_uint32), ("n_labels", C.c_uint32), ("n_kp", C.c_uint32),
+                ("obj_label", C.c_void_p), ("obj_class", C.c_void_p), ("obj_path", C.c_void_p),
+                ("obj_kp_off", C.c_void_p), ("obj_kp", C.c_void_p), ("inst_stats", C.c_void_p),
+                ("spans", C.c_void_p), ("span_offsets", C.c_void_p), ("kp_uv", C.c_void_p), ("kp_vis", C.c_void_p)]
 
 
 def load() -> C.CDLL:
@@ -56,6 +65,8 @@ def load() -> C.CDLL:
     lib.csgio_write_depth_csv.argtypes = [cp, vp, u32, u32]
     lib.csgio_write_pointcloud_txt.argtypes = [cp, vp, vp, u64]
     lib.csgio_write_label_json.argtypes = [cp, C.POINTER(Label)]
+    lib.csgio_spans_to_rle.argtypes = [vp, vp, u32, u32, u32, vp, u64, vp, vp, u64, vp]
+    lib.csgio_write_coco_fragment.argtypes = [cp, C.POINTER(Coco)]
     if lib.csgio_abi_version() != ABI_VERSION:
         raise CsgIoError(f"libcsgio.so ABI {lib.csgio_abi_version()} != binding ABI {ABI_VERSION}; rebuild")
     _lib = lib
@@ -185,6 +196,32 @@ def write_depth16_png(path: str, depth: np.ndarray, counts_per_metre: float = 25
         fh.write(depth16_png_bytes(depth_to_u16(depth, counts_per_metre)))
 
 
+def spans_to_rle(spans: np.ndarray, offsets: np.ndarray, height: int, width: int):
+    """One frame's mask spans (``Renderer.mask_spans``: ``spans`` (total, 2)
+    uint32 start / len, ``offsets`` (L + 1,) uint32) as COCO run-length masks,
+    natively with the GIL released (csgio_spans_to_rle; ``masks.spans_to_counts``
+    and ``masks.counts_to_string`` are its NumPy restatement).  Returns
+    ``(counts, counts_off, string, string_off)``: label l's counts are
+    ``counts[counts_off[l]:counts_off[l + 1]]`` (uint32) and its compressed
+    string ``string[string_off[l]:string_off[l + 1]]`` (bytes); labels without
+    spans have empty ranges."""
+    off = np.ascontiguousarray(offsets, np.uint32).reshape(-1)
+    L = off.shape[0] - 1
+    total = int(off[L])
+    sp = np.ascontiguousarray(spans, np.uint32).reshape(-1, 2)
+    if L < 0 or sp.shape[0] < total:
+        raise CsgIoError(f"spans_to_rle: {sp.shape[0]} spans, offsets end at {total}")
+    n_counts = 2 * total + L + 1          # at most 2 k + 1 counts for a label's k spans
+    counts = np.empty(n_counts, np.uint32)
+    text = np.empty(6 * n_counts, np.uint8)  # a count (or its difference) has at most 6 groups of 5 bits
+    c_off = np.zeros(L + 1, np.uint64)
+    s_off = np.zeros(L + 1, np.uint64)
+    _check(load().csgio_spans_to_rle(sp.ctypes.data, off.ctypes.data, L, int(height), int(width), counts.ctypes.data,
+                                     counts.shape[0], c_off.ctypes.data, text.ctypes.data, text.shape[0],
+                                     s_off.ctypes.data), "spans_to_rle", "")
+    return counts[:int(c_off[L])], c_off, text[:int(s_off[L])].tobytes(), s_off
+
+
 class LabelWriter:
     """Label files written natively (csgio_write_label_json, GIL released):
     byte-identical to ``save_label_json(label_record(...))`` (labels.py) for
@@ -260,3 +297,46 @@ class LabelWriter:
                   cv.ctypes.data if cv is not None else None, uv.ctypes.data, vis.ctypes.data,
                   C.cast(self.kp_name, C.c_void_p).value, lst.ctypes.data if lst is not None else None)
         _check(load().csgio_write_label_json(path.encode(), C.byref(L)), "write_label_json", path)
+
+
+class FragmentWriter:
+    """COCO fragments written natively (csgio_write_coco_fragment, GIL
+    released): byte-identical to ``masks.write_fragment`` for one scene's
+    objects (``poses`` of any epoch, labels.object_poses: inst_idx, class_id and
+    prim_path do not change between epochs) and keypoint table."""
+
+    def __init__(self, poses, kp_table, height: int, width: int):
+        import json
+        self.height, self.width = int(height), int(width)
+        n = len(poses)
+        self.n = n
+        self.labels = np.array([p["inst_idx"] for p in poses] or [0], np.int32)
+        self.classes = np.array([p["class_id"] for p in poses] or [0], np.int32)
+        self._paths = [json.dumps(p["prim_path"], ensure_ascii=False).encode("utf-8") for p in poses]
+        self.paths = (C.c_char_p * max(n, 1))(*self._paths)
+        by = [[] for _ in range(n)]
+        for k, (j, _) in enumerate(kp_table):
+            if j < n:
+                by[j].append(k)
+        self.n_kp = len(kp_table)
+        self.kp_off = np.zeros(n + 1, np.uint32)
+        self.kp_off[1:] = np.cumsum([len(x) for x in by])
+        self.kp_idx = np.array([k for x in by for k in x] or [0], np.uint32)
+
+    def write(self, path: str, frame_id: int, inst_stats: np.ndarray, spans: np.ndarray, offsets: np.ndarray,
+              kp_uv: Optional[np.ndarray] = None, kp_vis: Optional[np.ndarray] = None) -> None:
+        st = np.ascontiguousarray(inst_stats, np.uint32)
+        off = np.ascontiguousarray(offsets, np.uint32).reshape(-1)
+        sp = np.ascontiguousarray(spans, np.uint32).reshape(-1, 2)
+        if off.shape[0] != st.shape[0] + 1 or sp.shape[0] < int(off[-1]):
+            raise CsgIoError(f"write_coco_fragment: {st.shape[0]} labels, {off.shape[0]} offsets, {sp.shape[0]} spans")
+        n_kp = self.n_kp if kp_uv is not None and kp_vis is not None else 0
+        uv = np.ascontiguousarray(kp_uv, np.float32) if n_kp else None
+        vis = np.ascontiguousarray(kp_vis, np.int32) if n_kp else None
+        if n_kp and (uv.size < 2 * n_kp or vis.size < n_kp):
+            raise CsgIoError(f"write_coco_fragment: {n_kp} keypoints in the table, {vis.size} in the frame")
+        F = Coco(int(frame_id), self.height, self.width, self.n, st.shape[0], n_kp, self.labels.ctypes.data,
+                 self.classes.ctypes.data, C.cast(self.paths, C.c_void_p).value, self.kp_off.ctypes.data,
+                 self.kp_idx.ctypes.data, st.ctypes.data, sp.ctypes.data if sp.size else None, off.ctypes.data,
+                 uv.ctypes.data if n_kp else None, vis.ctypes.data if n_kp else None)
+        _check(load().csgio_write_coco_fragment(path.encode(), C.byref(F)), "write_coco_fragment", path)

@@ -647,6 +647,80 @@ typedef struct {
 } csg_amodal_geometry_job;
 int csg_crop_amodal_geometry(csg_ctx* ctx, const csg_amodal_geometry_job* job, uint32_t n_frames, void* stream);
 
+/* Per-object run-length masks: the vertical runs of every label of an instance
+ * image, in the column-major order of COCO's run-length masks, so that a
+ * frame's per-object masks leave the GPU as a few thousand 8-byte records
+ * instead of a dense image.  A stand-alone pass on device memory only, like
+ * the crops: it needs no scene and no earlier render, and the frame size is the
+ * job's own (as in csg_encode_files), not the context's.  Integers only.
+ *
+ * Definition.  `instance` is [n][H][W] int32, L = n_labels.  A pixel belongs to
+ * label l iff its id equals l and 0 <= l < L; every other value (-1, any other
+ * negative, >= L) belongs to no label.  A span of label l in frame f is a
+ * maximal run of vertically adjacent pixels of l within one column x, rows
+ * y0 .. y0 + len - 1; spans never cross a column boundary.  It is stored as a
+ * csg_span: start = x * H + y0 (COCO's column-major pixel index) and len.
+ *
+ *   spans         [n][C] csg_span, C = capacity.  Frame f uses spans[f * C ..],
+ *                 ordered by label ascending, then start ascending.
+ *   span_offsets  [n][L + 1] uint32.  Label l's spans of frame f are records
+ *                 [off[f][l], off[f][l + 1]) of the frame; off[f][0] = 0 and
+ *                 off[f][L] is the frame's total WHETHER OR NOT IT FITS.
+ *
+ * Overflow.  When a frame's total exceeds C, that frame's records are
+ * unspecified within its C slots (its offsets are still exact); nothing is
+ * written outside them and the other frames are unaffected.  The call is
+ * asynchronous and cannot return the overflow: the caller reads off[f][L] > C
+ * after its stream completes and repeats the pass with a larger C.  A frame has
+ * at most W * ((H + 1) / 2) spans.
+ *
+ * The result is a pure function of the input (the order is total; nothing in
+ * it depends on scheduling), every record below a fitting frame's total and
+ * every offset is written, and nothing else: records from a frame's total up to
+ * C keep what they held.  No input value makes a kernel read or write outside
+ * the arrays described.
+ *
+ * Enqueues on `stream` (NULL = the context's stream) and returns; behind the
+ * render that wrote `instance` on the same stream it needs no synchronisation.
+ * csg_synchronize waits for it under the rule for the crops.  The pass has
+ * scratch of its own (4 bytes per frame, label and 64 columns), grown to the
+ * job, and never touches the render's work buffers.
+ *
+ * CSG_ERR_INVALID, nothing enqueued or written: job, instance, spans or
+ * span_offsets NULL; n_frames == 0; width or height 0 or above 8192;
+ * capacity == 0; n_labels == 0; spans not 8-byte or span_offsets not 4-byte
+ * aligned.  CSG_ERR_LIMIT: n_labels above CSG_SPAN_MAX_LABELS (a wave keeps a
+ * 256-byte row per label in LDS; the one-byte id wire of csg_host_id_bytes
+ * marks the same practical range). */
+#define CSG_SPAN_MAX_LABELS 256u
+typedef struct {            /* 8 bytes */
+  uint32_t start;           /* x * height + y0 */
+  uint32_t len;             /* rows, >= 1 */
+} csg_span;
+
+typedef struct {
+  uint32_t width, height;      /* of the frames in `instance`: 1..8192 each */
+  uint32_t n_labels;           /* L: 1..CSG_SPAN_MAX_LABELS */
+  uint32_t capacity;           /* C: span records per frame, >= 1 */
+  const int32_t* instance;     /* DEVICE [n][H][W] */
+  csg_span* spans;             /* DEVICE [n][C], 8-B aligned */
+  uint32_t* span_offsets;      /* DEVICE [n][L + 1], 4-B aligned */
+} csg_span_job;
+int csg_mask_spans(csg_ctx* ctx, const csg_span_job* job, uint32_t n_frames, void* stream);
+
+/* The ids of a host-output batch for csg_mask_spans, without their trip to the
+ * host.  A host-output batch (csg_outputs.on_device = 0) renders the instance
+ * ids only when csg_outputs.instance asks for them, and then copies them.
+ * After csg_keep_instance(ctx, 1) every later host-output batch renders them
+ * into the context's own device image even when csg_outputs.instance is NULL,
+ * and copies nothing more than it did; 0 turns that off again.
+ * csg_last_instance returns the device image [n_frames][height][width] int32 of
+ * the context's last batch and its frame count (NULL and 0 when that batch
+ * rendered no ids, or wrote them to the caller's device memory); it stays
+ * valid until the context's next batch.  Neither call touches the GPU. */
+int csg_keep_instance(csg_ctx* ctx, int32_t keep);
+int csg_last_instance(csg_ctx* ctx, const int32_t** instance, uint32_t* n_frames);
+
 /* Stand-alone 3D->2D projection (host buffers): uv [n][2], vis [n] without a
  * depth test (1 = in front and inside the image, 0 otherwise). */
 int csg_project_keypoints(csg_ctx* ctx, const float* pts_world, uint32_t n, const float* view,
