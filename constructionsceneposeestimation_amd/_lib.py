@@ -31,7 +31,7 @@ EXPORTED = (
     "csg_instance_bounds", "csg_copy_files", "csg_host_alloc", "csg_host_free", "csg_size_work",
     "csg_get_work_info", "csg_host_id_bytes", "csg_set_object_frames", "csg_crop_objects", "csg_encode_files",
     "csg_crop_objects_filtered", "csg_crop_amodal", "csg_crop_amodal_geometry", "csg_mask_spans",
-    "csg_keep_instance", "csg_last_instance",
+    "csg_keep_instance", "csg_last_instance", "csg_amodal_spans",
 )
 
 
@@ -137,6 +137,12 @@ class SpanJob(C.Structure):
                 ("instance", C.c_void_p), ("spans", C.c_void_p), ("span_offsets", C.c_void_p)]
 
 
+class AmodalSpanJob(C.Structure):
+    """csg_amodal_span_job (csg_amodal_spans)."""
+    _fields_ = [("capacity", C.c_uint32), ("frames", C.c_void_p), ("eligible", C.c_void_p), ("spans", C.c_void_p),
+                ("span_offsets", C.c_void_p), ("amodal_stats", C.c_void_p)]
+
+
 class EncodeJob(C.Structure):
     """csg_encode_job (csg_encode_files)."""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n_frames", C.c_uint32), ("file_kinds", C.c_uint32),
@@ -217,6 +223,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     lib.csg_crop_amodal_geometry.argtypes = [vp, C.POINTER(AmodalGeometryJob), u32, vp]
     lib.csg_encode_files.argtypes = [vp, C.POINTER(EncodeJob)]
     lib.csg_mask_spans.argtypes = [vp, C.POINTER(SpanJob), u32, vp]
+    lib.csg_amodal_spans.argtypes = [vp, C.POINTER(AmodalSpanJob), u32, vp]
     lib.csg_keep_instance.argtypes = [vp, i32]
     lib.csg_last_instance.argtypes = [vp, C.POINTER(vp), C.POINTER(u32)]
     if lib.csg_abi_version() != ABI_VERSION:

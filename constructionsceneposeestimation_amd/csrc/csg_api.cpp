@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/csg_api.h"
+#include "csg_amodal_spans.h"
 #include "csg_crops.h"
 #include "csg_encode.h"
 #include "csg_kernels.h"
@@ -245,6 +246,15 @@ struct csg_ctx {
   hipEvent_t am_done = nullptr;
   hipStream_t am_stream = nullptr;
   bool am_busy = false;
+  // Full-frame amodal spans (csg_amodal_spans): host copies of the label -> chunks table (the item list
+  // of a job is built from them and the job's `eligible`), and the pass's scratch under am_done's
+  // ordering: the bit planes of one frame range, their "touched" words, the span counts, and the item
+  // and label -> plane tables with their pinned staging (as_stage_ev: the slot's last H2D copy).
+  std::vector<uint32_t> h_lab_off, h_lab_chunks;
+  DevBuf<uint32_t> as_planes, as_touched, as_cnt, as_tables;
+  uint32_t* as_stage = nullptr;
+  size_t as_stage_n = 0;
+  hipEvent_t as_stage_ev = nullptr;
   // Mask spans (csg_mask_spans): the pass's own scratch, the span counts [n][L][groups of 64 columns],
   // grown to the job; ms_done orders passes on different streams as am_done does the amodal passes.
   DevBuf<uint32_t> ms_cnt;
@@ -425,6 +435,9 @@ void csg_destroy(csg_ctx* c) {
     if (c->am_stage[k]) (void)hipHostFree(c->am_stage[k]);
     if (c->am_stage_ev[k]) (void)hipEventDestroy(c->am_stage_ev[k]);
   }
+  c->as_planes.release(); c->as_touched.release(); c->as_cnt.release(); c->as_tables.release();
+  if (c->as_stage) (void)hipHostFree(c->as_stage);
+  if (c->as_stage_ev) (void)hipEventDestroy(c->as_stage_ev);
   if (c->am_done) (void)hipEventDestroy(c->am_done);
   if (c->ms_busy) (void)hipEventSynchronize(c->ms_done);   // a span pass on a stream of the caller's
   c->ms_cnt.release();
@@ -570,6 +583,8 @@ int csg_upload_scene(csg_ctx* c, const csg_mesh* meshes, uint32_t n_meshes, cons
     HIP_TRY(c, hipMemcpy(c->lab_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(c->lab_chunks.p, list.data(), list.size() * 4, hipMemcpyHostToDevice));
     c->lab_max_chunks = most;
+    c->h_lab_off = off;
+    c->h_lab_chunks = list;
   }
   c->iset.release();   // rebuilt for the new instances by the next sync_scene_state
   HIP_TRY(c, hipMemcpy(c->chunks.p, ch.data(), ch.size() * sizeof(Chunk), hipMemcpyHostToDevice));
@@ -2282,6 +2297,114 @@ int csg_crop_amodal_geometry(csg_ctx* c, const csg_amodal_geometry_job* job, uin
     a.bits = g.depth ? reinterpret_cast<uint32_t*>(g.depth) : c->am_keys.p;
     HIP_TRY(c, hipMemsetAsync(a.bits, 0, (size_t)nf * per_frame * sizeof(uint32_t), st));
     launch_crop_amodal_geometry(scene_dev(c), a, g, nf, c->lab_max_chunks, st);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return am_end(c, st);
+}
+
+// Full-frame amodal spans: the scene tables and the caller's frames as the other amodal passes read
+// them; bit planes, counts and tables are scratch of the pass's own.  The planes are bounded at
+// kAmPlaneCap bytes: a job that needs more runs as frame ranges on the stream, each zeroing, filling and
+// reading the same scratch.
+int csg_amodal_spans(csg_ctx* c, const csg_amodal_span_job* job, uint32_t n_frames, void* stream) {
+  constexpr size_t kAmPlaneCap = 64u << 20;
+  if (!c) return CSG_ERR_INVALID;
+  if (!job) return c->fail(CSG_ERR_INVALID, "amodal_spans: null job");
+  if (n_frames == 0) return c->fail(CSG_ERR_INVALID, "amodal_spans: no frames");
+  if (!job->frames) return c->fail(CSG_ERR_INVALID, "amodal_spans: frames is NULL");
+  if (!job->spans || !job->span_offsets)
+    return c->fail(CSG_ERR_INVALID, "amodal_spans: spans and span_offsets must not be NULL");
+  if (job->capacity == 0) return c->fail(CSG_ERR_INVALID, "amodal_spans: capacity must be at least 1");
+  if (((uintptr_t)job->spans & 7u) || ((uintptr_t)job->span_offsets & 3u) || ((uintptr_t)job->amodal_stats & 3u))
+    return c->fail(CSG_ERR_INVALID, "amodal_spans: spans must be 8-byte aligned, span_offsets and amodal_stats 4-byte");
+  if (!c->have_scene) return c->fail(CSG_ERR_INVALID, "amodal_spans: no scene uploaded");
+  if (c->n_lab > CSG_SPAN_MAX_LABELS)
+    return c->fail(CSG_ERR_LIMIT, "amodal_spans: %u labels above CSG_SPAN_MAX_LABELS %u", c->n_lab, CSG_SPAN_MAX_LABELS);
+  for (uint32_t f = 0; f < n_frames; ++f)
+    if (job->frames[f].xform_set >= c->set_valid.size())
+      return c->fail(CSG_ERR_INVALID, "amodal_spans: frame %u: transform set %u is not resident (%u sets)", f,
+                     job->frames[f].xform_set, (unsigned)c->set_valid.size());
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+  int rc = sync_scene_state(c);
+  if (rc) return rc;
+  const uint32_t L = c->n_lab, W = c->cfg.width, H = c->cfg.height;
+  const uint32_t G = (W + 63u) / 64u, HW = (H + 31u) / 32u;
+  // the job's tables: label -> plane, and one (chunk, plane) item per chunk of an eligible label
+  std::vector<uint32_t> plane_of(L, kNoPlane), items_c, items_p;
+  uint32_t P = 0;
+  for (uint32_t l = 0; l < L; ++l) {
+    if (job->eligible && !job->eligible[l]) continue;
+    plane_of[l] = P;
+    for (uint32_t k = c->h_lab_off[l]; k < c->h_lab_off[l + 1]; ++k) {
+      items_c.push_back(c->h_lab_chunks[k]);
+      items_p.push_back(P);
+    }
+    ++P;
+  }
+  const uint32_t n_items = (uint32_t)items_c.size();
+  const size_t n_tab = (size_t)L + 2u * n_items;
+  const size_t per_frame = (size_t)P * HW * W;   // words of one frame's planes
+  size_t cap = kAmPlaneCap;
+  if (const char* e = getenv("CSG_AMODAL_PLANE_CAP")) cap = (size_t)strtoull(e, nullptr, 10);   // (tests: bytes)
+  uint32_t range = std::min<uint32_t>(n_frames, 65535u);   // grid z limit
+  if (per_frame) range = (uint32_t)std::min<size_t>(range, std::max<size_t>(1, cap / (per_frame * sizeof(uint32_t))));
+  const size_t n_planes = (size_t)range * per_frame, n_touched = (size_t)range * std::max(P, 1u);
+  const size_t n_cnt = (size_t)range * L * G;
+  if (!c->am_done) HIP_TRY(c, hipEventCreateWithFlags(&c->am_done, hipEventDisableTiming));
+  if (c->am_busy && (c->as_planes.n < n_planes || c->as_touched.n < n_touched || c->as_cnt.n < n_cnt ||
+                     c->as_tables.n < n_tab))
+    HIP_TRY(c, hipEventSynchronize(c->am_done));   // the last pass still reads what is freed below
+  HIP_TRY(c, c->as_planes.alloc(n_planes));
+  HIP_TRY(c, c->as_touched.alloc(n_touched));
+  HIP_TRY(c, c->as_cnt.alloc(n_cnt));
+  HIP_TRY(c, c->as_tables.alloc(n_tab));
+  rc = am_begin(c, job->frames, n_frames, 0, 0, st);   // (waits for a pass on another stream)
+  if (rc) return rc;
+  if (!c->as_stage_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->as_stage_ev, hipEventDisableTiming));
+  else HIP_TRY(c, hipEventSynchronize(c->as_stage_ev));   // the staging's last H2D copy is done
+  if (c->as_stage_n < n_tab) {
+    if (c->as_stage) HIP_TRY(c, hipHostFree(c->as_stage));
+    c->as_stage = nullptr;
+    c->as_stage_n = 0;
+    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->as_stage), sizeof(uint32_t) * n_tab));
+    c->as_stage_n = n_tab;
+  }
+  memcpy(c->as_stage, plane_of.data(), sizeof(uint32_t) * L);
+  if (n_items) {
+    memcpy(c->as_stage + L, items_c.data(), sizeof(uint32_t) * n_items);
+    memcpy(c->as_stage + L + n_items, items_p.data(), sizeof(uint32_t) * n_items);
+  }
+  HIP_TRY(c, hipMemcpyAsync(c->as_tables.p, c->as_stage, sizeof(uint32_t) * n_tab, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipEventRecord(c->as_stage_ev, st));
+  AmodalSpanDev a{};
+  a.W = W;
+  a.H = H;
+  a.L = L;
+  a.P = P;
+  a.G = G;
+  a.HW = HW;
+  a.C = job->capacity;
+  a.n_sets = (uint32_t)c->set_valid.size();
+  a.n_items = n_items;
+  a.plane_of = c->as_tables.p;
+  a.item_chunk = c->as_tables.p + L;
+  a.item_plane = c->as_tables.p + L + n_items;
+  a.chunks = c->chunks.p;
+  a.models = c->models.p;
+  a.iset = c->iset.p;
+  a.planes = c->as_planes.p;
+  a.touched = c->as_touched.p;
+  a.cnt = c->as_cnt.p;
+  for (uint32_t f0 = 0; f0 < n_frames; f0 += range) {   // every array from the range's first frame
+    const uint32_t nf = std::min(range, n_frames - f0);
+    a.frames = c->am_frames.p + f0;
+    a.spans = reinterpret_cast<SpanRec*>(job->spans) + (size_t)f0 * a.C;
+    a.offsets = job->span_offsets + (size_t)f0 * (L + 1u);
+    a.stats = job->amodal_stats ? job->amodal_stats + (size_t)f0 * L * 5u : nullptr;
+    if (per_frame) HIP_TRY(c, hipMemsetAsync(a.planes, 0, (size_t)nf * per_frame * sizeof(uint32_t), st));
+    HIP_TRY(c, hipMemsetAsync(a.touched, 0, n_touched * sizeof(uint32_t), st));
+    launch_amodal_spans(scene_dev(c), a, nf, st);
   }
   HIP_TRY(c, hipGetLastError());
   return am_end(c, st);

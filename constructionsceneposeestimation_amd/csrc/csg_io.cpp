@@ -423,7 +423,11 @@ int csgio_spans_to_rle(const uint32_t* spans, const uint32_t* offsets, uint32_t 
   return fits ? 0 : -ENOSPC;
 }
 
-int csgio_write_coco_fragment(const char* path, const csgio_coco* F) {
+}  // extern "C"
+
+// Both fragment writers: `ast`, `asp`, `aoff` are the frame's amodal stats, spans and offsets, or all NULL.
+static int write_coco(const char* path, const csgio_coco* F, const uint32_t* ast, const uint32_t* asp,
+                      const uint32_t* aoff) {
   if (!path || !F || !F->span_offsets || (F->n_objects && (!F->obj_label || !F->obj_class || !F->obj_path)) ||
       (F->n_labels && !F->inst_stats) || (F->n_kp && (!F->kp_uv || !F->kp_vis || !F->obj_kp_off || !F->obj_kp)))
     return -EINVAL;
@@ -434,8 +438,16 @@ int csgio_write_coco_fragment(const char* path, const csgio_coco* F) {
   const int rc = csgio_spans_to_rle(F->spans, F->span_offsets, L, F->height, F->width, nullptr, 0, c_off.data(),
                                     text.data(), text.size(), s_off.data());
   if (rc) return rc;
+  std::vector<char> atext;
+  std::vector<uint64_t> as_off(L + 1, 0);
+  if (aoff) {
+    atext.resize(6 * (2 * (uint64_t)aoff[L] + L + 1));
+    const int arc = csgio_spans_to_rle(asp, aoff, L, F->height, F->width, nullptr, 0, c_off.data(), atext.data(),
+                                       atext.size(), as_off.data());
+    if (arc) return arc;
+  }
   std::string o;
-  o.reserve(65536 + (size_t)s_off[L]);
+  o.reserve(65536 + (size_t)s_off[L] + (size_t)as_off[L]);
   char num[48];
   auto put_int = [&](long long v) { o.append(num, std::to_chars(num, num + sizeof num, v).ptr); };
   auto put_dbl = [&](double v) {
@@ -487,7 +499,32 @@ int csgio_write_coco_fragment(const char* path, const csgio_coco* F) {
       if (text[k] == '\\') o += '\\';
       o += text[k];
     }
-    o += "\"},\"inst_idx\":";
+    o += "\"}";
+    if (aoff && ast[(size_t)lab * 5] != 0) {   // the label's amodal mask (an eligible label of csg_amodal_spans)
+      const uint32_t* am = ast + (size_t)lab * 5;
+      if (as_off[lab + 1] == as_off[lab]) return -EINVAL;   // amodal pixels and no amodal spans
+      o += ",\"amodal_bbox\":[";
+      put_int(am[1]);
+      o += ',';
+      put_int(am[2]);
+      o += ',';
+      put_int((long long)am[3] - am[1] + 1);
+      o += ',';
+      put_int((long long)am[4] - am[2] + 1);
+      o += "],\"amodal_area\":";
+      put_int(am[0]);
+      o += ",\"amodal_segmentation\":{\"size\":[";
+      put_int(F->height);
+      o += ',';
+      put_int(F->width);
+      o += "],\"counts\":\"";
+      for (uint64_t k = as_off[lab]; k < as_off[lab + 1]; ++k) {
+        if (atext[k] == '\\') o += '\\';
+        o += atext[k];
+      }
+      o += "\"}";
+    }
+    o += ",\"inst_idx\":";
     put_int(lab);
     o += ",\"prim_path\":";
     o += F->obj_path[j];
@@ -515,6 +552,18 @@ int csgio_write_coco_fragment(const char* path, const csgio_coco* F) {
   if (!f.f) return -errno;
   if (!f.write(o.data(), o.size())) return -EIO;
   return f.close();
+}
+
+extern "C" {
+
+int csgio_write_coco_fragment(const char* path, const csgio_coco* F) {
+  return write_coco(path, F, nullptr, nullptr, nullptr);
+}
+
+int csgio_write_coco_fragment_amodal(const char* path, const csgio_coco* F, const uint32_t* amodal_stats,
+                                     const uint32_t* amodal_spans, const uint32_t* amodal_offsets) {
+  if (!amodal_stats || !amodal_offsets) return -EINVAL;
+  return write_coco(path, F, amodal_stats, amodal_spans, amodal_offsets);
 }
 
 }  // extern "C"

@@ -131,6 +131,18 @@ def spans_to_mask(size: Tuple[int, int], spans: np.ndarray) -> np.ndarray:
     return (np.cumsum(d[:-1]) > 0).reshape(W, H).T
 
 
+def visible_fraction(inst_stats: np.ndarray, amodal_stats: np.ndarray) -> np.ndarray:
+    """BOP's ``visib_fract`` per label: visible pixels / amodal pixels, from the
+    ``inst_stats`` of a render and the ``amodal_stats`` of ``Renderer.amodal_spans``
+    of the same frames (``(..., L, 5)`` each; column 0 is the pixel count).
+    float64, NaN where the amodal count is 0."""
+    vis = np.asarray(inst_stats)[..., 0].astype(np.float64)
+    amo = np.asarray(amodal_stats)[..., 0].astype(np.float64)
+    out = np.full(vis.shape, np.nan)
+    np.divide(vis, amo, out=out, where=amo != 0)
+    return out
+
+
 # -- the generator's per-frame fragment ---------------------------------------------------
 def keypoints_by_object(kp_table) -> Dict[int, List[int]]:
     """object index -> indices of its keypoints, in table order (Workload.kp_table)."""
@@ -147,19 +159,39 @@ def image_record(frame_id: int, height: int, width: int) -> dict:
 
 def coco_fragment(frame_id: int, height: int, width: int, poses: List[dict], inst_stats: np.ndarray,
                   spans: np.ndarray, offsets: np.ndarray, kp_by_obj: Optional[Dict[int, List[int]]] = None,
-                  kp_uv: Optional[np.ndarray] = None, kp_vis: Optional[np.ndarray] = None) -> dict:
+                  kp_uv: Optional[np.ndarray] = None, kp_vis: Optional[np.ndarray] = None,
+                  amodal_spans: Optional[np.ndarray] = None, amodal_offsets: Optional[np.ndarray] = None,
+                  amodal_stats: Optional[np.ndarray] = None) -> dict:
     """One frame's COCO ``image`` record and ``annotations``: one per object of
     ``poses`` (labels.object_poses) with visible pixels.  ``bbox`` = [x, y, w,
     h] and ``area`` come from the GPU's ``inst_stats`` (pixels, inclusive box),
     the mask from the frame's ``spans`` / ``offsets`` through the native
     ``writers.spans_to_rle``; ``keypoints`` are the object's label keypoints as
     [u, v, vis, ...] with the label file's visibility codes.  Ids are
-    deterministic: ``image_id = frame_id``, ``id = frame_id * 65536 + inst_idx``."""
+    deterministic: ``image_id = frame_id``, ``id = frame_id * 65536 + inst_idx``.
+
+    With ``amodal_spans`` / ``amodal_offsets`` / ``amodal_stats`` (one frame of
+    ``Renderer.amodal_spans``; all three or none) an annotation whose label has
+    amodal pixels -- every listed object of an eligible label -- gains, directly
+    after ``segmentation``, ``amodal_bbox`` [x, y, w, h], ``amodal_area`` and
+    ``amodal_segmentation`` {size, counts}: the object's full silhouette as if
+    nothing stood in front of it (BOP's ``bbox_obj``, ``px_count_all`` and
+    ``mask``).  Which objects are listed does not change."""
     from . import writers
     off = np.asarray(offsets, np.uint32).reshape(-1)
     L = off.shape[0] - 1
     _, _, text, s_off = writers.spans_to_rle(spans, off, height, width)
     s_off = s_off.tolist()
+    amodal = amodal_spans is not None or amodal_offsets is not None or amodal_stats is not None
+    if amodal:
+        if amodal_spans is None or amodal_offsets is None or amodal_stats is None:
+            raise ValueError("coco_fragment: amodal_spans, amodal_offsets and amodal_stats go together")
+        a_off = np.asarray(amodal_offsets, np.uint32).reshape(-1)
+        _, _, a_text, as_off = writers.spans_to_rle(amodal_spans, a_off, height, width)
+        as_off = as_off.tolist()
+        a_stats = np.asarray(amodal_stats).tolist()
+        if a_off.shape[0] != L + 1 or len(a_stats) != len(np.asarray(inst_stats)):
+            raise ValueError("coco_fragment: the amodal arrays are of another label table")
     stats = np.asarray(inst_stats).tolist()
     uv = kp_uv.tolist() if kp_uv is not None else None
     vis = kp_vis.tolist() if kp_vis is not None else None
@@ -174,8 +206,18 @@ def coco_fragment(frame_id: int, height: int, width: int, poses: List[dict], ins
         a = {"id": int(frame_id) * ANN_ID_STRIDE + i, "image_id": int(frame_id), "category_id": int(p["class_id"]),
              "bbox": [x0, y0, x1 - x0 + 1, y1 - y0 + 1], "area": px, "iscrowd": 0,
              "segmentation": {"size": [int(height), int(width)],
-                              "counts": text[int(s_off[i]):int(s_off[i + 1])].decode("ascii")},
-             "inst_idx": i, "prim_path": p["prim_path"]}
+                              "counts": text[int(s_off[i]):int(s_off[i + 1])].decode("ascii")}}
+        if amodal and a_stats[i][0] != 0:
+            if as_off[i + 1] == as_off[i]:
+                raise ValueError(f"coco_fragment: frame {frame_id}: label {i} has {a_stats[i][0]} amodal pixels "
+                                 f"and no amodal spans")
+            apx, ax0, ay0, ax1, ay1 = a_stats[i]
+            a["amodal_bbox"] = [ax0, ay0, ax1 - ax0 + 1, ay1 - ay0 + 1]
+            a["amodal_area"] = apx
+            a["amodal_segmentation"] = {"size": [int(height), int(width)],
+                                        "counts": a_text[int(as_off[i]):int(as_off[i + 1])].decode("ascii")}
+        a["inst_idx"] = i
+        a["prim_path"] = p["prim_path"]
         ks = kp_by_obj.get(j) if kp_by_obj is not None and uv is not None else None
         if ks:
             flat = []

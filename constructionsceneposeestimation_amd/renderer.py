@@ -36,6 +36,10 @@ OUTPUT_KINDS = ("rgb", "instance", "depth", "keypoints", "stats", "normals", "po
 # most of them): the largest count plus three eighths, 640 KiB of device memory per frame of a batch.
 # Only the records in use are copied to the host.
 DEFAULT_SPAN_CAPACITY = 81920
+# ... and Renderer.amodal_spans_host: with every label of C3 at 1080p 30.3 thousand amodal spans per frame
+# on average, 65.4 thousand at the 99th percentile and 73.0 thousand at most over 480 frames (the dynamic
+# kinds alone: 1.6, 3.7 and 4.4 thousand; profiles/amodal_rle/cost.json); the same rule, 784 KiB per frame.
+DEFAULT_AMODAL_SPAN_CAPACITY = 100352
 
 
 def make_frames(views: np.ndarray, projs: np.ndarray, sets: Sequence[int], frame_ids: Sequence[int]) -> np.ndarray:
@@ -631,6 +635,97 @@ class Renderer:
             st.synchronize()
             sp = h_sp.numpy().view(np.uint32).copy()
         return [(off[f], sp[int(ends[f] - totals[f]):int(ends[f])]) for f in range(n)], cap
+
+    # -- full-frame amodal masks as spans ------------------------------------------
+    def amodal_spans(self, frames: np.ndarray, *, spans: int, span_offsets: int, capacity: int, amodal_stats: int = 0,
+                     eligible=None, stream: int = 0) -> None:
+        """Enqueue the amodal mask spans of ``frames`` (csg_amodal_spans; raw
+        device pointers, like :meth:`mask_spans`): for every label its full
+        silhouette over the frame as if nothing stood in front of it -- the
+        pixels some triangle of the label covers, with the depth range and the
+        alpha test but no depth test -- as the records :meth:`mask_spans` makes
+        of the visible ids: ``spans`` (n, capacity, 2) uint32 ordered by label
+        then start, ``span_offsets`` (n, L + 1) uint32 with ``off[f, L]`` the
+        frame's total whether or not it fits.  Spans of different labels may
+        overlap.  ``amodal_stats`` (n, L, 5) uint32, or 0, gets each mask's
+        pixel count and inclusive box (the layout of ``inst_stats``).
+        ``frames`` are the HOST records of the frames (FRAME_DTYPE: view, proj
+        and transform set are read), copied before the call returns;
+        ``eligible`` an optional mask of the labels wanted (the others get no
+        spans and empty stats).  L is the uploaded scene's label-table length,
+        the largest instance label + 1 (``n_labels`` unless the scene lists
+        objects without instances; a longer ``eligible`` is cut to it)."""
+        frames = np.ascontiguousarray(frames, FRAME_DTYPE)
+        el = None
+        if eligible is not None:
+            el = np.ascontiguousarray(np.asarray(eligible).reshape(-1)[:self._n_inst_labels]).astype(np.uint8)
+            if el.shape != (self._n_inst_labels,):
+                raise ValueError(f"amodal_spans: eligible has {el.shape[0]} entries, the scene {self._n_inst_labels} labels")
+        job = _lib.AmodalSpanJob(int(capacity), frames.ctypes.data, el.ctypes.data if el is not None else None,
+                                 spans or None, span_offsets or None, amodal_stats or None)
+        self._check(self.lib.csg_amodal_spans(self.ctx, C.byref(job), int(frames.shape[0]), stream or None),
+                    "amodal_spans")
+
+    def amodal_spans_host(self, frames: np.ndarray, *, capacity: int = 0, eligible=None):
+        """:meth:`amodal_spans` delivered to the host: returns ``(frames, stats,
+        capacity)`` where ``frames`` is a list of ``n`` pairs ``(offsets
+        (L + 1,) uint32, spans (total, 2) uint32)``, ``stats`` the (n, L, 5)
+        uint32 amodal pixel counts and boxes (L = ``n_labels`` here, the table
+        length of ``inst_stats``), and ``capacity`` the per-frame
+        capacity that was enough.  As :meth:`mask_spans_host`: the pass starts
+        at ``capacity`` (0: ``DEFAULT_AMODAL_SPAN_CAPACITY``) and is repeated
+        with the capacity doubled (at least the largest total seen) until every
+        frame fits; offsets and stats follow the pass into page-locked memory, and
+        the records in use are packed on the device and copied once.
+        Synchronous."""
+        import torch
+        frames = np.ascontiguousarray(frames, FRAME_DTYPE)
+        n, L = int(frames.shape[0]), self._n_inst_labels
+        cap = int(capacity) or DEFAULT_AMODAL_SPAN_CAPACITY
+        dev = torch.device("cuda", self.device)
+        self.synchronize()
+        if getattr(self, "_span_stream", None) is None:
+            self._span_stream, self._span_pin = torch.cuda.Stream(dev), {}
+        st = self._span_stream
+
+        def pinned(name: str, count: int):   # a page-locked int32 staging tensor, grown by doubling and kept
+            t = self._span_pin.get(name)
+            if t is None or t.numel() < count:
+                t = torch.empty(max(count, 2 * (t.numel() if t is not None else 0), 1024), dtype=torch.int32,
+                                pin_memory=True)
+                self._span_pin[name] = t
+            return t[:count]
+
+        with torch.cuda.stream(st):
+            d_off = torch.empty((n, L + 1), dtype=torch.int32, device=dev)
+            d_st = torch.empty((n, L, 5), dtype=torch.int32, device=dev)
+            h_off = pinned("offsets", n * (L + 1)).view(n, L + 1)
+            h_st = pinned("amodal_stats", n * L * 5).view(n, L, 5)
+            while True:
+                d_sp = torch.empty((n, cap, 2), dtype=torch.int32, device=dev)
+                self.amodal_spans(frames, spans=d_sp.data_ptr(), span_offsets=d_off.data_ptr(), capacity=cap,
+                                  amodal_stats=d_st.data_ptr(), eligible=eligible, stream=st.cuda_stream)
+                h_off.copy_(d_off, non_blocking=True)
+                h_st.copy_(d_st, non_blocking=True)
+                st.synchronize()
+                off = h_off.numpy().view(np.uint32).copy()
+                top = int(off[:, L].max())
+                if top <= cap:
+                    break
+                cap = max(2 * cap, top)
+            stats = h_st.numpy().view(np.uint32).copy()
+            totals = off[:, L].astype(np.int64)
+            if self.n_labels > L:   # labels without instances: no spans, empty stats, in inst_stats' table length
+                off = np.concatenate([off, np.repeat(off[:, L:], self.n_labels - L, axis=1)], axis=1)
+                pad = np.tile(np.array([0, 0xFFFFFFFF, 0xFFFFFFFF, 0, 0], np.uint32), (n, self.n_labels - L, 1))
+                stats = np.concatenate([stats, pad], axis=1)
+            ends = np.cumsum(totals)
+            packed = torch.cat([d_sp[f, :int(totals[f])] for f in range(n)])   # the records in use, and no more
+            h_sp = pinned("spans", 2 * int(ends[-1])).view(int(ends[-1]), 2)
+            h_sp.copy_(packed, non_blocking=True)
+            st.synchronize()
+            sp = h_sp.numpy().view(np.uint32).copy()
+        return [(off[f], sp[int(ends[f] - totals[f]):int(ends[f])]) for f in range(n)], stats, cap
 
     def keep_instance(self, keep: bool = True) -> None:
         """Host-output batches (:meth:`render`, :meth:`render_files`) keep their

@@ -16,10 +16,10 @@ import numpy as np
 
 from .build import IO_LIB, build_io, needs_build, IO_DEPS
 
-ABI_VERSION = 5  # CSGIO_ABI_VERSION in include/csg_io.h
+ABI_VERSION = 6  # CSGIO_ABI_VERSION in include/csg_io.h
 EXPORTED = ("csgio_abi_version", "csgio_write_png_rgb", "csgio_write_npy", "csgio_write_depth_csv",
             "csgio_write_pointcloud_txt", "csgio_depth_stats", "csgio_write_label_json", "csgio_spans_to_rle",
-            "csgio_write_coco_fragment")
+            "csgio_write_coco_fragment", "csgio_write_coco_fragment_amodal")
 PNG_STRATEGY = {"default": 0, "rle": 1, "huffman": 2}
 _lib: Optional[C.CDLL] = None
 
@@ -67,6 +67,7 @@ def load() -> C.CDLL:
     lib.csgio_write_label_json.argtypes = [cp, C.POINTER(Label)]
     lib.csgio_spans_to_rle.argtypes = [vp, vp, u32, u32, u32, vp, u64, vp, vp, u64, vp]
     lib.csgio_write_coco_fragment.argtypes = [cp, C.POINTER(Coco)]
+    lib.csgio_write_coco_fragment_amodal.argtypes = [cp, C.POINTER(Coco), vp, vp, vp]
     if lib.csgio_abi_version() != ABI_VERSION:
         raise CsgIoError(f"libcsgio.so ABI {lib.csgio_abi_version()} != binding ABI {ABI_VERSION}; rebuild")
     _lib = lib
@@ -324,7 +325,12 @@ class FragmentWriter:
         self.kp_idx = np.array([k for x in by for k in x] or [0], np.uint32)
 
     def write(self, path: str, frame_id: int, inst_stats: np.ndarray, spans: np.ndarray, offsets: np.ndarray,
-              kp_uv: Optional[np.ndarray] = None, kp_vis: Optional[np.ndarray] = None) -> None:
+              kp_uv: Optional[np.ndarray] = None, kp_vis: Optional[np.ndarray] = None,
+              amodal_spans: Optional[np.ndarray] = None, amodal_offsets: Optional[np.ndarray] = None,
+              amodal_stats: Optional[np.ndarray] = None) -> None:
+        """With the three amodal arrays (one frame of ``Renderer.amodal_spans``)
+        the fragment carries the amodal keys of ``masks.coco_fragment``
+        (csgio_write_coco_fragment_amodal)."""
         st = np.ascontiguousarray(inst_stats, np.uint32)
         off = np.ascontiguousarray(offsets, np.uint32).reshape(-1)
         sp = np.ascontiguousarray(spans, np.uint32).reshape(-1, 2)
@@ -339,4 +345,17 @@ class FragmentWriter:
                  self.classes.ctypes.data, C.cast(self.paths, C.c_void_p).value, self.kp_off.ctypes.data,
                  self.kp_idx.ctypes.data, st.ctypes.data, sp.ctypes.data if sp.size else None, off.ctypes.data,
                  uv.ctypes.data if n_kp else None, vis.ctypes.data if n_kp else None)
-        _check(load().csgio_write_coco_fragment(path.encode(), C.byref(F)), "write_coco_fragment", path)
+        if amodal_spans is None and amodal_offsets is None and amodal_stats is None:
+            _check(load().csgio_write_coco_fragment(path.encode(), C.byref(F)), "write_coco_fragment", path)
+            return
+        if amodal_spans is None or amodal_offsets is None or amodal_stats is None:
+            raise CsgIoError("write_coco_fragment: amodal_spans, amodal_offsets and amodal_stats go together")
+        ast = np.ascontiguousarray(amodal_stats, np.uint32)
+        aoff = np.ascontiguousarray(amodal_offsets, np.uint32).reshape(-1)
+        asp = np.ascontiguousarray(amodal_spans, np.uint32).reshape(-1, 2)
+        if ast.shape != st.shape or aoff.shape[0] != off.shape[0] or asp.shape[0] < int(aoff[-1]):
+            raise CsgIoError(f"write_coco_fragment: amodal arrays of {ast.shape[0]} labels, {aoff.shape[0]} offsets, "
+                             f"{asp.shape[0]} spans")
+        _check(load().csgio_write_coco_fragment_amodal(path.encode(), C.byref(F), ast.ctypes.data,
+                                                       asp.ctypes.data if asp.size else None, aoff.ctypes.data),
+               "write_coco_fragment_amodal", path)

@@ -60,6 +60,10 @@
  *                               would render the frame once more per object
  *   csg_crop_amodal_geometry .. (new) the amodal depth and object coordinates of each
  *                               crop (and its amodal mask) from one pass of the same kind
+ *   csg_mask_spans ............ (new) per-object run-length masks (COCO RLE spans) of
+ *                               the visible ids
+ *   csg_amodal_spans .......... (new) the same spans of every object's amodal mask over
+ *                               the whole frame, with its amodal box and pixel count
  *   csg_last_error / csg_destroy
  *
  * Threading: several contexts may share a device (each has its own stream
@@ -720,6 +724,65 @@ int csg_mask_spans(csg_ctx* ctx, const csg_span_job* job, uint32_t n_frames, voi
  * valid until the context's next batch.  Neither call touches the GPU. */
 int csg_keep_instance(csg_ctx* ctx, int32_t keep);
 int csg_last_instance(csg_ctx* ctx, const int32_t** instance, uint32_t* n_frames);
+
+/* Full-frame amodal object masks as run-length spans: for every label its
+ * silhouette over the whole frame as if nothing stood in front of it (BOP's
+ * `mask` next to `mask_visib`), in the layout of csg_mask_spans, with the amodal
+ * box (`bbox_obj`) and pixel count (`px_count_all`), from one pass over the
+ * scene.  L is the uploaded scene's label-table length (largest instance label
+ * + 1, at least 1); W and H are the context's frame size.
+ *
+ * Definition.  Pixel (x, y) of frame f belongs to the amodal mask of label l iff
+ * eligible[l] holds (NULL = every label) and the pixel satisfies
+ * csg_crop_amodal's condition at (px, py) = (x, y): some instance with
+ * inst_idx == l has a triangle one of whose raster sub-triangles covers the
+ * pixel centre under the frame's transform set (spec 3.1-3.4), with its 1/W in
+ * [1/far, 1/near] (3.5) and passing the alpha test with the material that set
+ * gives the instance (3.6, texture swaps applied).  There is no depth test and
+ * no per-tile label cap: equivalently, the pixel is not -1 in a render of the
+ * frame with every instance of another label removed.  So every pixel whose
+ * rendered id is l lies in l's mask, and masks of different labels may overlap.
+ *
+ *   spans, span_offsets  the spans of that per-label mask under exactly
+ *                 csg_mask_spans' rules: vertical runs, start = x * H + y0,
+ *                 ordered by label and then by start; off[f][0] = 0 and
+ *                 off[f][L] is the frame's total WHETHER OR NOT IT FITS C.  An
+ *                 overflowing frame has unspecified records inside its own C
+ *                 slots and exact offsets; nothing outside its slots is written
+ *                 and other frames are unaffected.  Records from a fitting
+ *                 frame's total up to C keep what they held.
+ *   amodal_stats  [n][L][5] uint32 = pixels, minx, miny, maxx, maxy of the mask
+ *                 (inclusive box, inside the frame by construction); a label
+ *                 without pixels gets inst_stats' empty value (0, 0xFFFFFFFF,
+ *                 0xFFFFFFFF, 0, 0).  Every entry is written.  May be NULL.
+ *
+ * A transform set inside the resident range that was never uploaded draws
+ * nothing.  The result is a pure function of the input.
+ *
+ * Asynchronous on `stream`; the stream, ownership and csg_synchronize rules are
+ * csg_crop_amodal's: `frames` and `eligible` are copied before the call
+ * returns, pending scene changes are uploaded first as by a render, and the
+ * completion event shared with the other amodal passes orders the pass against
+ * scene uploads, reallocation and passes on other streams.  Scratch is the
+ * pass's own, never the render's work buffers: one bit per pixel, eligible label
+ * and frame of a range (rows packed 32 to a word), bounded at 64 MiB -- a job
+ * that needs more runs as frame ranges on the stream, each range zeroing,
+ * filling and reading the same scratch (at least one frame per range).
+ * CSG_AMODAL_PLANE_CAP (bytes) overrides the bound.
+ *
+ * CSG_ERR_INVALID, nothing enqueued or written: job, frames, spans or
+ * span_offsets NULL; n_frames == 0; capacity == 0; spans not 8-byte or
+ * span_offsets / amodal_stats not 4-byte aligned; no scene uploaded; a frame's
+ * xform_set not resident.  CSG_ERR_LIMIT: L above CSG_SPAN_MAX_LABELS. */
+typedef struct {
+  uint32_t capacity;          /* C: span records per frame, >= 1 */
+  const csg_frame* frames;    /* HOST [n]: view, proj, xform_set; copied before the call returns */
+  const uint8_t* eligible;    /* HOST [L] or NULL (= all): labels with 0 get no spans and empty stats; copied */
+  csg_span* spans;            /* DEVICE [n][C], 8-B aligned */
+  uint32_t* span_offsets;     /* DEVICE [n][L + 1], 4-B aligned */
+  uint32_t* amodal_stats;     /* DEVICE [n][L][5] = pixels, minx, miny, maxx, maxy, 4-B aligned, or NULL */
+} csg_amodal_span_job;
+int csg_amodal_spans(csg_ctx* ctx, const csg_amodal_span_job* job, uint32_t n_frames, void* stream);
 
 /* Stand-alone 3D->2D projection (host buffers): uv [n][2], vis [n] without a
  * depth test (1 = in front and inside the image, 0 otherwise). */

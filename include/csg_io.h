@@ -17,7 +17,7 @@
  *   csgio_write_label_json ..... save_label_json(json.dump indent=2) of
  *                                the frame's label record            :608-613, :2056-2064
  *
- * Without a counterpart there: csgio_spans_to_rle and csgio_write_coco_fragment,
+ * Without a counterpart there: csgio_spans_to_rle, csgio_write_coco_fragment and csgio_write_coco_fragment_amodal,
  * the COCO run-length masks and per-frame annotation files made from the GPU's
  * mask spans.
  *
@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CSGIO_ABI_VERSION 5
+#define CSGIO_ABI_VERSION 6
 
 int csgio_abi_version(void);
 
@@ -144,6 +144,19 @@ typedef struct {
 } csgio_coco;
 
 int csgio_write_coco_fragment(const char* path, const csgio_coco* fragment);
+
+/* The same fragment with the objects' amodal masks (the generator's
+ * "amodal_rle" output), byte-identical to masks.coco_fragment(...) with its
+ * amodal arguments: amodal_stats [n_labels][5], amodal_spans and amodal_offsets
+ * [n_labels + 1] are one frame of csg_amodal_spans (include/csg_api.h) in the
+ * layout of inst_stats, spans and span_offsets.  An annotation whose label has
+ * amodal pixels (amodal_stats[label][0] != 0: every listed object of an eligible
+ * label) gains, directly after `segmentation`, amodal_bbox [x, y, w, h],
+ * amodal_area and amodal_segmentation {size, counts}.  Which objects are listed
+ * does not change.  -EINVAL also for a NULL amodal_stats or amodal_offsets and
+ * for a label with amodal pixels and no amodal spans. */
+int csgio_write_coco_fragment_amodal(const char* path, const csgio_coco* fragment, const uint32_t* amodal_stats,
+                                     const uint32_t* amodal_spans, const uint32_t* amodal_offsets);
 
 #ifdef __cplusplus
 }
