@@ -23,6 +23,7 @@ DEPS = SOURCES + [os.path.join(PKG, "csrc", "csg_kernels.h"), os.path.join(PKG, 
                   os.path.join(PKG, "csrc", "csg_crops.h"), os.path.join(PKG, "csrc", "csg_spans.h"),
                   os.path.join(PKG, "csrc", "csg_amodal_spans.h"), os.path.join(PKG, "csrc", "csg_raster_math.h"),
                   os.path.join(PKG, "csrc", "csg_amodal_tri.inc"),
+                  os.path.join(PKG, "csrc", "csg_alpha_box.h"),
                   os.path.join(ROOT, "include", "csg_api.h")]
 ARCH = os.environ.get("CSG_OFFLOAD_ARCH", "gfx950")
 IO_LIB = os.path.join(PKG, "libcsgio.so")

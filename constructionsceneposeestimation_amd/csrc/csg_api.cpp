@@ -15,11 +15,14 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <map>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/csg_api.h"
+#include "csg_alpha_box.h"
 #include "csg_amodal_spans.h"
 #include "csg_crops.h"
 #include "csg_encode.h"
@@ -89,6 +92,13 @@ struct csg_ctx {
   uint32_t n_inst = 0, n_meshes = 0, n_materials = 0;
   uint64_t n_tris_total = 0;
   DevBuf<float> tri_pos, tri_uv;       // de-indexed triangle soup (see SceneDev)
+  // Alpha trim (csg_alpha_box.h): one opaque uv box per soup triangle, built by sync_scene_state from the
+  // mesh's authored alpha texture and threshold (h_abox_tex: that texture per mesh, -1: no box built).
+  // CSG_ALPHA_TRIM=0 uploads "full" boxes and sets no InstSetDev::trim: nothing is trimmed (A/B, tests).
+  DevBuf<float> abox;                   // [T][4] u_lo u_hi v_lo v_hi
+  std::vector<float> h_tri_uv;          // host copy of tri_uv (the boxes are rebuilt when textures change)
+  std::vector<int32_t> h_abox_tex;      // per mesh
+  bool alpha_trim = true;
   DevBuf<InstDesc> inst;
   std::vector<MatDesc> h_mats;
   std::vector<MatDesc> h_set_mats;      // [sets][n_materials] as uploaded
@@ -368,6 +378,7 @@ int csg_create(const csg_config* cfg, csg_ctx** out) {
   if (const char* d = getenv("CSG_DEBUG")) c->dbg = (uint32_t)strtoul(d, nullptr, 0);
   if (const char* v = getenv("CSG_NARROW_IDS")) c->narrow_ids = atoi(v) != 0;
   if (const char* v = getenv("CSG_SPLIT_PAGEABLE")) c->split_pageable = atoi(v) != 0;
+  if (const char* v = getenv("CSG_ALPHA_TRIM")) c->alpha_trim = atoi(v) != 0;
   c->chain_frames = cfg->frames_per_launch ? cfg->frames_per_launch : kAutoChainFrames;
   if (const char* v = getenv("CSG_CHAIN")) c->chain_frames = (uint32_t)std::max(1, atoi(v));
   c->chain_frames = std::min(c->chain_frames, cfg->max_frames);
@@ -411,7 +422,7 @@ void csg_destroy(csg_ctx* c) {
   // (every batch's stream waits for its copies and id widening on the copy
   // stream, copy_done; synchronized here too before the buffers they read go)
   if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
-  c->tri_pos.release(); c->tri_uv.release(); c->inst.release(); c->set_mats.release(); c->iset.release(); c->lights.release();
+  c->tri_pos.release(); c->tri_uv.release(); c->abox.release(); c->inst.release(); c->set_mats.release(); c->iset.release(); c->lights.release();
   c->chunks.release();
   c->texels.release();
   c->aquad.release();
@@ -587,6 +598,8 @@ int csg_upload_scene(csg_ctx* c, const csg_mesh* meshes, uint32_t n_meshes, cons
     c->h_lab_chunks = list;
   }
   c->iset.release();   // rebuilt for the new instances by the next sync_scene_state
+  c->abox.release();   // so are the triangles' opaque boxes
+  c->h_tri_uv = tri_uv;
   HIP_TRY(c, hipMemcpy(c->chunks.p, ch.data(), ch.size() * sizeof(Chunk), hipMemcpyHostToDevice));
   c->n_inst = n_inst;
   c->n_meshes = n_meshes;
@@ -765,6 +778,45 @@ static int build_alpha_classes(csg_ctx* c, const std::vector<TexDesc>& td, size_
   return CSG_OK;
 }
 
+// The opaque uv box of every soup triangle (csg_alpha_box.h) whose mesh has uvs and an authored
+// alpha-tested material with a texture; "full" for all others, and for all with CSG_ALPHA_TRIM=0.
+static int build_alpha_boxes(csg_ctx* c) {
+  const size_t n_soup = c->h_tri_uv.size() / 6;
+  std::vector<float> box(std::max<size_t>(n_soup, 1) * 4);
+  for (size_t g = 0; g < box.size() / 4; ++g) alpha_box_full(&box[g * 4]);
+  c->h_abox_tex.assign(c->h_meshes.size(), -1);
+  std::map<std::pair<int, uint32_t>, AlphaScan> scans;   // (texture, threshold)
+  for (size_t m = 0; m < c->h_meshes.size() && c->alpha_trim; ++m) {
+    const MeshDesc& d = c->h_meshes[m];
+    const MatDesc& mat = c->h_mats[d.material];
+    if (!d.has_uv || !mat.alpha_test || mat.texture < 0 || (size_t)mat.texture >= c->textures.size() ||
+        !c->textures[mat.texture].present || mat.alpha_threshold >= 255u)
+      continue;
+    const HostTexture& t = c->textures[mat.texture];
+    AlphaScan& sc = scans[{mat.texture, mat.alpha_threshold}];
+    if (sc.w == 0) alpha_scan_build(t.rgba.data(), t.w, t.h, mat.alpha_threshold, sc);
+    for (uint32_t k = 0; k < d.ntris; ++k) {
+      const size_t g = (size_t)d.tbase + k;
+      alpha_tri_box(sc, &c->h_tri_uv[g * 6], &box[g * 4]);
+    }
+    c->h_abox_tex[m] = mat.texture;
+  }
+  HIP_TRY(c, c->abox.alloc(box.size()));
+  HIP_TRY(c, hipMemcpy(c->abox.p, box.data(), box.size() * 4, hipMemcpyHostToDevice));
+  return CSG_OK;
+}
+
+// The alpha channels of two textures are byte-identical (same size): boxes built from one hold for the other.
+static bool same_alpha(const csg_ctx* c, int a, int b) {
+  if (a == b) return true;
+  const HostTexture& x = c->textures[a];
+  const HostTexture& y = c->textures[b];
+  if (x.w != y.w || x.h != y.h) return false;
+  for (size_t k = 3; k < x.rgba.size(); k += 4)
+    if (x.rgba[k] != y.rgba[k]) return false;
+  return true;
+}
+
 static int sync_scene_state(csg_ctx* c) {
   const uint32_t n_sets = (uint32_t)c->set_valid.size();
   if (c->tex_dirty || c->dr_dirty || c->models_dirty || (c->kp_dirty && c->n_kp) || c->n_table_sets != n_sets) {
@@ -777,6 +829,7 @@ static int sync_scene_state(csg_ctx* c) {
   const bool tex_changed = c->tex_dirty;
   const bool iset_dirty = c->tex_dirty || c->dr_dirty || c->n_table_sets != n_sets || !c->iset.p;
   const bool cls_dirty = c->tex_dirty || c->dr_dirty || c->n_table_sets != n_sets || !c->acls.p;
+  const bool box_dirty = c->tex_dirty || !c->abox.p;
   std::vector<TexDesc> td(c->textures.size());
   size_t total = 0;
   for (size_t k = 0; k < c->textures.size(); ++k) {
@@ -840,8 +893,23 @@ static int sync_scene_state(csg_ctx* c) {
       return c->fail(CSG_ERR_INVALID, "material %u (set %u) references texture %d that was not uploaded",
                      (unsigned)(k % c->n_materials), (unsigned)(k / c->n_materials), t);
   }
-  if (iset_dirty) {   // each instance's material per set, texture descriptors inlined
+  if (box_dirty) {
+    const int rc = build_alpha_boxes(c);
+    if (rc) return rc;
+  }
+  if (iset_dirty || box_dirty) {   // each instance's material per set, texture descriptors inlined
     std::vector<InstSetDev> is((size_t)n_sets * c->n_inst);
+    // an instance's records are trimmed to its triangles' opaque boxes only in sets whose resolved alpha
+    // texture and threshold are those the boxes were built from
+    std::vector<int32_t> inst_mesh(c->n_inst, -1);
+    for (uint32_t i = 0; i < c->n_inst; ++i)
+      for (size_t m = 0; m < c->h_meshes.size(); ++m)
+        if (c->h_meshes[m].tbase == c->h_inst[i].tbase && c->h_meshes[m].material == c->h_inst[i].material &&
+            c->h_abox_tex[m] >= 0) {
+          inst_mesh[i] = (int32_t)m;
+          break;
+        }
+    std::map<std::pair<int, int>, bool> same;
     for (uint32_t set = 0; set < n_sets; ++set)
       for (uint32_t i = 0; i < c->n_inst; ++i) {
         const InstDesc& d = c->h_inst[i];
@@ -858,6 +926,13 @@ static int sync_scene_state(csg_ctx* c) {
         }
         e.label = d.label;
         e.alpha_uv = (m.alpha_test && d.has_uv) ? 1u : 0u;
+        if (c->alpha_trim && e.alpha_uv && e.atex != kNoAlpha && inst_mesh[i] >= 0 &&
+            m.alpha_threshold == c->h_mats[d.material].alpha_threshold) {
+          const std::pair<int, int> key{c->h_abox_tex[inst_mesh[i]], m.texture};
+          auto it = same.find(key);
+          if (it == same.end()) it = same.emplace(key, same_alpha(c, key.first, key.second)).first;
+          e.trim = it->second ? 1u : 0u;
+        }
         is[(size_t)set * c->n_inst + i] = e;
       }
     HIP_TRY(c, c->iset.alloc(std::max<size_t>(is.size(), 1)));
@@ -982,7 +1057,8 @@ static int ensure_work(csg_ctx* c) {
 
 static SceneDev scene_dev(const csg_ctx* c) {
   SceneDev s{};
-  s.tri_pos = c->tri_pos.p; s.tri_uv = c->tri_uv.p; s.inst = c->inst.p;
+  s.tri_pos = c->tri_pos.p; s.tri_uv = c->tri_uv.p; s.tri_abox = reinterpret_cast<const float4*>(c->abox.p);
+  s.inst = c->inst.p;
   s.texd = c->texd.p; s.texels = c->texels.p; s.aquad = c->aquad.p; s.acls = c->acls.p; s.n_inst = c->n_inst;
   s.W = c->cfg.width; s.H = c->cfg.height;
   s.tiles_x = c->tiles_x; s.tiles_y = c->tiles_y; s.n_tiles = c->n_tiles;

@@ -54,7 +54,7 @@ struct InstSetDev {
   uint32_t athr;      // alpha threshold
   int32_t label;      // the instance's label
   uint32_t alpha_uv;  // alpha-tested material on a mesh with uvs (the record carries uv planes)
-  uint32_t pad;
+  uint32_t trim;      // 1: the triangles' opaque boxes (SceneDev::tri_abox) hold for this set's alpha texture
 };
 static_assert(sizeof(InstSetDev) == 32, "InstSetDev layout");
 struct TexDesc { uint32_t offset, width, height, pad; };
@@ -122,6 +122,7 @@ static_assert(sizeof(Slab) == 32, "Slab layout");
 struct SceneDev {
   const float* tri_pos;        // [T][3][3] object space
   const float* tri_uv;         // [T][3][2] (zeros for meshes without uvs)
+  const float4* tri_abox;      // [T] opaque uv box u_lo u_hi v_lo v_hi of alpha-tested triangles (csg_alpha_box.h)
   const InstDesc* inst;        // [I]
   const TexDesc* texd;
   const uint8_t* texels;        // RGBA8, all textures back to back (TexDesc.offset in texels)

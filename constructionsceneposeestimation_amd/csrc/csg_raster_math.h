@@ -296,6 +296,126 @@ __device__ __forceinline__ bool make_rec(const SceneDev& s, const float* su, con
   return true;
 }
 
+// ---------------------------------------------------------------------------
+// Alpha trim: k_setup shrinks the pixel box of an
+// alpha-tested record to the pixels whose (u, v) can fall inside the
+// triangle's opaque uv box (csg_alpha_box.h).  Every dropped pixel centre
+// provably fails alpha_pass as k_raster's fragment() evaluates it, so no output
+// changes.  Only unclipped triangles are trimmed (one record, whose covered
+// pixel centres lie inside the snapped triangle).
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ float rcp_w(float w);
+constexpr float kTrimEps = 0x1p-20f;   // 4x the rounding of any expression bounded below (at most 2^-22 of its magnitude sum)
+#ifndef CSG_TRIM_PASSES
+#define CSG_TRIM_PASSES 2
+#endif
+constexpr int kTrimPasses = CSG_TRIM_PASSES;   // x / y rounds over the four half-planes (A/B: profiles/HISTORY.md)
+
+// The guards.  `v` are the clip-space vertices (W >= near), uv their texture
+// coordinates, U V D the record's planes, T = max(tw, th).  With
+//   X, Y   >= |x|, |y| of every vertex, snapped vertex and covered pixel centre,
+//   S, Sd  = magnitude sums |P0| X + |P1| Y + |P2| of the uv planes (the larger) and of D,
+//   umax   >= |u|, |v| of every covered pixel,
+// it returns true only if
+//   dmin > 0 bounds the real-valued D below at the three snapped vertices, hence
+//     (D is affine, a covered centre is a convex combination of them) at every
+//     covered pixel, where u = U / D is then a convex combination of the vertices'
+//     U / D as well;
+//   (b) the real-valued U / D, V / D at each snapped vertex are within 1 / T
+//     of the vertex's uv, so every covered pixel's real (u, v) lies within one
+//     texel of the true uv triangle;
+//   (a) the (u, v) that fragment() computes and the texel coordinates alpha_pass
+//     derives from them differ from the real values by at most 1/4 texel.
+// `m` bounds twice over the rounding of a half-plane (U - bound * D)(x, y)
+// evaluated in float at any centre of the box, for |bound| <= B.
+__device__ __forceinline__ bool alpha_trim_guard(const Cv3* v, const float* uv, const float* U, const float* V,
+                                                 const float* D, float T, float B, float& m) {
+  float su[3], sv[3], X = 0.0f, Y = 0.0f, umax = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float r = rcp_w(v[k].w);
+    su[k] = v[k].x * r;
+    sv[k] = v[k].y * r;
+    X = fmaxf(X, fabsf(su[k]));
+    Y = fmaxf(Y, fabsf(sv[k]));
+    umax = fmaxf(umax, fmaxf(fabsf(uv[2 * k]), fabsf(uv[2 * k + 1])));
+  }
+  X += 1.0f;
+  Y += 1.0f;
+  umax += 2.0f;
+  const float Sd = (fabsf(D[0]) * X + fabsf(D[1]) * Y) + fabsf(D[2]);
+  const float S = fmaxf((fabsf(U[0]) * X + fabsf(U[1]) * Y) + fabsf(U[2]), (fabsf(V[0]) * X + fabsf(V[1]) * Y) + fabsf(V[2]));
+  // a plane at the snapped vertex (within 1/512 px of su, sv) against its float value at (su, sv)
+  const float dD = kTrimEps * Sd + (fabsf(D[0]) + fabsf(D[1])) * (1.0f / 256.0f);
+  const float dU = kTrimEps * S + fmaxf(fabsf(U[0]) + fabsf(U[1]), fabsf(V[0]) + fabsf(V[1])) * (1.0f / 256.0f);
+  float dmin = INFINITY, res = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float Dk = plane_at(D[0], D[1], D[2], su[k], sv[k]);
+    const float Uk = plane_at(U[0], U[1], U[2], su[k], sv[k]), Vk = plane_at(V[0], V[1], V[2], su[k], sv[k]);
+    dmin = fminf(dmin, Dk);
+    res = fmaxf(res, fmaxf(fabsf(Uk - uv[2 * k] * Dk), fabsf(Vk - uv[2 * k + 1] * Dk)));
+  }
+  dmin -= dD;
+  if (!(dmin >= 0x1p-100f)) return false;
+  if (!(((res + dU) + umax * dD) * T <= dmin)) return false;                                           // (b)
+  if (!(kTrimEps * T * ((S + umax * Sd) + (umax + 1.0f) * dmin) <= 0.25f * dmin)) return false;      // (a)
+  m = kTrimEps * (S + B * Sd);
+  return m < INFINITY;
+}
+
+// Shrink the pixel range [lo, hi] of one axis against the half-plane
+// g(t, o) = (a * t + b * o) + c >= 0 (t: this axis' pixel centre, o in [o0, o1]
+// the other's): a line of pixels goes when g < -m at both of its ends.  g is
+// monotone in t, so the lines that go are a prefix (a > 0) or a suffix (a < 0);
+// the reciprocal only proposes the bound, the line next to it is then evaluated
+// and decides (one retry a line further in, else no change).
+__device__ __forceinline__ void trim_axis(float a, float b, float c, float m, float o0, float o1, int& lo, int& hi) {
+  if (!(a != 0.0f) || lo > hi) return;
+  const float est = -((fmaxf(b * o0, b * o1) + c) + m) * __builtin_amdgcn_rcpf(a);   // g = -m at t = est
+  const float e = fminf(fmaxf(est - 0.5f, (float)lo - 1.0f), (float)hi + 1.0f);
+  auto gone = [&](int p) {
+    const float t = (float)p + 0.5f;
+    return fmaxf((a * t + b * o0) + c, (a * t + b * o1) + c) < -m;
+  };
+  if (a > 0.0f) {
+    int n = max((int)ceilf(e), lo);    // the first line kept
+    if (n > lo && !gone(n - 1)) {
+      --n;
+      if (n > lo && !gone(n - 1)) n = lo;
+    }
+    lo = n;
+  } else {
+    int n = min((int)floorf(e), hi);   // the last line kept
+    if (n < hi && !gone(n + 1)) {
+      ++n;
+      if (n < hi && !gone(n + 1)) n = hi;
+    }
+    hi = n;
+  }
+}
+
+// The record's pixel box against the opaque uv box bx = u_lo u_hi v_lo v_hi
+// (finite).  False: no pixel is left.
+__device__ __forceinline__ bool alpha_trim_box(const float* U, const float* V, const float* D, float4 bx, float m,
+                                               int& px0, int& py0, int& px1, int& py1) {
+  // u >= u_lo, u <= u_hi, v >= v_lo, v <= v_hi, each times D > 0: P - bound * D >= 0 or its negation.
+  // (The coefficients are formed where they are used: twelve of them held across the loop cost k_setup
+  // a wave of occupancy.)
+#pragma nounroll
+  for (int pass = 0; pass < kTrimPasses; ++pass) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float* P = k < 2 ? U : V;
+      const float bd = k == 0 ? bx.x : k == 1 ? bx.y : k == 2 ? bx.z : bx.w, sg = (k & 1) ? -1.0f : 1.0f;
+      const float h0 = sg * (P[0] - bd * D[0]), h1 = sg * (P[1] - bd * D[1]), h2 = sg * (P[2] - bd * D[2]);
+      trim_axis(h0, h1, h2, m, (float)py0 + 0.5f, (float)py1 + 0.5f, px0, px1);
+      trim_axis(h1, h0, h2, m, (float)px0 + 0.5f, (float)px1 + 0.5f, py0, py1);
+    }
+  }
+  return px0 <= px1 && py0 <= py1;
+}
+
 // q / w for q < 2^24, 1 <= w <= 256: float reciprocal estimate (off by at
 // most one), then one exact correction (no integer division sequence)
 __device__ __forceinline__ uint32_t small_div(uint32_t q, uint32_t w) {

@@ -288,7 +288,14 @@ int csg_set_dr_textures(csg_ctx* ctx, uint32_t set_id, const int32_t* texture_pe
  * csg_synchronize.  With host outputs the batch runs as launch chains of an
  * eighth of it (at least 32 frames), each chain's outputs copied to the host
  * on a copy stream while later chains render (CSG_SPLIT_PAGEABLE=0 at
- * csg_create: pageable destinations as one chain). */
+ * csg_create: pageable destinations as one chain).
+ *
+ * Alpha-tested records are trimmed to their triangle's opaque uv box, computed
+ * at upload from the mesh uvs, the authored alpha texture and its threshold
+ * (DESIGN.md section 3, item 6): fewer records, bin entries and fragments, the
+ * same outputs.  CSG_ALPHA_TRIM=0 at csg_create uploads "full" boxes and
+ * renders untrimmed (A/B, tests); csg_get_batch_stats' records and bin_entries
+ * show the difference. */
 int csg_render_batch(csg_ctx* ctx, const csg_frame* frames, uint32_t n_frames, const csg_outputs* out);
 /* Same, enqueued on `stream` (a hipStream_t, NULL = context stream); frames
  * may be a device pointer when frames_on_device = 1.  Returns after enqueue;
