@@ -31,7 +31,7 @@ EXPORTED = (
     "csg_instance_bounds", "csg_copy_files", "csg_host_alloc", "csg_host_free", "csg_size_work",
     "csg_get_work_info", "csg_host_id_bytes", "csg_set_object_frames", "csg_crop_objects", "csg_encode_files",
     "csg_crop_objects_filtered", "csg_crop_amodal", "csg_crop_amodal_geometry", "csg_mask_spans",
-    "csg_keep_instance", "csg_last_instance", "csg_amodal_spans",
+    "csg_keep_instance", "csg_last_instance", "csg_amodal_spans", "csg_sample_object_points",
 )
 
 
@@ -143,6 +143,15 @@ class AmodalSpanJob(C.Structure):
                 ("span_offsets", C.c_void_p), ("amodal_stats", C.c_void_p)]
 
 
+class PointJob(C.Structure):
+    """csg_point_job (csg_sample_object_points)."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n_labels", C.c_uint32), ("per_frame", C.c_uint32),
+                ("samples", C.c_uint32), ("seed", C.c_uint32), ("instance", C.c_void_p), ("info", C.c_void_p),
+                ("depth", C.c_void_p), ("intrinsics", C.c_void_p), ("rgb", C.c_void_p), ("obj_coords", C.c_void_p),
+                ("frame_keys", C.c_void_p), ("pt_count", C.c_void_p), ("pt_choose", C.c_void_p),
+                ("pt_xyz", C.c_void_p), ("pt_rgb", C.c_void_p), ("pt_coords", C.c_void_p)]
+
+
 class EncodeJob(C.Structure):
     """csg_encode_job (csg_encode_files)."""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n_frames", C.c_uint32), ("file_kinds", C.c_uint32),
@@ -224,6 +233,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     lib.csg_encode_files.argtypes = [vp, C.POINTER(EncodeJob)]
     lib.csg_mask_spans.argtypes = [vp, C.POINTER(SpanJob), u32, vp]
     lib.csg_amodal_spans.argtypes = [vp, C.POINTER(AmodalSpanJob), u32, vp]
+    lib.csg_sample_object_points.argtypes = [vp, C.POINTER(PointJob), u32, vp]
     lib.csg_keep_instance.argtypes = [vp, i32]
     lib.csg_last_instance.argtypes = [vp, C.POINTER(vp), C.POINTER(u32)]
     if lib.csg_abi_version() != ABI_VERSION:

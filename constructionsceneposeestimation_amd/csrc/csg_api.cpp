@@ -27,6 +27,7 @@
 #include "csg_crops.h"
 #include "csg_encode.h"
 #include "csg_kernels.h"
+#include "csg_points.h"
 #include "csg_spans.h"
 #include "csg_widen.h"
 
@@ -271,6 +272,12 @@ struct csg_ctx {
   hipEvent_t ms_done = nullptr;
   hipStream_t ms_stream = nullptr;
   bool ms_busy = false;
+  // Object points (csg_sample_object_points): the pass's own scratch, the pixel counts [n][L][chunks] and
+  // the totals [n][L] behind them, grown to the job; op_done orders passes on different streams as ms_done does.
+  DevBuf<uint32_t> op_cnt;
+  hipEvent_t op_done = nullptr;
+  hipStream_t op_stream = nullptr;
+  bool op_busy = false;
   // csg_keep_instance / csg_last_instance: host-output batches keep their ids on the device
   bool keep_ids = false;
   const int32_t* last_inst = nullptr;
@@ -453,6 +460,9 @@ void csg_destroy(csg_ctx* c) {
   if (c->ms_busy) (void)hipEventSynchronize(c->ms_done);   // a span pass on a stream of the caller's
   c->ms_cnt.release();
   if (c->ms_done) (void)hipEventDestroy(c->ms_done);
+  if (c->op_busy) (void)hipEventSynchronize(c->op_done);   // a point pass on a stream of the caller's
+  c->op_cnt.release();
+  if (c->op_done) (void)hipEventDestroy(c->op_done);
   for (auto& e : c->ring)
     if (e) (void)hipEventDestroy(e);
   if (c->h_ids_n) (void)hipHostFree(c->h_ids_n);
@@ -2191,6 +2201,80 @@ int csg_mask_spans(csg_ctx* c, const csg_span_job* job, uint32_t n_frames, void*
   HIP_TRY(c, hipEventRecord(c->ms_done, st));
   c->ms_stream = st;
   c->ms_busy = true;
+  return CSG_OK;
+}
+
+// Object points: a stand-alone pass over device arrays (no scene state, no work buffers); validates the
+// job, grows the pass's own count scratch and enqueues count, scan and emit.
+int csg_sample_object_points(csg_ctx* c, const csg_point_job* job, uint32_t n_frames, void* stream) {
+  static_assert(kPointMaxLabels == CSG_SPAN_MAX_LABELS, "label limit");
+  if (!c) return CSG_ERR_INVALID;
+  if (!job) return c->fail(CSG_ERR_INVALID, "sample_object_points: null job");
+  if (n_frames == 0) return c->fail(CSG_ERR_INVALID, "sample_object_points: no frames");
+  if (job->width < 1 || job->width > 8192 || job->height < 1 || job->height > 8192)
+    return c->fail(CSG_ERR_INVALID, "sample_object_points: frame %u x %u outside 1..8192", job->width, job->height);
+  if (job->n_labels == 0) return c->fail(CSG_ERR_INVALID, "sample_object_points: n_labels must be at least 1");
+  if (job->n_labels > CSG_SPAN_MAX_LABELS)
+    return c->fail(CSG_ERR_LIMIT, "sample_object_points: n_labels %u above CSG_SPAN_MAX_LABELS %u", job->n_labels,
+                   CSG_SPAN_MAX_LABELS);
+  if (job->per_frame < 1 || job->per_frame > 64)
+    return c->fail(CSG_ERR_INVALID, "sample_object_points: per_frame %u outside 1..64", job->per_frame);
+  if (job->samples < 16 || job->samples > 16384 || (job->samples & 3u))
+    return c->fail(CSG_ERR_INVALID, "sample_object_points: samples %u is not a multiple of 4 in 16..16384",
+                   job->samples);
+  if (!job->instance || !job->info)
+    return c->fail(CSG_ERR_INVALID, "sample_object_points: instance and info are always needed");
+  if (!job->pt_count && !job->pt_choose && !job->pt_xyz && !job->pt_rgb && !job->pt_coords)
+    return c->fail(CSG_ERR_INVALID, "sample_object_points: no output");
+  if (job->pt_xyz && (!job->depth || !job->intrinsics))
+    return c->fail(CSG_ERR_INVALID, "sample_object_points: pt_xyz needs depth and intrinsics");
+  if (job->pt_rgb && !job->rgb) return c->fail(CSG_ERR_INVALID, "sample_object_points: pt_rgb needs rgb");
+  if (job->pt_coords && !job->obj_coords)
+    return c->fail(CSG_ERR_INVALID, "sample_object_points: pt_coords needs obj_coords");
+  if ((((uintptr_t)job->instance | (uintptr_t)job->info | (uintptr_t)job->depth | (uintptr_t)job->intrinsics |
+        (uintptr_t)job->frame_keys | (uintptr_t)job->pt_count | (uintptr_t)job->pt_choose | (uintptr_t)job->pt_xyz |
+        (uintptr_t)job->pt_rgb) & 3u) || (((uintptr_t)job->obj_coords | (uintptr_t)job->pt_coords) & 1u))
+    return c->fail(CSG_ERR_INVALID, "sample_object_points: obj_coords and pt_coords must be 2-byte aligned, every "
+                                    "other pointer but rgb 4-byte");
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+  PointArgs a{};
+  a.W = job->width;
+  a.H = job->height;
+  a.P = job->width * job->height;
+  a.L = job->n_labels;
+  a.K = job->per_frame;
+  a.N = job->samples;
+  a.CH = (a.P + kPointChunk - 1u) / kPointChunk;
+  a.seed = job->seed;
+  a.instance = job->instance;
+  a.info = reinterpret_cast<const CropSlot*>(job->info);
+  a.depth = job->pt_xyz ? job->depth : nullptr;   // a source nobody asked for is never read
+  a.intrinsics = job->pt_xyz ? job->intrinsics : nullptr;
+  a.rgb = job->pt_rgb ? job->rgb : nullptr;
+  a.obj_coords = job->pt_coords ? job->obj_coords : nullptr;
+  a.frame_keys = job->frame_keys;
+  a.pt_count = job->pt_count;
+  a.pt_choose = job->pt_choose;
+  a.pt_xyz = job->pt_xyz;
+  a.pt_rgb = job->pt_rgb;
+  a.pt_coords = job->pt_coords;
+  const size_t n_tot = (size_t)n_frames * a.L, n_cnt = n_tot * a.CH;
+  if (!c->op_done) HIP_TRY(c, hipEventCreateWithFlags(&c->op_done, hipEventDisableTiming));
+  if (c->op_busy) {
+    if (c->op_cnt.n < n_cnt + n_tot) HIP_TRY(c, hipEventSynchronize(c->op_done));   // the last pass still reads what is freed below
+    else if (c->op_stream != st) HIP_TRY(c, hipStreamWaitEvent(st, c->op_done, 0));   // ... or what this pass overwrites
+  }
+  HIP_TRY(c, c->op_cnt.alloc(n_cnt + n_tot));
+  a.cnt = c->op_cnt.p;
+  a.total = c->op_cnt.p + n_cnt;
+  launch_pts_count(a, n_frames, st);
+  launch_pts_scan(a, n_frames, st);
+  launch_pts_emit(a, n_frames, st);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipEventRecord(c->op_done, st));
+  c->op_stream = st;
+  c->op_busy = true;
   return CSG_OK;
 }
 

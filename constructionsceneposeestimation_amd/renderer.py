@@ -20,6 +20,7 @@ from ._lib import CsgError
 from .camera_math import Intrinsics
 from .crops import CROP_INFO_DTYPE, DYNAMIC_KINDS, crop_intrinsics, eligible_labels
 from .labels import object_unit_transforms
+from .object_points import intrinsics_rows
 from .packing import PackedScene, light_constants, pack_scene
 from .scene.model import Scene
 
@@ -460,7 +461,7 @@ class Renderer:
     def render_crops(self, frames: np.ndarray, size: int = 128, per_frame: int = 8, min_pixels: int = 64,
                      pad: float = 1.5, kinds: Sequence[str] = DYNAMIC_KINDS,
                      want: Iterable[str] = ("rgb", "mask", "coords"), object_frames=None,
-                     rgb_filter: str = "bilinear") -> Dict[str, np.ndarray]:
+                     rgb_filter: str = "bilinear", samples: int = 1024, seed: int = 0) -> Dict[str, np.ndarray]:
         """Render ``frames`` and deliver only their object crops to the host:
         chunks of ``max_frames`` are rendered into device tensors (torch),
         cropped on the same stream, and the crops and their ``info`` copied to
@@ -471,7 +472,14 @@ class Renderer:
         "amodal_coords" (``crop_amodal_depth`` float32 and
         ``crop_amodal_coords`` uint16 of :meth:`crop_amodal_geometry`, one
         geometry pass per chunk, which also makes the amodal mask when that is
-        wanted with them; the coordinates need the tables "coords" needs);
+        wanted with them; the coordinates need the tables "coords" needs) and
+        "points" (the point samples of :meth:`sample_points` for the planned
+        slots: ``pt_count`` (n, K) uint32, ``pt_choose`` (n, K, N) uint32,
+        ``pt_xyz`` (n, K, N, 3) float32, ``pt_rgb`` (n, K, N, 3) uint8 and
+        ``pt_coords`` (n, K, N, 3) uint16 with N = ``samples``, drawn under
+        ``seed`` with the frames' own ids as keys, so a frame's samples do not
+        depend on its place in ``frames``; ``pt_coords`` needs the tables
+        "coords" needs);
         ``kinds`` the object
         kinds that may be cropped (:func:`crops.eligible_labels`).  Returns
         ``crop_rgb`` / ``crop_mask`` / ``crop_coords`` / ``crop_depth`` (those
@@ -491,9 +499,10 @@ class Renderer:
         frames = np.ascontiguousarray(frames, FRAME_DTYPE)
         n, S, K, H, W = frames.shape[0], int(size), int(per_frame), self.height, self.width
         want = set(want)
-        if not want or want - {"rgb", "mask", "coords", "depth", "amodal", "amodal_depth", "amodal_coords"}:
+        if not want or want - {"rgb", "mask", "coords", "depth", "amodal", "amodal_depth", "amodal_coords", "points"}:
             raise CsgError(f"render_crops: want {sorted(want)} must be a non-empty subset of rgb, mask, coords, depth, "
-                           "amodal, amodal_depth, amodal_coords")
+                           "amodal, amodal_depth, amodal_coords, points")
+        pts, N = "points" in want, int(samples)
         for set_id, of in (object_frames or {}).items():
             self.set_object_frames(int(set_id), of)
         dev = torch.device("cuda", self.device)
@@ -505,9 +514,10 @@ class Renderer:
         def ptr(t):
             return t.data_ptr() if t is not None else 0
 
-        src = {"rgb": dbuf("rgb" in want, (m, H, W, 3), torch.uint8), "instance": dbuf(True, (m, H, W), torch.int32),
-               "depth": dbuf("depth" in want, (m, H, W), torch.float32),
-               "obj_coords": dbuf("coords" in want, (m, H, W, 3), torch.int16),
+        src = {"rgb": dbuf(pts or "rgb" in want, (m, H, W, 3), torch.uint8),
+               "instance": dbuf(True, (m, H, W), torch.int32),
+               "depth": dbuf(pts or "depth" in want, (m, H, W), torch.float32),
+               "obj_coords": dbuf(pts or "coords" in want, (m, H, W, 3), torch.int16),
                "stats": dbuf(True, (m, self.n_labels, 5), torch.int32)}
         shapes = {"crop_rgb": ("rgb", (K, S, S, 3), torch.uint8), "crop_mask": ("mask", (K, S, S), torch.uint8),
                   "crop_coords": ("coords", (K, S, S, 3), torch.int16), "crop_depth": ("depth", (K, S, S), torch.float32),
@@ -515,6 +525,12 @@ class Renderer:
                   "crop_amodal_depth": ("amodal_depth", (K, S, S), torch.float32),
                   "crop_amodal_coords": ("amodal_coords", (K, S, S, 3), torch.int16),
                   "info": (None, (K, CROP_INFO_DTYPE.itemsize), torch.uint8)}
+        if pts:
+            shapes.update({"pt_count": ("points", (K,), torch.int32), "pt_choose": ("points", (K, N), torch.int32),
+                           "pt_xyz": ("points", (K, N, 3), torch.float32), "pt_rgb": ("points", (K, N, 3), torch.uint8),
+                           "pt_coords": ("points", (K, N, 3), torch.int16)})
+            intr = torch.from_numpy(intrinsics_rows(frames)).to(dev)
+            keys = torch.from_numpy(np.ascontiguousarray(frames["frame_id"]).view(np.int32)).to(dev)
         d_out = {k: dbuf(w is None or w in want, (m,) + sh, dt) for k, (w, sh, dt) in shapes.items()}
         h_out = {k: torch.empty((n,) + sh, dtype=dt, pin_memory=True)
                  for k, (w, sh, dt) in shapes.items() if d_out[k] is not None}
@@ -542,20 +558,65 @@ class Renderer:
                 elif "amodal" in want:
                     self.crop_amodal(frames[s:e], size=S, per_frame=K, info=ptr(d_out["info"]),
                                      crop_amodal=ptr(d_out["crop_amodal"]), stream=stream.cuda_stream)
+                if pts:
+                    self.sample_points(e - s, samples=N, per_frame=K, seed=seed, instance=ptr(src["instance"]),
+                                       info=ptr(d_out["info"]), depth=ptr(src["depth"]),
+                                       intrinsics=intr.data_ptr() + 16 * s, rgb=ptr(src["rgb"]),
+                                       obj_coords=ptr(src["obj_coords"]), frame_keys=keys.data_ptr() + 4 * s,
+                                       pt_count=ptr(d_out["pt_count"]), pt_choose=ptr(d_out["pt_choose"]),
+                                       pt_xyz=ptr(d_out["pt_xyz"]), pt_rgb=ptr(d_out["pt_rgb"]),
+                                       pt_coords=ptr(d_out["pt_coords"]), stream=stream.cuda_stream)
                 for k, h in h_out.items():
                     h[s:e].copy_(d_out[k][:e - s], non_blocking=True)
         stream.synchronize()
         self.synchronize()
         out = {k: h.numpy() for k, h in h_out.items()}
-        for k in ("crop_coords", "crop_amodal_coords"):
+        for k in ("crop_coords", "crop_amodal_coords", "pt_coords"):
             if k in out:
                 out[k] = out[k].view(np.uint16)
+        for k in ("pt_count", "pt_choose"):
+            if k in out:
+                out[k] = out[k].view(np.uint32)
         info = out["info"].view(CROP_INFO_DTYPE).reshape(n, K)
         # (the kernel numbers frames within a chunk: here they index `frames`)
         info["frame"] = np.where(info["label"] >= 0, np.arange(n, dtype=np.uint32)[:, None], np.uint32(0))
         out["info"] = info
         out["intrinsics"] = crop_intrinsics(self.intr, info, S)
         return out
+
+    # -- per-object point samples ---------------------------------------------------
+    def sample_points(self, n: int, *, samples: int, per_frame: int, instance: int, info: int, seed: int = 0,
+                      depth: int = 0, intrinsics: int = 0, rgb: int = 0, obj_coords: int = 0, frame_keys: int = 0,
+                      pt_count: int = 0, pt_choose: int = 0, pt_xyz: int = 0, pt_rgb: int = 0, pt_coords: int = 0,
+                      n_labels: Optional[int] = None, height: Optional[int] = None, width: Optional[int] = None,
+                      stream: int = 0) -> None:
+        """Enqueue the point samples of ``n`` frames (csg_sample_object_points;
+        raw device pointers, like :meth:`mask_spans`): for each slot of
+        ``info`` (n, K) of ``crops.CROP_INFO_DTYPE`` (only ``label`` is read:
+        what :meth:`crop_objects` planned, or the caller's own) ``samples`` = N
+        pixels of the visible mask of the slot's label in ``instance``
+        (n, H, W) int32, into ``pt_count`` (n, K) uint32 (the label's pixels
+        M), ``pt_choose`` (n, K, N) uint32 (row-major indices ``y * W + x``),
+        ``pt_xyz`` (n, K, N, 3) float32 (OpenCV camera frame, from ``depth``
+        (n, H, W) float32 and ``intrinsics`` (n, 4) float32 ``fx, fy, cx, cy``:
+        :func:`object_points.intrinsics_rows`), ``pt_rgb`` (n, K, N, 3) uint8
+        (from ``rgb``) and ``pt_coords`` (n, K, N, 3) uint16 (from
+        ``obj_coords``).  Any output may be 0, not all.  With M <= N every
+        pixel is used and they repeat in order (``np.pad(..., 'wrap')``); with
+        M > N one pixel per stratum of the label's row-major pixel list is
+        drawn under ``seed``, the frame's key (``frame_keys`` (n,) uint32; 0:
+        the frame's index) and the label, so samples ascend in pixel order (a
+        CPU loader's random choice is unordered).  A slot without pixels gets
+        0, 0xFFFFFFFF, NaN, 0 and 0.  ``n_labels`` defaults to the scene's,
+        ``height`` / ``width`` to the renderer's.  On the stream of the render
+        and the crops no synchronisation is needed in between."""
+        job = _lib.PointJob(self.width if width is None else int(width), self.height if height is None else int(height),
+                            self.n_labels if n_labels is None else int(n_labels), int(per_frame), int(samples),
+                            int(seed) & 0xFFFFFFFF, instance or None, info or None, depth or None, intrinsics or None,
+                            rgb or None, obj_coords or None, frame_keys or None, pt_count or None, pt_choose or None,
+                            pt_xyz or None, pt_rgb or None, pt_coords or None)
+        self._check(self.lib.csg_sample_object_points(self.ctx, C.byref(job), int(n), stream or None),
+                    "sample_points")
 
     # -- per-object run-length masks ----------------------------------------------
     def mask_spans(self, n: int, *, instance: int, spans: int, span_offsets: int, capacity: int,

@@ -64,6 +64,9 @@
  *                               the visible ids
  *   csg_amodal_spans .......... (new) the same spans of every object's amodal mask over
  *                               the whole frame, with its amodal box and pixel count
+ *   csg_sample_object_points .. (new) N pixels of each object's visible mask with their
+ *                               image indices, camera-frame points, colours and object
+ *                               coordinates: the input of the point-based pose networks
  *   csg_last_error / csg_destroy
  *
  * Threading: several contexts may share a device (each has its own stream
@@ -790,6 +793,101 @@ typedef struct {
   uint32_t* amodal_stats;     /* DEVICE [n][L][5] = pixels, minx, miny, maxx, maxy, 4-B aligned, or NULL */
 } csg_amodal_span_job;
 int csg_amodal_spans(csg_ctx* ctx, const csg_amodal_span_job* job, uint32_t n_frames, void* stream);
+
+/* Fixed-size per-object point samples: for each slot of `info`, N pixels drawn
+ * from the visible mask of the slot's label, as their indices in the image
+ * (what the public loaders of DenseFusion, PVN3D or FFB6D call `choose`), their
+ * points in the camera's frame, their colours and their object coordinates --
+ * some 30 bytes per sample instead of the dense arrays.  A stand-alone pass on
+ * device memory only, like csg_mask_spans: it needs no scene and no earlier
+ * render, and the frame size is the job's own.  L = n_labels, K = per_frame,
+ * N = samples, P = H * W.
+ *
+ * Slot liveness.  Slot [f][k] is live iff 0 <= info[f][k].label < L (the label
+ * rule of the crops); its window fields are ignored, and `info` is only read.
+ * Two slots may name the same label: each gets the full result.
+ *
+ * Rank.  Let l be a live slot's label.  The pixels of frame f whose id equals l
+ * are ranked 0 .. M - 1 in row-major order p = y * W + x, the order of
+ * numpy.flatnonzero(instance[f] == l).  pt_count[f][k] = M.
+ *
+ * Which rank sample s = 0 .. N - 1 takes:
+ *   M == 0, or the slot is not live: the slot is empty -- pt_count 0, pt_choose
+ *     0xFFFFFFFF, pt_xyz NaN (bits 0x7FC00000), pt_rgb 0, pt_coords 0.
+ *   1 <= M <= N: rank s mod M.  Every pixel is used, then they repeat in order
+ *     (numpy.pad(..., 'wrap')).
+ *   M > N: stratified, one sample per stratum, in unsigned 64-bit integers:
+ *     lo_s = (s * M) / N, w_s = lo_{s+1} - lo_s (>= 1),
+ *     r_s = lo_s + (uint32)(((uint64)h_s * w_s) >> 32), with
+ *     fmix32(x): x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35;
+ *                x ^= x >> 16 (uint32),
+ *     key_f = frame_keys[f], or f when frame_keys is NULL,
+ *     base = fmix32(fmix32(seed ^ key_f) ^ (uint32)l),
+ *     h_s = fmix32(base ^ (s * 0x9E3779B9u)).
+ *     The samples are therefore in ascending pixel order (the CPU loaders' random
+ *     choice is unordered; point-set networks do not depend on the order).
+ *
+ * Values of a sample at pixel (px, py), p = py * W + px:
+ *   pt_choose  p.
+ *   pt_rgb, pt_coords  rgb[f][py][px] and obj_coords[f][py][px], bit for bit.
+ *   pt_xyz     with d = depth[f][py][px] and fx, fy, cx, cy = intrinsics[f], the
+ *              point in the OpenCV camera frame (x right, y down, z forward):
+ *                X = ((((float)px + 0.5f) - cx) * d) / fx
+ *                Y = ((((float)py + 0.5f) - cy) * d) / fy
+ *                Z = d
+ *              float32, each operation rounded once in the written order ('/' is
+ *              the correctly rounded division): the camera point of csg_outputs
+ *              .points before its rotation to the world, with y and z not negated.
+ *              No value of depth or intrinsics is rejected; infinities and NaN
+ *              propagate.  An X or Y that is NaN is stored as 0x7FC00000 (the
+ *              sign and payload of a NaN an operation makes are the machine's);
+ *              Z is d's bits.
+ *
+ * The output is a pure function of the inputs: no atomic decides a position,
+ * nothing depends on scheduling, and a frame's result depends on its place in
+ * the batch only through its key (with frame_keys, the same image under the same
+ * key gives the same samples at any position).  Every element of every requested
+ * output is written.  No id, label or source value yields an address outside
+ * the arrays described: ids index a table only when 0 <= id < L, and lanes past
+ * the image load nothing.
+ *
+ * Enqueues on `stream` (NULL = the context's stream) and returns; behind the
+ * render that wrote the sources and the csg_crop_objects that planned `info` on
+ * the same stream it needs no synchronisation.  csg_synchronize waits for it
+ * under the rule for the crops.  The pass has scratch of its own (4 bytes per
+ * frame, label and 4096 pixels, and 4 per frame and label), grown to the job; an
+ * event orders passes on different streams; it never touches the render's work
+ * buffers.
+ *
+ * CSG_ERR_INVALID, nothing enqueued or written: job NULL; n_frames == 0; width
+ * or height outside 1..8192; n_labels == 0; per_frame outside 1..64; samples not
+ * a multiple of 4 in 16..16384; instance or info NULL; pt_xyz without depth or
+ * intrinsics, pt_rgb without rgb, pt_coords without obj_coords; no output at
+ * all; a pointer that is not aligned to its element (4 bytes for instance, info,
+ * depth, intrinsics, frame_keys, pt_count, pt_choose, pt_xyz and pt_rgb; 2 for
+ * obj_coords and pt_coords).  CSG_ERR_LIMIT: n_labels above CSG_SPAN_MAX_LABELS. */
+typedef struct {
+  uint32_t width, height;      /* of the frames: 1..8192 each */
+  uint32_t n_labels;           /* L: 1..CSG_SPAN_MAX_LABELS */
+  uint32_t per_frame;          /* K: slots per frame, 1..64 */
+  uint32_t samples;            /* N: samples per slot, a multiple of 4, 16..16384 */
+  uint32_t seed;
+  /* sources, device memory */
+  const int32_t*  instance;    /* [n][H][W], always */
+  const csg_crop_info* info;   /* [n][K], always; read only, only `label` is used */
+  const float*    depth;       /* [n][H][W], iff pt_xyz */
+  const float*    intrinsics;  /* [n][4] = fx, fy, cx, cy, iff pt_xyz */
+  const uint8_t*  rgb;         /* [n][H][W][3], iff pt_rgb */
+  const uint16_t* obj_coords;  /* [n][H][W][3], iff pt_coords */
+  const uint32_t* frame_keys;  /* [n], or NULL: the key of frame f is f */
+  /* outputs, device memory; any may be NULL, not all */
+  uint32_t* pt_count;          /* [n][K]: M, the pixels of the slot's label */
+  uint32_t* pt_choose;         /* [n][K][N] */
+  float*    pt_xyz;            /* [n][K][N][3] */
+  uint8_t*  pt_rgb;            /* [n][K][N][3], 4-B aligned */
+  uint16_t* pt_coords;         /* [n][K][N][3] */
+} csg_point_job;
+int csg_sample_object_points(csg_ctx* ctx, const csg_point_job* job, uint32_t n_frames, void* stream);
 
 /* Stand-alone 3D->2D projection (host buffers): uv [n][2], vis [n] without a
  * depth test (1 = in front and inside the image, 0 otherwise). */

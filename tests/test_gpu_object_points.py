@@ -1,0 +1,312 @@
+"""csg_sample_object_points on the GPU: every output is bit-exact (NaN bit
+patterns included) against the restatement of tests/test_object_points.py --
+synthetic id images with random sources (every shape, pattern, count, slot
+and source of the definition's corner cases), repeatability, subsets of
+outputs, frame keys, every argument check, rendered frames behind a render and
+the crops' plan on one stream against the CPU oracle's arrays, and
+``render_crops(want=(..., "points"))``.  Outputs are prefilled with 7 and
+followed by a guard that must stay untouched."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from tests.test_crop_amodal import FIDS3, H3, K3, MINPX3, PAD3, S3, W3, c3_reference
+from tests.test_object_crops import INFO_DTYPE
+from tests.test_object_points import (M32, NAN_BITS, SHAPES, c3_sources, patterns, random_sources, restate_points,
+                                      slot_labels)
+
+pytestmark = pytest.mark.gpu
+FILL = 0x07
+GUARD = 4096         # bytes behind every output that must stay untouched
+NAMES = ("pt_count", "pt_choose", "pt_xyz", "pt_rgb", "pt_coords")
+DTYPE = {"pt_count": np.uint32, "pt_choose": np.uint32, "pt_xyz": np.float32, "pt_rgb": np.uint8,
+         "pt_coords": np.uint16}
+SOURCE_OF = {"pt_xyz": ("depth", "intrinsics"), "pt_rgb": ("rgb",), "pt_coords": ("obj_coords",)}
+
+
+def _shape(name, n, K, N):
+    return (n, K) if name == "pt_count" else (n, K, N) if name == "pt_choose" else (n, K, N, 3)
+
+
+@pytest.fixture(scope="module")
+def ctx(cone):
+    """One context for every shape of the module (its own size is irrelevant)."""
+    from constructionsceneposeestimation_amd.renderer import Renderer
+    with Renderer(cone, 64, 64, max_frames=1) as r:
+        yield r
+
+
+def _dev(a, lead=0):
+    """The bytes of ``a`` on the device behind ``lead`` spare bytes -> (tensor, pointer to the data)."""
+    import torch
+    raw = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+    t = torch.zeros(lead + raw.size, dtype=torch.uint8, device=torch.device("cuda", 0))
+    t[lead:] = torch.from_numpy(raw.copy()).to(t.device)
+    return t, t.data_ptr() + lead
+
+
+def _info(labels):
+    info = np.zeros(labels.shape, INFO_DTYPE)
+    info["label"] = labels
+    info["x0"], info["y0"], info["side"] = np.inf, -1e30, np.nan      # the window fields are ignored
+    return info
+
+
+def _out_buffers(names, n, K, N):
+    import torch
+    size = {k: int(np.prod(_shape(k, n, K, N))) * np.dtype(DTYPE[k]).itemsize for k in names}
+    return {k: torch.full((size[k] + GUARD,), FILL, dtype=torch.uint8, device=torch.device("cuda", 0)) for k in names}
+
+
+def _to_host(bufs, n, K, N, what):
+    out = {}
+    for k, t in bufs.items():
+        raw = t.cpu().numpy()
+        assert (raw[-GUARD:] == FILL).all(), f"{what}: the guard behind {k} was written"
+        out[k] = raw[:-GUARD].view(DTYPE[k]).reshape(_shape(k, n, K, N))
+    return out
+
+
+def _run(r, ids, labels, L, N, seed=0, keys=None, src=None, names=NAMES, stream=None, lead=0, what=""):
+    """The pass on ``ids`` (n, H, W) with slot labels (n, K) -> the outputs in ``names`` on the host."""
+    n, H, W = ids.shape
+    K = labels.shape[1]
+    src = src or {}
+    keep = {"instance": _dev(ids.astype(np.int32), lead), "info": _dev(_info(labels))}
+    for k in ("depth", "intrinsics", "rgb", "obj_coords"):
+        if k in src:
+            keep[k] = _dev(src[k])
+    if keys is not None:
+        keep["frame_keys"] = _dev(np.asarray(keys, np.uint32))
+    bufs = _out_buffers(names, n, K, N)
+    r.sample_points(n, samples=N, per_frame=K, seed=seed, n_labels=L, height=H, width=W,
+                    stream=stream.cuda_stream if stream is not None else 0,
+                    **{k: p for k, (_, p) in keep.items()}, **{k: t.data_ptr() for k, t in bufs.items()})
+    if stream is not None:
+        stream.synchronize()
+    r.synchronize()
+    return _to_host(bufs, n, K, N, what)
+
+
+def _bits(a):
+    return a.view(np.uint32) if a.dtype == np.float32 else a
+
+
+def _check(got, exp, what):
+    for k, g in got.items():
+        e = exp[k]
+        assert g.dtype == e.dtype and g.shape == e.shape, f"{what}: {k}"
+        bad = np.argwhere(_bits(g) != _bits(e))
+        assert len(bad) == 0, (f"{what}: {k}: {len(bad)} values differ, first at {bad[:4].tolist()}: "
+                               f"{_bits(g)[tuple(bad[0])]} != {_bits(e)[tuple(bad[0])]}")
+
+
+@pytest.mark.parametrize("H,W", SHAPES)
+@pytest.mark.parametrize("N", [16, 1024])
+@pytest.mark.parametrize("K", [1, 64])
+@pytest.mark.parametrize("L", [1, 256])
+def test_synthetic(ctx, H, W, N, K, L):
+    pats = patterns(H, W, L, N)
+    names = list(pats)
+    names += names[:-len(names) % 3]                                   # whole batches of n = 3 different frames
+    rng = np.random.default_rng(H + 3 * W + N + K + L)
+    seen = set()
+    for b in range(0, len(names), 3):
+        batch = names[b:b + 3]
+        ids = np.stack([pats[k][0] for k in batch])
+        labels = np.stack([slot_labels(K, L, pats[k][1], rng) for k in batch])
+        src = random_sources(3, H, W, rng)
+        keys = None if b % 2 == 0 else rng.integers(0, 2 ** 32, 3, dtype=np.uint64).astype(np.uint32)
+        exp = restate_points(ids, labels, L, N, seed=b + 1, keys=keys, **src)
+        got = _run(ctx, ids, labels, L, N, seed=b + 1, keys=keys, src=src, what=str(batch))
+        _check(got, exp, f"{batch}")
+        seen |= {"empty" if m == 0 else "wrap" if m <= N else "strata" for m in exp["pt_count"].reshape(-1).tolist()}
+    assert "empty" in seen and "wrap" in seen and (("strata" in seen) == (H * W > N))
+
+
+def test_repeatable_on_any_stream_any_subset_and_any_alignment(ctx):
+    import torch
+    H, W, L, N, K = 130, 517, 256, 16, 64
+    pats = patterns(H, W, L, N)
+    rng = np.random.default_rng(4)
+    batch = ["random", "checkerboard", f"count_{2 * N - 1}"]
+    ids = np.stack([pats[k][0] for k in batch])
+    labels = np.stack([slot_labels(K, L, pats[k][1], rng) for k in batch])
+    src = random_sources(3, H, W, rng)
+    exp = restate_points(ids, labels, L, N, seed=9, **src)
+    assert (exp["pt_count"] > N).sum() >= 6
+    first = _run(ctx, ids, labels, L, N, seed=9, src=src)
+    _check(first, exp, "first")
+    _check(_run(ctx, ids, labels, L, N, seed=9, src=src), first, "the same job again")
+    side = torch.cuda.Stream(torch.device("cuda", 0))
+    _check(_run(ctx, ids, labels, L, N, seed=9, src=src, stream=side), first, "on a second stream")
+    _check(_run(ctx, ids, labels, L, N, seed=9, src=src), first, "back on the context's stream")
+    for names in [(k,) for k in NAMES] + [("pt_choose", "pt_rgb"), ("pt_count", "pt_xyz", "pt_coords")]:
+        need = {s: src[s] for k in names for s in SOURCE_OF.get(k, ())}          # only the sources those outputs read
+        got = _run(ctx, ids, labels, L, N, seed=9, src=need, names=names)
+        assert set(got) == set(names)
+        _check(got, first, f"only {names}")
+    # ids that 16-byte loads could take (H * W is a multiple of 4) behind a pointer that does not allow them
+    H, W = 9, 200
+    pats = patterns(H, W, L, N)
+    ids = np.stack([pats[k][0] for k in ("random", "one_label", "run_of_64")])
+    labels = np.stack([slot_labels(K, L, pats[k][1], rng) for k in ("random", "one_label", "run_of_64")])
+    exp = restate_points(ids, labels, L, N, seed=2)
+    for lead in (0, 4, 8):
+        _check(_run(ctx, ids, labels, L, N, seed=2, names=("pt_count", "pt_choose"), lead=lead), exp, f"lead {lead}")
+
+
+def test_frame_keys(ctx):
+    H, W, L, N, K = 67, 131, 256, 16, 64
+    pats = patterns(H, W, L, N)
+    rng = np.random.default_rng(8)
+    img, focus = pats[f"count_{N - 1}"]                               # most labels hold some 9 pixels ...
+    img = img.copy()
+    img[:30], img[30, :100], img[31, :40], img[32, :24] = 0, 1, 2, 3   # ... and these more than N
+    ids = np.stack([img, pats["checkerboard"][0], img])
+    labels = np.stack([slot_labels(K, L, focus, rng)] * 3)
+    src = random_sources(3, H, W, rng)
+    src = {k: v[[0, 1, 0]] for k, v in src.items()}                    # frames 0 and 2 are the same image
+    keys = np.array([0xDEADBEEF, 7, 0xDEADBEEF], np.uint32)
+    got = _run(ctx, ids, labels, L, N, seed=1, keys=keys, src=src)
+    _check(got, restate_points(ids, labels, L, N, seed=1, keys=keys, **src), "keys")
+    for k, v in got.items():
+        assert np.array_equal(_bits(v)[0], _bits(v)[2]), k             # the same key: the same samples
+    plain = _run(ctx, ids, labels, L, N, seed=1, src=src)
+    _check(plain, restate_points(ids, labels, L, N, seed=1, **src), "NULL keys")
+    M = plain["pt_count"][0]
+    assert (M > N).sum() >= 4 and ((M > 0) & (M <= N)).sum() >= 3
+    for k in range(K):                                                  # the key is the position: another draw
+        assert np.array_equal(plain["pt_choose"][0, k], plain["pt_choose"][2, k]) == (M[k] <= N), (k, M[k])
+
+
+def test_argument_checks(ctx):
+    import torch
+    from constructionsceneposeestimation_amd import _lib
+    H, W, L, N, K = 5, 3, 2, 16, 2
+    ids = np.zeros((1, H, W), np.int32)
+    labels = np.array([[0, 1]], np.int32)
+    src = random_sources(1, H, W, np.random.default_rng(0))
+    keep = {"instance": _dev(ids), "info": _dev(_info(labels)), "frame_keys": _dev(np.zeros(1, np.uint32))}
+    keep.update({k: _dev(v) for k, v in src.items()})
+    bufs = _out_buffers(NAMES, 1, K, N)
+    ok = dict(width=W, height=H, n_labels=L, per_frame=K, samples=N, seed=0,
+              **{k: p for k, (_, p) in keep.items()}, **{k: t.data_ptr() for k, t in bufs.items()})
+
+    def call(n=1, **kw):
+        job = _lib.PointJob(**dict(ok, **kw))
+        return ctx.lib.csg_sample_object_points(ctx.ctx, C.byref(job), n, None)
+
+    INVALID, LIMIT_ERR = -1, -5
+    assert ctx.lib.csg_sample_object_points(ctx.ctx, None, 1, None) == INVALID
+    assert call(n=0) == INVALID
+    for kw in (dict(width=0), dict(height=0), dict(width=8193), dict(height=8193), dict(n_labels=0),
+               dict(per_frame=0), dict(per_frame=65), dict(samples=0), dict(samples=12), dict(samples=18),
+               dict(samples=16388), dict(instance=None), dict(info=None), dict(depth=None), dict(intrinsics=None),
+               dict(rgb=None), dict(obj_coords=None), {k: None for k in NAMES}):
+        assert call(**kw) == INVALID, kw
+    for name, step in (("instance", 2), ("info", 2), ("depth", 2), ("intrinsics", 2), ("frame_keys", 2),
+                       ("obj_coords", 1), ("pt_count", 2), ("pt_choose", 2), ("pt_xyz", 2), ("pt_rgb", 2),
+                       ("pt_rgb", 1), ("pt_coords", 1)):
+        assert call(**{name: ok[name] + step}) == INVALID, name
+    assert call(n_labels=257) == LIMIT_ERR
+    assert b"CSG_SPAN_MAX_LABELS" in ctx.lib.csg_last_error(ctx.ctx)
+    with pytest.raises(_lib.CsgError):
+        ctx.sample_points(1, samples=N, per_frame=K, instance=ok["instance"], info=ok["info"], pt_rgb=ok["pt_rgb"],
+                          n_labels=L, height=H, width=W)                           # pt_rgb without rgb
+    ctx.synchronize()
+    torch.cuda.synchronize()
+    for k, t in bufs.items():
+        assert (t.cpu().numpy() == FILL).all(), k                                  # nothing was enqueued
+    # a source nobody asked for may be missing, and the job itself is fine
+    assert call(depth=None, intrinsics=None, pt_xyz=None) == 0 and call(frame_keys=None) == 0 and call() == 0
+    ctx.synchronize()
+    got = _to_host(bufs, 1, K, N, "the valid job")
+    _check(got, restate_points(ids, labels, L, N, keys=[0], **src), "the valid job")
+    assert got["pt_count"].tolist() == [[H * W, 0]] and (got["pt_xyz"][0, 1].view(np.uint32) == NAN_BITS).all()
+    assert (got["pt_choose"][0, 1] == M32).all()
+
+
+N3 = 256             # samples per slot on the rendered frames: their slots hold 76 to 8,263 pixels
+
+
+def _upload(r, ref):
+    for k, e in enumerate(ref["epochs"]):
+        st = ref["wl"].epoch(e)
+        r.set_instance_transforms(k, st.models)
+        r.set_object_frames(k, st.object_frames)
+
+
+def _c3_expected(labels, seed):
+    from constructionsceneposeestimation_amd.object_points import intrinsics_rows
+    ref, src = c3_reference(None), c3_sources()
+    return restate_points(ref["instance"], labels, ref["n_labels"], N3, seed=seed, keys=ref["fr"]["frame_id"],
+                          depth=src["depth"], intrinsics=intrinsics_rows(ref["fr"]), rgb=src["rgb"],
+                          obj_coords=src["obj_coords"])
+
+
+def test_behind_a_render_and_the_plan_on_one_stream():
+    """render_into -> crop_objects (the plan) -> sample_points on one non-default stream, nothing in between."""
+    import torch
+    from constructionsceneposeestimation_amd.object_points import intrinsics_rows
+    from constructionsceneposeestimation_amd.renderer import Renderer
+    ref = c3_reference(None)
+    n, L = 3, ref["n_labels"]
+    dev = torch.device("cuda", 0)
+    fr = ref["fr"]
+    with Renderer(ref["wl"].scene, W3, H3, max_frames=3) as r:
+        assert r.n_labels == L
+        _upload(r, ref)
+        src = {"rgb": torch.empty((n, H3, W3, 3), dtype=torch.uint8, device=dev),
+               "instance": torch.empty((n, H3, W3), dtype=torch.int32, device=dev),
+               "depth": torch.empty((n, H3, W3), dtype=torch.float32, device=dev),
+               "obj_coords": torch.empty((n, H3, W3, 3), dtype=torch.int16, device=dev),
+               "stats": torch.empty((n, L, 5), dtype=torch.int32, device=dev)}
+        info = torch.full((n, K3, INFO_DTYPE.itemsize), FILL, dtype=torch.uint8, device=dev)
+        elig, elig_p = _dev(ref["elig"][:L])
+        intr, intr_p = _dev(intrinsics_rows(fr))
+        keys, keys_p = _dev(np.ascontiguousarray(fr["frame_id"]))
+        bufs = _out_buffers(NAMES, n, K3, N3)
+        stream = torch.cuda.Stream(dev)
+        stream.wait_stream(torch.cuda.current_stream(dev))
+        r.render_into(fr.ctypes.data, n, False, rgb=src["rgb"].data_ptr(), instance=src["instance"].data_ptr(),
+                      depth=src["depth"].data_ptr(), stats=src["stats"].data_ptr(),
+                      obj_coords=src["obj_coords"].data_ptr(), stream=stream.cuda_stream)
+        r.crop_objects(n, size=S3, per_frame=K3, min_pixels=MINPX3, pad=PAD3, instance=src["instance"].data_ptr(),
+                       stats=src["stats"].data_ptr(), eligible=elig_p, info=info.data_ptr(), stream=stream.cuda_stream)
+        r.sample_points(n, samples=N3, per_frame=K3, seed=5, instance=src["instance"].data_ptr(),
+                        info=info.data_ptr(), depth=src["depth"].data_ptr(), intrinsics=intr_p,
+                        rgb=src["rgb"].data_ptr(), obj_coords=src["obj_coords"].data_ptr(), frame_keys=keys_p,
+                        stream=stream.cuda_stream, **{k: t.data_ptr() for k, t in bufs.items()})
+        stream.synchronize()
+        r.synchronize()
+    got = _to_host(bufs, n, K3, N3, "C3 frames")
+    g_info = info.cpu().numpy().view(INFO_DTYPE).reshape(n, K3)
+    assert FIDS3 == [4, 17, 23] and np.array_equal(src["instance"].cpu().numpy(), ref["instance"])   # else: the renderer's
+    assert np.array_equal(g_info["label"], ref["info"]["label"])                                  # else: the crops'
+    exp = _c3_expected(g_info["label"], 5)
+    assert np.array_equal(exp["pt_count"], ref["info"]["pixels"])
+    assert (exp["pt_count"] > N3).sum() >= 10 and ((exp["pt_count"] > 0) & (exp["pt_count"] <= N3)).sum() >= 5
+    assert (exp["pt_count"] == 0).sum() == 3
+    _check(got, exp, "C3 frames")
+
+
+def test_render_crops_delivers_points():
+    from constructionsceneposeestimation_amd.camera_math import Intrinsics
+    from constructionsceneposeestimation_amd.object_points import intrinsics_rows
+    from constructionsceneposeestimation_amd.renderer import Renderer
+    ref = c3_reference(None)
+    it = Intrinsics(W3, H3)
+    rows = intrinsics_rows(ref["fr"])
+    assert (rows.view(np.uint32) == np.array([it.fx, it.fy, it.cx, it.cy], np.float32).view(np.uint32)).all()
+    with Renderer(ref["wl"].scene, W3, H3, max_frames=2) as r:         # two chunks: 2 frames and 1
+        _upload(r, ref)
+        kw = dict(size=S3, per_frame=K3, min_pixels=MINPX3, pad=PAD3)
+        out = r.render_crops(ref["fr"], want=("mask", "points"), samples=N3, seed=11, **kw)
+        plain = r.render_crops(ref["fr"], want=("mask",), **kw)
+    assert set(plain) == {"crop_mask", "info", "intrinsics"}           # the parent's keys
+    assert set(out) == set(plain) | set(NAMES)
+    assert np.array_equal(out["crop_mask"], plain["crop_mask"]) and np.array_equal(out["crop_mask"], ref["crop_mask"])
+    assert np.array_equal(out["info"]["label"], ref["info"]["label"])
+    _check({k: out[k] for k in NAMES}, _c3_expected(out["info"]["label"], 11), "render_crops")
