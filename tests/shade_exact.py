@@ -24,6 +24,24 @@ is shared with the oracle or the kernels (of the package only the scene model an
 * ids: the largest Z among fragments that are covered (``raster_exact.edge_cover``),
   lie in 2^-8 <= 1/W <= 2 and pass their alpha test; a tie goes to the smaller
   ``instance << 20 | triangle``.
+* The near plane (item 3).  A vertex may have W = +-2^j in front of the near plane
+  (1/8, 1/4) or behind the camera (negative); it is then given by its virtual screen
+  position, clip X = U W / 256 as before.  Clipping interpolates X and Y only; depth,
+  uv, det and the normal come from the original triangle's edge rows, so ``planes_exact``
+  and ``_grid_ints`` hold unchanged (the affine function that takes 1 / W_k at virtual
+  vertex k is the D plane, whatever the signs).  ``clip_exact`` is Sutherland-Hodgman
+  against W >= 1/2 in rationals over v0 -> v1, v1 -> v2, v2 -> v0 and the fan (q0, q_f,
+  q_f+1).  tt = (near - Wa) / (Wb - Wa) is in general no float32, but the clip vertex is
+  snapped to 24.8: a triangle is kept only if the exact 256 u and 256 v of every clip
+  vertex lie MARGIN_Q away from a rounding tie and below 2^19 px, and the float32 chain
+  in the written order snaps to the same integers.  Then the sub-triangles are integer
+  triangles, and a clipped triangle covers the union of ``edge_cover`` of them (zero
+  area drops one, negative area swaps), cut to 2^-8 <= 1/W <= 2 on the exact grid
+  integers.  A vertex with W = 0 (``tri_w0``) has no virtual position: its planes come
+  from the rational edge rows (``_grid_ints_w0``), with the same float32 check.
+* Texture tables.  A frame may carry a per-material table (an index, -1, KEEP_TEXTURE)
+  as ``csg_set_dr_textures`` takes it; ``render`` resolves every material through it, so
+  size, wrap, weights and alpha are the swapped texture's.
 
 Undecided fragments.  The kernels evaluate t in float32 (two or three roundings).  A
 fragment whose exact 256 t lies within max(2^-12, the sum of those roundings' half ulps)
@@ -62,10 +80,13 @@ Families (``FAMILIES``; the generators' docstrings say what each aims at, and
 tests/test_shade_exact.py counts that the aims occur): texel (and texel_npot, the 13 x 7
 texture in a frame of its own, so that the power-of-two frame can be asserted exact),
 thresh, persp, cross (and cross_near, the nearly parallel pairs), tie, range, light (one
-frame per light set) and trim.  Every frame
+frame per light set), trim, clip (clip, clip_edge, clip_tex, clip_pair: near-clipped
+triangles) and swap (seven frames that draw the same instances under seven texture
+tables).  Every frame
 is generated in both vertex orders; all frames of one size are one scene, frame f drawing
 its own instances (transform set f holds identity for them and the zero matrix for all
-others) under its own DR light, with N_KP keypoints of its own.
+others; the swap frames of one order share theirs) under its own DR light and texture
+table, with N_KP keypoints of its own.
 """
 import functools
 import math
@@ -85,7 +106,9 @@ ZS = 12 + PQ
 Z_FAR, Z_NEAR = 1 << (ZS - 8), 1 << (ZS + 1)
 TF = 40                    # fractional bits of the fixed-point texel arithmetic
 EDGES = ((1, 2), (2, 0), (0, 1))
-FAMILIES = ("texel", "thresh", "persp", "cross", "tie", "range", "light", "trim")
+FAMILIES = ("texel", "thresh", "persp", "cross", "tie", "range", "light", "trim", "clip", "swap")
+CLIP_GUARD = 1 << 27       # a clip vertex stays below 2^19 px
+KEEP_TEXTURE = -2          # a texture table's "as authored"
 MARGIN_Q = Fr(1, 1 << 10)
 MARGIN_REL = Fr(1, 1 << 18)
 NORMAL_COND = Fr(1, 1 << 21)
@@ -93,23 +116,43 @@ NEAR_ULPS = 8              # cross: two surfaces this many float32 ulps of 1 / W
 FAR_ULPS = 64              # range: a dropped centre this many ulps below 1 / far = 2^-8 (ulp 2^-32 there)
 
 
-def tri(xy, w, uv=None):
-    """A triangle: fixed-point vertices, one W (a float) or three, uvs in 1/256 or None."""
+def tri(xy, w, uv=None, tag=None):
+    """A triangle: fixed-point vertices, one W (a float) or three, uvs in 1/256 or None.  A vertex of W < near
+    (negative included) is given by its virtual screen position, X W / 256 being its clip X; ``tag`` names the
+    case a generator built it for (the tests count them)."""
     w = (w, w, w) if isinstance(w, (int, float)) else tuple(w)
-    return dict(xy=[(int(x), int(y)) for x, y in xy], w=tuple(float(v) for v in w),
-                uv=None if uv is None else [(int(a), int(b)) for a, b in uv])
+    t = dict(xy=[None if v is None else (int(v[0]), int(v[1])) for v in xy], w=tuple(float(v) for v in w),
+             uv=None if uv is None else [(int(a), int(b)) for a, b in uv])
+    if tag is not None:
+        t["tag"] = tag
+    return t
+
+
+def tri_w0(k, clip_xy, xy, w, tag=None):
+    """A triangle whose vertex k lies in the camera's plane: W = 0, clip (X, Y) = ``clip_xy`` (integers; it
+    has no screen position), the two others as in ``tri``.  No uvs."""
+    xy, w = list(xy), list(w)
+    xy.insert(k, None)
+    w.insert(k, 0.0)
+    t = tri(xy, w, None, tag)
+    t["clip0"] = (int(clip_xy[0]), int(clip_xy[1]))
+    return t
 
 
 def swapped(t):
     """The other vertex order: vertices 1 and 2 exchanged."""
     s = lambda a: None if a is None else [a[0], a[2], a[1]]      # noqa: E731
-    return dict(xy=s(t["xy"]), w=tuple(s(list(t["w"]))), uv=s(t["uv"]))
+    o = dict(xy=s(t["xy"]), w=tuple(s(list(t["w"]))), uv=s(t["uv"]))
+    for key in ("tag", "clip0"):
+        if key in t:
+            o[key] = t[key]
+    return o
 
 
 def vertices(t, cx, cy):
     """(3, 3) float64 camera-space vertices: ((U - 256 cx) W / 65536, -(V - 256 cy) W / 65536, -W)."""
-    return np.array([[(x - 256 * cx) * w / 65536.0, -(y - 256 * cy) * w / 65536.0, -w]
-                     for (x, y), w in zip(t["xy"], t["w"])])
+    return np.array([[t["clip0"][0] / 256.0, -t["clip0"][1] / 256.0, 0.0] if v is None else
+                     [(v[0] - 256 * cx) * w / 65536.0, -(v[1] - 256 * cy) * w / 65536.0, -w] for v, w in zip(t["xy"], t["w"])])
 
 
 def _grid_ints(t, Wd, Hd):
@@ -117,6 +160,8 @@ def _grid_ints(t, Wd, Hd):
     N / 2^(12 + pq), u / W = NU / 2^(20 + pq), v / W likewise: barycentric numerators e_k (they add up
     to 2 area) weighted with IW_k = 4096 / W_k and the vertex uvs."""
     xy = t["xy"]
+    if "clip0" in t:
+        return _grid_ints_w0(t, Wd, Hd)
     a2 = area2(xy)
     pq = abs(a2).bit_length() - 1
     assert a2 != 0 and abs(a2) == 1 << pq and pq <= PQ, "2 area is not a power of two"
@@ -125,16 +170,44 @@ def _grid_ints(t, Wd, Hd):
     Y = np.arange(Hd, dtype=np.int64) * 256 + 128
     N = np.zeros((Hd, Wd), np.int64)
     NU, NV = N.copy(), N.copy()
+    span = max(max(abs(c) for v in xy for c in v), 256 * max(Wd, Hd)) * 2     # bounds every coordinate difference: no int64 overflow
     for k, (a, b) in enumerate(EDGES):
         (xa, ya), (xb, yb) = xy[a], xy[b]
         iw = IWS / t["w"][k]
-        assert iw == int(iw) and 4 <= iw <= 4 * IWS
+        assert iw == int(iw) and 4 <= abs(iw) <= 8 * IWS
+        assert 2 * span * span * abs(int(iw)) * (1 if t["uv"] is None else max(1, max(abs(c) for c in t["uv"][k]))) < 1 << 60
         e = ((xa - X)[None, :] * (yb - Y)[:, None] - (xb - X)[None, :] * (ya - Y)[:, None]) * (s * int(iw))
         N += e
         if t["uv"] is not None:
             NU += e * t["uv"][k][0]
             NV += e * t["uv"][k][1]
     return N, NU, NV, pq
+
+
+def _edge_rows(v):
+    """The homogeneous edge rows A, B, C and det of clip vertices (X, Y, W), in rationals."""
+    A = [v[a][1] * v[b][2] - v[a][2] * v[b][1] for a, b in EDGES]
+    B = [v[a][2] * v[b][0] - v[a][0] * v[b][2] for a, b in EDGES]
+    C = [v[a][0] * v[b][1] - v[a][1] * v[b][0] for a, b in EDGES]
+    return A, B, C, v[0][0] * A[0] + v[0][1] * B[0] + v[0][2] * C[0]
+
+
+def det_exact(t):
+    """det of the clip matrix, a Fraction."""
+    return _edge_rows(_clip_space(t))[3]
+
+
+def _grid_ints_w0(t, Wd, Hd):
+    """``_grid_ints`` for a triangle with a vertex of W = 0 (no virtual screen triangle to take barycentric
+    numerators of): 1 / W = (sum A x + sum B y + sum C) / det from the rational edge rows, as N / 2^ZS, or
+    None if that is no integer at some centre."""
+    A, B, C, det = _edge_rows(_clip_space(t))
+    da, db, dc = sum(A) / det, sum(B) / det, sum(C) / det
+    n0, na, nb = (da / 2 + db / 2 + dc) * (1 << ZS), da * (1 << ZS), db * (1 << ZS)
+    if any(n.denominator != 1 for n in (n0, na, nb)) or abs(n0) + abs(na) * Wd + abs(nb) * Hd >= 1 << 62:
+        return None
+    N = int(n0) + int(na) * np.arange(Wd, dtype=np.int64)[None, :] + int(nb) * np.arange(Hd, dtype=np.int64)[:, None]
+    return N, np.zeros_like(N), np.zeros_like(N), PQ
 
 
 def _eq_scaled(val32, num, shift):
@@ -154,15 +227,13 @@ def planes_exact(t, Wd, Hd, cx, cy):
     P = projection(cx, cy).astype(f)
     with np.errstate(all="ignore"):
         X, Y, Wc = [((P[r, 0] * p[:, 0] + P[r, 1] * p[:, 1]) + P[r, 2] * p[:, 2]) + P[r, 3] for r in (0, 1, 3)]
-        eX = [Fr(x) * Fr(w) / 256 for (x, _), w in zip(t["xy"], t["w"])]
-        eY = [Fr(y) * Fr(w) / 256 for (_, y), w in zip(t["xy"], t["w"])]
-        eW = [Fr(w) for w in t["w"]]
+        eX, eY, eW = ([v[c] for v in _clip_space(t)] for c in range(3))
         same = lambda got, want: all(np.isfinite(g) and Fr(float(g)) == e for g, e in zip(got, want))   # noqa: E731
         if not (same(X, eX) and same(Y, eY) and same(Wc, eW)):
             return False
         rw = f(1.0) / Wc
         su, sv = X * rw, Y * rw
-        if [(int(np.rint(a * f(256.0))), int(np.rint(b * f(256.0)))) for a, b in zip(su, sv)] != t["xy"]:
+        if any(v is not None and (int(np.rint(a * f(256.0))), int(np.rint(b * f(256.0)))) != v for a, b, v in zip(su, sv, t["xy"])):
             return False
         A = [Y[a] * Wc[b] - Wc[a] * Y[b] for a, b in EDGES]
         B = [Wc[a] * X[b] - X[a] * Wc[b] for a, b in EDGES]
@@ -181,7 +252,10 @@ def planes_exact(t, Wd, Hd, cx, cy):
             return False
         uv = [(f(1.0), f(1.0))] * 3 if t["uv"] is None else [(f(a / UVQ), f(b / UVQ)) for a, b in t["uv"]]
         euv = [(Fr(1), Fr(1))] * 3 if t["uv"] is None else [(Fr(a, UVQ), Fr(b, UVQ)) for a, b in t["uv"]]
-        N, NU, NV, pq = _grid_ints(t, Wd, Hd)
+        grid = _grid_ints(t, Wd, Hd)
+        if grid is None:
+            return False
+        N, NU, NV, pq = grid
         x = (np.arange(Wd) + 0.5).astype(f)[None, :]
         y = (np.arange(Hd) + 0.5).astype(f)[:, None]
         for c, num, shift in ((None, N, 12 + pq), (0, NU, 20 + pq), (1, NV, 20 + pq)):
@@ -204,6 +278,83 @@ def planes_exact(t, Wd, Hd, cx, cy):
 def assert_planes_exact(tris, Wd, Hd, cx, cy):
     for k, t in enumerate(tris):
         assert planes_exact(t, Wd, Hd, cx, cy), f"triangle {k} is not exact: {t}"
+
+
+# -- item 3: the near plane ------------------------------------------------------------------------------
+def is_clipped(t):
+    return min(t["w"]) < NEAR
+
+
+def _clip_space(t):
+    """Clip X, Y, W of the three vertices as Fractions."""
+    return [(Fr(t["clip0"][0]), Fr(t["clip0"][1]), Fr(0)) if v is None else (Fr(v[0]) * Fr(w) / 256, Fr(v[1]) * Fr(w) / 256, Fr(w))
+            for v, w in zip(t["xy"], t["w"])]
+
+
+def _snap_clip_vertex(a, b):
+    """The vertex where the edge a -> b (clip X, Y, W, Fractions) meets W = near, snapped to 24.8: the
+    intersection in rationals, accepted only if 256 u and 256 v lie MARGIN_Q away from a rounding tie, below
+    CLIP_GUARD, and the float32 chain in the written order (tt, a + tt (b - a), times 1 / near, times 256,
+    rint) gives the same integers -> ((U, V), whether tt is a float32), or None."""
+    f = np.float32
+    near = Fr(NEAR)
+    tt = (near - a[2]) / (b[2] - a[2])
+    with np.errstate(all="ignore"):
+        tt32 = (f(NEAR) - f(a[2])) / (f(b[2]) - f(a[2]))
+        out = []
+        for c in (0, 1):
+            e = (a[c] + tt * (b[c] - a[c])) / near * 256
+            fl = e.numerator // e.denominator
+            if abs(e) >= CLIP_GUARD or abs(e - fl - Fr(1, 2)) < MARGIN_Q:
+                return None
+            n = (e + Fr(1, 2)).numerator // (e + Fr(1, 2)).denominator
+            r = f(a[c]) + tt32 * (f(b[c]) - f(a[c]))
+            got = np.rint((r * (f(1.0) / f(NEAR))) * f(256.0))
+            if not np.isfinite(got) or int(got) != n:
+                return None
+            out.append(n)
+    return tuple(out), Fr(float(tt32)) == tt
+
+
+@functools.lru_cache(maxsize=None)
+def _clip_key(xy, w, clip0):
+    v = _clip_space(dict(xy=xy, w=w, clip0=clip0))
+    inside = [p[2] >= Fr(NEAR) for p in v]
+    poly, tt_exact, ends = [], [], []
+    for k in range(3):                               # Sutherland-Hodgman over v0 -> v1, v1 -> v2, v2 -> v0
+        a, b = k, (k + 1) % 3
+        if inside[a]:
+            poly.append(xy[a])
+        if inside[a] != inside[b]:
+            r = _snap_clip_vertex(v[a], v[b])
+            if r is None:
+                return None
+            poly.append(r[0])
+            tt_exact.append(r[1])
+            ends.append((NEAR - w[a]) / (w[b] - w[a]))
+    subs = [[poly[0], poly[j], poly[j + 1]] for j in range(1, len(poly) - 1)]          # the fan
+    return dict(code=sum(int(s) << k for k, s in enumerate(inside)), poly=poly, subs=subs, tt_exact=tt_exact, tt=ends)
+
+
+def clip_exact(t):
+    """Item 3 on a triangle with a vertex of W < near, in rationals: dict(code: the inside mask, poly: the
+    snapped polygon, subs: its fan (q0, q_f, q_f+1), zero-area ones included, tt, tt_exact per crossing), or
+    None if a clip vertex is not decided (``_snap_clip_vertex``)."""
+    if not is_clipped(t):                            # (nothing to intersect: no rationals needed)
+        return dict(code=7, poly=list(t["xy"]), subs=[list(t["xy"])], tt_exact=[], tt=[])
+    return _clip_key(tuple(t["xy"]), tuple(t["w"]), t.get("clip0"))
+
+
+def cover_of(t, Wd, Hd):
+    """The pixel centres a triangle's raster sub-triangles cover (items 3 and 4; no range test)."""
+    if not is_clipped(t):
+        return edge_cover(t["xy"], Wd, Hd)
+    c = clip_exact(t)
+    assert c is not None, "a clip vertex of a generated triangle is not decided"
+    cov = np.zeros((Hd, Wd), bool)
+    for s in c["subs"]:
+        cov |= edge_cover(s, Wd, Hd)                  # (zero area covers nothing, negative area swaps)
+    return cov
 
 
 # -- the two rounding steps ----------------------------------------------------------------------------
@@ -375,8 +526,7 @@ def shade(t, cx, cy, consts):
             if not (_cmp_sqrt(lo + m, c2, hi - m) and _cmp_sqrt(lo * (1 + rel), c2, hi * (1 - rel))):
                 return None
         q.append(min(max(qk, 0), 65535))
-    X, Y, Wc = ([Fr(x) * Fr(w) / 256 for (x, _), w in zip(t["xy"], t["w"])],
-                [Fr(y) * Fr(w) / 256 for (_, y), w in zip(t["xy"], t["w"])], [Fr(w) for w in t["w"]])
+    X, Y, Wc = ([v[c] for v in _clip_space(t)] for c in range(3))
     det = (X[0] * (Y[1] * Wc[2] - Wc[1] * Y[2]) + Y[0] * (Wc[1] * X[2] - X[1] * Wc[2])
            + Wc[0] * (X[1] * Y[2] - Y[1] * X[2]))
     return dict(q=q, normal=normal, flipped=flip, det_positive=det > 0, flat=flat)
@@ -389,9 +539,10 @@ def _base255(material):
     return b.astype(np.int64)
 
 
-def render(insts, scene, light, Wd, Hd, cx, cy, first_instance):
+def render(insts, scene, light, Wd, Hd, cx, cy, first_instance, table=None):
     """The expected outputs of one frame.  ``insts``: [(label, material, [tri, ...])], drawn as the
-    scene's instances first_instance, first_instance + 1, ..."""
+    scene's instances first_instance, first_instance + 1, ...; ``table``: per material of the scene the
+    texture this frame gives it (an index, -1 for none, KEEP_TEXTURE), or None for the authored ones."""
     consts = light_fractions(light)
     npx = Wd * Hd
     bestZ = np.full(npx, -1, np.int64)
@@ -401,6 +552,7 @@ def render(insts, scene, light, Wd, Hd, cx, cy, first_instance):
     rgb = np.tile(np.array(consts[3], np.uint8), (npx, 1))
     normals = np.zeros((npx, 3), np.uint16)
     und_px = np.zeros(npx, bool)
+    clip_win = np.zeros(npx, bool)                         # the winner is a near-clipped triangle
     masks = np.zeros((N_LABELS, npx), bool)
     und_lab = np.zeros((N_LABELS, npx), bool)
     beyond = np.zeros((N_LABELS, npx), bool)               # covered but out of range (not in any output)
@@ -414,14 +566,17 @@ def render(insts, scene, light, Wd, Hd, cx, cy, first_instance):
     for i, (label, m, tris) in enumerate(insts):
         mat = scene.materials[m]
         base = _base255(mat)
-        tex = scene.textures[mat.texture].rgba if mat.texture >= 0 else None
+        ti = mat.texture if table is None or table[m] == KEEP_TEXTURE else int(table[m])
+        tex = scene.textures[ti].rgba if ti >= 0 else None
         for k, t in enumerate(tris):
             uid = ((first_instance + i) << 20) | k
-            cov = edge_cover(t["xy"], Wd, Hd).ravel()
+            cov = cover_of(t, Wd, Hd).ravel()
             N, NU, NV, pq = _grid_ints(t, Wd, Hd)
             Z = np.where(cov, N.ravel(), 0) << (PQ - pq)
             inr = cov & (Z >= Z_FAR) & (Z <= Z_NEAR)
             beyond[label] |= cov & ~inr
+            if 0 < max(t["w"]) < NEAR and min(t["w"]) > 0:         # wholly in front of the near plane: what it would cover
+                beyond[label] |= edge_cover(t["xy"], Wd, Hd).ravel()
             aims["out_far"] += int((cov & (Z < Z_FAR)).sum())
             if (cov & (Z < Z_FAR)).any():
                 gap = int((Z_FAR - Z[cov & (Z < Z_FAR)]).min())
@@ -430,7 +585,7 @@ def render(insts, scene, light, Wd, Hd, cx, cy, first_instance):
             if px.size == 0:
                 continue
             aims["frags"] += px.size
-            aims["w_ratio"] = max(aims["w_ratio"], max(t["w"]) / min(t["w"]))
+            aims["w_ratio"] = max(aims["w_ratio"], max(abs(v) for v in t["w"]) / min(abs(v) for v in t["w"] if v))
             Zp = Z[px]
             aims["z_far_exact"] += int((Zp == Z_FAR).sum())
             aims["z_near_exact"] += int((Zp == Z_NEAR).sum())
@@ -496,6 +651,7 @@ def render(insts, scene, light, Wd, Hd, cx, cy, first_instance):
             bestZ[w], bestU[w] = Zq[better], uid
             ids[w], depth[w], rgb[w] = label, d[passed][better], col[passed][better]
             normals[w] = np.array(sh["normal"], np.uint16)
+            clip_win[w] = is_clipped(t)
             drawn.append(dict(inst=i, tri=k, shade=sh, n_won=int(better.sum())))
     d64 = depth.astype(np.float64)
     on = ids >= 0
@@ -511,7 +667,7 @@ def render(insts, scene, light, Wd, Hd, cx, cy, first_instance):
     out = dict(ids=ids2, depth=depth.reshape(shp), rgb=rgb.reshape(Hd, Wd, 3), normals=normals.reshape(Hd, Wd, 3),
                points=points.reshape(Hd, Wd, 3), undecided=und_px.reshape(shp), bestZ=bestZ.reshape(shp),
                uid=bestU.reshape(shp), masks=masks.reshape(N_LABELS, Hd, Wd), und_label=und_lab.reshape(N_LABELS, Hd, Wd),
-               beyond=beyond.reshape(N_LABELS, Hd, Wd),
+               beyond=beyond.reshape(N_LABELS, Hd, Wd), clip_win=clip_win.reshape(shp),
                inst_stats=np.array([stats_of(ids2 == l) for l in range(N_LABELS)], np.uint32),
                amodal_stats=np.array([stats_of(mk.reshape(shp)) for mk in masks], np.uint32),
                covered=masks.sum(1).astype(np.uint32), aims=aims, drawn=drawn)
@@ -562,6 +718,7 @@ class _Builder:
         self.consts = [light_fractions(l) for l in self.lights]
         self.frames = []
         self.rejected = 0
+        self.undecided_clips = 0
 
     def texture(self, rgba):
         from constructionsceneposeestimation_amd.scene.model import Texture
@@ -790,7 +947,7 @@ def _cross(b, rng):
 def plane_z(t, Wd, Hd):
     """(Z, in range, covered) (H, W) of one triangle: 1 / W = Z / 2^ZS on the covered centres."""
     N, _, _, pq = _grid_ints(t, Wd, Hd)
-    cov = edge_cover(t["xy"], Wd, Hd)
+    cov = cover_of(t, Wd, Hd)
     Z = np.where(cov, N, 0) << (PQ - pq)
     return Z, cov & (Z >= Z_FAR) & (Z <= Z_NEAR), cov
 
@@ -975,14 +1132,327 @@ def _trim(b, rng):
     b.frame("trim", 0, insts)
 
 
-_GENERATORS = (_texel, _thresh, _persp, _cross, _tie, _range, _light, _trim)
+def _virt_tri(rng, Wd, Hd, p, q, horiz, pad_px, snap=16):
+    """As ``right_tri`` with the vertices up to ``pad_px`` outside the frame: the virtual screen position of
+    a vertex in front of the near plane may lie anywhere."""
+    n_al, n_ac = (Wd, Hd) if horiz else (Hd, Wd)
+    L, Q, pad = 1 << p, 1 << q, pad_px * 256
+    if n_al * 256 + 2 * pad < L:
+        return None
+    a0 = int(rng.integers(-pad // snap, (n_al * 256 + pad - L) // snap + 1)) * snap
+    b0 = int(rng.integers(-pad // snap, (n_ac * 256 + pad) // snap + 1)) * snap
+    sgn = int(rng.choice([-1, 1]))
+    c = int(rng.integers((a0 - L // 2) // snap, (a0 + L + L // 2) // snap + 1)) * snap
+    pts = [(a0, b0), (a0 + L, b0), (c, b0 + sgn * Q)]
+    return pts if horiz else [(y, x) for x, y in pts]
 
 
-def _place_keypoints(exp, rng, Wd, Hd, cx, cy):
-    """N_KP float32 camera-space points for a frame: on centres of drawn, decided pixels with W exactly the
-    drawn depth (vis 2) and one float32 step behind it (vis 1); on the last column and row; at u = W
-    (outside); behind the near plane."""
+def pair_need(Hd):
+    """clip_pair: each triangle of a pair is the nearer one on this many of their common centres."""
+    return 30 if Hd >= 64 else 12
+
+
+def texels_of(t, tex, Wd, Hd):
+    """The in-range fragments of one textured triangle on ``tex`` -> (texel column floor(t_x), texel row, filtered
+    alpha), unwrapped, as ``render`` computes them."""
+    N, NU, NV, pq = _grid_ints(t, Wd, Hd)
+    Z = np.where(cover_of(t, Wd, Hd), N, 0).ravel() << (PQ - pq)
+    px = np.nonzero((Z >= Z_FAR) & (Z <= Z_NEAR))[0]
+    d64 = rn32_recip(Z[px]).astype(np.float64)
+    u32 = (np.ldexp(NU.ravel()[px].astype(np.float64), -(20 + pq)) * d64).astype(np.float32)
+    v32 = (np.ldexp(NV.ravel()[px].astype(np.float64), -(20 + pq)) * d64).astype(np.float32)
+    c, _, _, flags = sample(tex, u32, v32)
+    tx = (flags["texel"] + 2048) // 4096
+    return tx, flags["texel"] - tx * 4096, c[:, 3]
+
+
+def _orient(t):
+    """The sign of det: that of 2 area W0 W1 W2 (positive W keep the screen orientation)."""
+    return 1 if area2(t["xy"]) * t["w"][0] * t["w"][1] * t["w"][2] > 0 else -1
+
+
+def _clip_search(rng, b, make, min_px, max_px, pred=None, tries=20000, must=True, cheap=None):
+    """A triangle from ``make`` that satisfies ``cheap``, whose clip vertices are decided in both vertex
+    orders, that shows min_px .. max_px in-range centres, satisfies ``pred`` (given the triangle and its
+    ``plane_z``) and passes the input conditions (``_Builder.ok``); the tests run cheapest first."""
+    for _ in range(tries):
+        t = make()
+        if t is None or abs(area2(t["xy"])).bit_length() - 1 > PQ or (cheap is not None and not cheap(t)):
+            continue
+        if clip_exact(t) is None:
+            b.undecided_clips += 1
+            continue
+        if min_px > 0:                               # no more centres than the polygon's box holds inside the frame,
+            x0, y0, x1, y1, need = getattr(pred, "within", (0, 0, b.W, b.H, min_px))      # or inside the pixel box ``pred`` needs
+            xs, ys = [v[0] for v in clip_exact(t)["poly"]] or [0], [v[1] for v in clip_exact(t)["poly"]] or [0]
+            bw = (min(max(xs), x1 * 256) - max(min(xs), x0 * 256)) // 256 + 1
+            bh = (min(max(ys), y1 * 256) - max(min(ys), y0 * 256)) // 256 + 1
+            if bw <= 0 or bh <= 0 or bw * bh < need:
+                continue
+        pz = plane_z(t, b.W, b.H)
+        if not min_px <= int(pz[1].sum()) <= max_px or (pred is not None and not pred(t, pz)):
+            continue
+        if clip_exact(swapped(t)) is None:
+            b.undecided_clips += 1
+            continue
+        if b.ok(t, 0):
+            return t
+    assert not must, "the generator found no exact clipped triangle"
+    return None
+
+
+PALETTE = ((255, 60, 60), (60, 255, 60), (60, 60, 255), (255, 255, 60), (255, 60, 255), (60, 255, 255), (255, 255, 255),
+           (128, 64, 200), (200, 128, 64), (64, 200, 128))
+W_IN, W_FRONT, W_BEHIND = (1.0, 2.0, 4.0, 16.0), (0.125, 0.25), (-4.0, -1.0, -0.5, -0.25)
+
+
+def _clip(b, rng):
+    """Triangles with one or two vertices in front of the near plane W = 1/2 (W of 1/8, 1/4, or negative:
+    behind the camera), in four frames, all in front of nothing or of a far backdrop.
+    clip: every inside mask (code 1, 2, 4: one sub-triangle; 3, 5, 6: two) with the outside vertices at small
+    positive W and behind the camera, in both orientations, W ratios up to 128; a vertex at exactly W = near
+    (inside; tt = 0 or 1 on its edges, a zero-area sub-triangle first or second in the fan) at each index, one
+    with both others outside (nothing left), and a flat triangle at W = near (all inside: drawn, 1 / W = 2); a
+    triangle of W = -1, -1, -2 alone in label 5 (nothing).
+    clip_edge: W varying along x or y only, 1, 1, -1, so that the clip edge is a column or row of pixel
+    centres with 1 / W = 2 exactly, as a left / top edge (centres kept) and a right / bottom one (not); a
+    visible strip whose virtual vertices lie left of, right of and above the frame (one behind the camera),
+    and one whose three virtual vertices all lie above it.
+    clip_tex: alpha-tested cards across the near plane (W constant along one axis, 16 x 8 texture, an opaque
+    2 x 2 block on the visible side and one on the cut side) and opaque textured clipped triangles.
+    clip_pair: pairs of different labels, clipped with clipped and clipped with unclipped, that cross inside
+    the clipped region (each is the nearer one on ``pair_need`` common centres or more)."""
+    Wd, Hd = b.W, b.H
+    big = Hd >= 64
+    lim = (60, 420) if big else (24, 150)
+    pal = iter(PALETTE * 8)
+
+    def coded(code, outs, ins, orient, uv=False, tag=None, lo=12, hi=15, lim=lim, pred=None):
+        def make():
+            p, q = _sizes(rng, Wd, Hd, lo, hi)
+            xy = _virt_tri(rng, Wd, Hd, p, q, bool(rng.integers(2)), 48)
+            if xy is None:
+                return None
+            w = [float(rng.choice(ins if code >> k & 1 else outs)) for k in range(3)]
+            uvs = [(int(rng.integers(-16, 17)) * 16, int(rng.integers(-16, 17)) * 16) for _ in range(3)] if uv else None
+            return tri(xy, w, uvs, tag)
+        return _clip_search(rng, b, make, lim[0], lim[1], pred, cheap=None if orient is None else lambda t: _orient(t) == orient)
+
+    insts = []
+    for code in (1, 2, 4, 3, 5, 6):
+        tris = [coded(code, W_FRONT, (16.0,) if code == 1 else W_IN, 1), coded(code, W_BEHIND, W_IN, -1),
+                coded(code, W_FRONT + W_BEHIND, W_IN, None)]
+        insts.append((len(insts) % 5, b.material(next(pal)), tris))
+    near = []
+    for idx in range(3):                             # W = near at vertex idx, the others (in, out) and (out, in)
+        for flip in (0, 1):
+            def make():
+                p, q = _sizes(rng, Wd, Hd, 12, 14)
+                xy = _virt_tri(rng, Wd, Hd, p, q, bool(rng.integers(2)), 16)
+                w = [0.0, 0.0, 0.0]
+                w[idx] = NEAR
+                w[(idx + 1 + flip) % 3] = float(rng.choice((1.0, 2.0, 4.0)))
+                w[(idx + 2 - flip) % 3] = float(rng.choice(W_FRONT + W_BEHIND))
+                return None if xy is None else tri(xy, w, None, "near_vertex")
+            near.append(_clip_search(rng, b, make, lim[0] // 2, lim[1]))
+
+    def make():
+        p, q = _sizes(rng, Wd, Hd, 12, 14)
+        xy = _virt_tri(rng, Wd, Hd, p, q, bool(rng.integers(2)), 16)
+        return None if xy is None else tri(xy, (NEAR, float(rng.choice(W_FRONT)), float(rng.choice(W_BEHIND))), None, "near_alone")
+    near.append(_clip_search(rng, b, make, 0, 0))
+    insts.append((0, b.material(next(pal)), near[:4]))
+    insts.append((1, b.material(next(pal)), near[4:]))
+
+    def make():
+        p, q = _sizes(rng, Wd, Hd, 11, 12)
+        xy = right_tri(rng, Wd, Hd, p, q, bool(rng.integers(2)), inside=True)
+        return None if xy is None else tri(xy, NEAR, None, "near_flat")
+    insts.append((2, b.material(next(pal)), [_pick(rng, b, 0, make)]))
+
+    def make():
+        p, q = _sizes(rng, Wd, Hd, 12, 14)
+        xy = right_tri(rng, Wd, Hd, p, q, bool(rng.integers(2)), inside=True)
+        return None if xy is None else tri(xy, (-1.0, -1.0, -2.0), None, "invisible")
+    insts.append((5, b.material(next(pal)), [_clip_search(rng, b, make, 0, 0)]))
+    b.frame("clip", 0, insts)
+
+    # clip edges through pixel centres, and the homogeneous reject
+    insts = []
+    p, q = (12, 13) if big else (11, 12)
+    L, Q = 1 << p, 1 << q
+    edge = []
+    for axis in (0, 1):
+        for sg in (1, -1):                           # sg > 0: the clip edge is the region's left / top edge
+            for _ in range(2):
+                def make():
+                    n_ac, n_al = (Wd, Hd) if axis == 0 else (Hd, Wd)
+                    lo, hi = (0, n_ac - Q // 512 - 1) if sg > 0 else (Q // 512, n_ac - 1)
+                    line = int(rng.integers(lo, hi + 1)) * 256 + 128            # 1 / W = 2 on this column / row of centres
+                    a = line + sg * (Q // 2)
+                    y0 = int(rng.integers(0, (n_al * 256 - L) // 16 + 1)) * 16
+                    yb = y0 + int(rng.integers(0, L // 16 + 1)) * 16
+                    pts = [(a, y0), (a, y0 + L), (a + sg * Q, yb)]
+                    return tri(pts if axis == 0 else [(y, x) for x, y in pts], (1.0, 1.0, -1.0), None,
+                               f"edge_{'xy'[axis]}_{'incl' if sg > 0 else 'excl'}")
+                edge.append(_clip_search(rng, b, make, 20, 1 << 20))
+    for k in range(0, 8, 2):
+        insts.append((k // 2, b.material(next(pal)), edge[k:k + 2]))
+    ya = (Hd - 8) * 256                              # a strip along the bottom: A left of, B right of, C above the frame
+    qs = 14 if big else 13
+    xa = -((1 << 15) - Wd * 256) // 2 // 16 * 16
+    strip = tri([(xa, ya), (xa + (1 << 15), ya), (Wd * 128, ya - (1 << qs))], (1.0, 1.0, -1.0), None, "hom_sides")
+    assert clip_exact(strip) is not None and b.ok(strip, 0), "the strip under the homogeneous reject is not exact"
+    xs = (Wd // 2 - 16) * 256                        # all three above the frame: A, B 8 px, C (behind the camera) 40 px
+    above = tri([(xs, -8 * 256), (xs + (1 << 13), -8 * 256), (xs + (1 << 12), -40 * 256)], (1.0, 1.0, -1.0), None, "hom_above")
+    assert clip_exact(above) is not None and b.ok(above, 0), "the triangle above the frame is not exact"
+    # a vertex in the camera's plane, W = 0: clip (+-2^a, 0, 0) or (0, +-2^a, 0); the two others differ by 2^j units
+    # across that axis, so that det = X0 W1 W2 (y1 - y2) is a power of two.  A seeded search of at most 10,000.
+    w0 = []
+    for n_try in range(10000):
+        a, axis, k, j = int(rng.integers(0, 7)), int(rng.integers(2)), int(rng.integers(3)), int(rng.integers(10, 14))
+        n_al, n_ac = (Wd, Hd) if axis == 0 else (Hd, Wd)
+        x1, y1 = int(rng.integers(0, n_al * 16 + 1)) * 16, int(rng.integers(0, n_ac * 16 + 1)) * 16
+        x2, y2 = x1 + int(rng.integers(-64, 65)) * 16, y1 + int(rng.choice([-1, 1])) * (1 << j)
+        c0 = (int(rng.choice([-1, 1])) << a, 0)
+        pts = [(x1, y1), (x2, y2)]
+        if axis:
+            pts, c0 = [(y, x) for x, y in pts], (0, c0[0])
+        t = tri_w0(k, c0, pts, [float(v) for v in rng.choice((0.5, 1.0, 2.0, 4.0), 2)], "w0")
+        if any(clip_exact(s) is None for s in (t, swapped(t))):
+            continue
+        if planes_exact(t, Wd, Hd, b.cx, b.cy) and int(plane_z(t, Wd, Hd)[1].sum()) >= 20 and b.ok(t, 0):
+            w0.append(t)
+            if len(w0) == 2:
+                break
+    b.w0_searched = n_try + 1
+    insts.append((4, b.material(next(pal)), [strip, above] + w0))
+    b.frame("clip_edge", 0, insts)
+
+    # textured: cards (their texture reads columns up to 7 of the window with W 1 -> 1/4 and up to 3 with 1 -> -1: the clip
+    # line lies at 2/3 and at 1/4 of the u range, so the second block, at columns 8, 9 and 5, 6, is never read) and opaque triangles
+    insts = []
+    back = [tri([(0, 0), (1 << 14, 0), (0, 1 << 13)], 64.0), tri([(1 << 14, 0), (1 << 14, 1 << 13), (0, 1 << 13)], 64.0)]
+    assert all(b.ok(t, 0) for t in back)
+    insts.append((0, b.material((120, 110, 100)), back))
+    Lc = 1 << 13
+    for k, (win, wout, vis, cut) in enumerate(((1.0, 0.25, 2, 8), (1.0, -1.0, 0, 5))):
+        t = _rgba(rng, 8, 16)
+        t[..., 3] = 0
+        bx, by = 4, 2
+        for off in (vis, cut):                       # window offsets of the two opaque blocks along the card's W axis
+            t[by:by + 2, (bx - 4 + off) % 16:(bx - 4 + off) % 16 + 2, 3] = 255
+        m = b.material((255, 255, 255), b.texture(t), True, 100)
+        for _ in range(4000):
+            x0 = int(rng.integers(2, max(3, Wd - 34))) * 256
+            y0 = int(rng.integers(0, max(1, Hd - 32 + 1))) * 256
+            if k == 1:                               # the visible part lies beyond the inside edge, away from the other
+                x0 = int(rng.integers(18, max(19, Wd - 2))) * 256
+            A, B, C, D = (x0, y0), (x0 + Lc, y0), (x0, y0 + Lc), (x0 + Lc, y0 + Lc)
+            u0, v0 = (bx - 4) * 16, 256 - (by - 2) * 32
+            uv = {A: (u0, v0), B: (u0 + 160, v0), C: (u0, v0 - 160), D: (u0 + 160, v0 - 160)}
+            w = {A: win, C: win, B: wout, D: wout}
+            t1 = tri([A, B, C], [w[A], w[B], w[C]], [uv[A], uv[B], uv[C]], "card")
+            t2 = tri([B, D, C], [w[B], w[D], w[C]], [uv[B], uv[D], uv[C]], "card")
+            if all(clip_exact(s) is not None for s in (t1, t2, swapped(t1), swapped(t2))) and b.ok(t1, 0) and b.ok(t2, 0):
+                break
+        else:
+            raise AssertionError("no exact clipped card")
+        insts.append((1 + k, m, [t1, t2]))
+    mo = b.material((255, 255, 255), b.texture(_rgba(rng, 8, 16)))
+    insts.append((3, mo, [coded(5, W_FRONT, (1.0, 2.0), None, uv=True), coded(2, W_BEHIND, (1.0, 2.0), None, uv=True)]))
+    def crossing(o, others=()):
+        """Whether a triangle and ``o`` are each the nearer one on enough common centres that ``others`` leave alone."""
+        need = pair_need(Hd)
+        Zo, io, _ = plane_z(o, Wd, Hd)
+        for x in others:
+            io = io & ~plane_z(x, Wd, Hd)[1]
+
+        def pred(t, pz):
+            Zt, it, _ = pz
+            return min(int((Zo > Zt)[io & it].sum()), int((Zo < Zt)[io & it].sum())) >= need
+        ys, xs = np.nonzero(io)                      # the partner's polygon has to reach 2 need centres of this box
+        pred.within = (int(xs.min()), int(ys.min()), int(xs.max()) + 1, int(ys.max()) + 1, 2 * need) if ys.size else (0, 0, 0, 0, 1)
+        return pred
+    a1 = coded(3, W_FRONT, (4.0, 16.0), None, tag="pair_cc")
+    a2 = coded(6, W_BEHIND + W_FRONT, W_IN, None, tag="pair_cc", pred=crossing(a1))
+
+    def make():
+        p, q = _sizes(rng, Wd, Hd, 12, 14)
+        xy = right_tri(rng, Wd, Hd, p, q, bool(rng.integers(2)))
+        return None if xy is None else tri(xy, [float(v) for v in rng.choice((1.0, 2.0, 4.0), 3)], None, "pair_cu")
+    for _ in range(20):                              # (not every clipped triangle has room for a partner beside the first pair)
+        c1 = coded(5, W_BEHIND, (4.0, 16.0), None, tag="pair_cu")
+        c2 = _clip_search(rng, b, make, 12, 1 << 20, crossing(c1, (a1, a2)), 2000, False)
+        if c2 is not None:
+            break
+    assert c2 is not None, "no crossing pair of a clipped and an unclipped triangle"
+    b.frame("clip_tex", 0, insts)
+    insts = [(0, b.material((120, 110, 100)), [dict(t) for t in back])]
+    for lab, t in ((1, a1), (2, a2), (3, c1), (4, c2)):
+        insts.append((lab, b.material(next(pal)), [t]))
+    b.frame("clip_pair", 0, insts)
+
+
+def _swap(b, rng):
+    """Texture tables (``csg_set_dr_textures``): one set of instances -- an opaque backdrop, two flat and two
+    tilted alpha-tested cards on one material (authored: 16 x 8, one opaque 2 x 2 block, as ``_trim``; the cards show
+    10 x 3 texels around it) and two
+    opaque textured triangles -- drawn by seven frames that differ in their table alone: the authored
+    indices spelt out; KEEP_TEXTURE; the same alpha with other RGB; the block in the opposite corner of the
+    card's window; a random 4 x 4; a random 13 x 7 (swap_npot); and -1 on the opaque material."""
+    Wd, Hd = b.W, b.H
+
+    def block(bx, by):
+        t = _rgba(rng, 8, 16)
+        t[..., 3] = 0
+        t[by:by + 2, bx:bx + 2, 3] = 255
+        return t
+    auth = block(2, 2)
+    rgb2 = _rgba(rng, 8, 16)
+    rgb2[..., 3] = auth[..., 3]
+    T = [b.texture(t) for t in (auth, rgb2, block(9, 3), _rgba(rng, 4, 4), _rgba(rng, 7, 13))]
+    O = [b.texture(_rgba(rng, 8, 16)) for _ in range(2)]
+    ma = b.material((255, 255, 255), T[0], True, 100)
+    mo = b.material((200, 255, 120), O[0])
+    insts = []
+    back = [tri([(0, 0), (1 << 14, 0), (0, 1 << 13)], 64.0), tri([(1 << 14, 0), (1 << 14, 1 << 13), (0, 1 << 13)], 64.0)]
+    assert all(b.ok(t, 0) for t in back)
+    insts.append((0, b.material((120, 110, 100)), back))
+    L = 1 << 13
+    for k in range(4):
+        for _ in range(2000):
+            x0 = int(rng.integers(0, max(1, Wd - 32 + 1))) * 256
+            y0 = int(rng.integers(0, max(1, Hd - 32 + 1))) * 256
+            A, B, C, D = (x0, y0), (x0 + L, y0), (x0, y0 + L), (x0 + L, y0 + L)
+            wl, wr = (2.0, 2.0) if k % 2 == 0 else ((2.0, 8.0) if k == 1 else (4.0, 1.0))
+            u0, v0 = 16, 256 - 48                    # the card shows texel columns 1 .. 11 and rows 1.5 .. 4.5: with the trim's
+            uv = {A: (u0, v0), B: (u0 + 160, v0), C: (u0, v0 - 96), D: (u0 + 160, v0 - 96)}   # guard band less than a repeat
+            w = {A: wl, C: wl, B: wr, D: wr}
+            t1 = tri([A, B, C], [w[A], w[B], w[C]], [uv[A], uv[B], uv[C]])
+            t2 = tri([B, D, C], [w[B], w[D], w[C]], [uv[B], uv[D], uv[C]])
+            if b.ok(t1, 0) and b.ok(t2, 0):
+                break
+        else:
+            raise AssertionError("no exact card")
+        insts.append((1 + k, ma, [t1, t2]))
+    insts.append((5, mo, [_tilted(rng, b, 0, ws, 2, 12, 13) for ws in ((1, 2, 2), (2, 2, 4))]))
+    for name, table in (("swap_id", {ma: T[0], mo: O[0]}), ("swap_keep", {}), ("swap_rgb", {ma: T[1], mo: O[1]}),
+                        ("swap_alpha", {ma: T[2]}), ("swap_4x4", {ma: T[3], mo: T[3]}), ("swap_npot", {ma: T[4]}),
+                        ("swap_none", {mo: -1})):
+        b.frames.append(dict(family=name, light=0, insts=insts, table=table, share="swap"))
+
+
+_GENERATORS = (_texel, _thresh, _persp, _cross, _tie, _range, _light, _trim, _clip, _swap)
+
+
+def _place_keypoints(exp, rng, Wd, Hd, cx, cy, prefer=None):
+    """N_KP float32 camera-space points for a frame: on centres of drawn, decided pixels (of ``prefer``, a
+    mask, where it has any) with W exactly the drawn depth (vis 2) and one float32 step behind it (vis 1);
+    on the last column and row; at u = W (outside); behind the near plane."""
     ok = (exp["ids"] >= 0) & ~exp["undecided"]
+    if prefer is not None and (ok & prefer).any():
+        ok &= prefer
     ys, xs = np.nonzero(ok)
     pts = []
     f = np.float32
@@ -1018,11 +1488,15 @@ def batch(Wd, Hd):
     scene = b.scene
     frames = []
     rng = np.random.default_rng(Wd)
+    shared = {}
     for spec in b.frames:
         for order in (0, 1):
             insts = [(l, m, [t if order == 0 else swapped(t) for t in tris]) for l, m, tris in spec["insts"]]
-            first = len(scene.instances)
-            for l, m, tris in insts:
+            key = (spec.get("share"), order)         # frames of one ``share`` draw the same instances
+            first = shared.get(key, len(scene.instances))
+            if key[0] is not None:
+                shared[key] = first
+            for l, m, tris in insts if first == len(scene.instances) else ():
                 assert_planes_exact(tris, Wd, Hd, cx, cy)
                 pos = np.concatenate([vertices(t, cx, cy) for t in tris]).astype(np.float32)
                 idx = np.arange(pos.shape[0], dtype=np.uint32).reshape(-1, 3)
@@ -1034,11 +1508,14 @@ def batch(Wd, Hd):
                     uvs, uvi = np.zeros((0, 2), np.float32), np.zeros((0, 3), np.uint32)
                 scene.meshes.append(Mesh(f"{spec['family']}{order}_{len(scene.meshes)}", pos, idx, uvs, uvi, m))
                 scene.instances.append(Instance(len(scene.meshes) - 1, np.eye(4), l, l, np.eye(4)))
-            exp = render(insts, scene, b.lights[spec["light"]], Wd, Hd, cx, cy, first)
-            kp = _place_keypoints(exp, rng, Wd, Hd, cx, cy)
+            table = None
+            if spec.get("table") is not None:
+                table = np.array([spec["table"].get(m, KEEP_TEXTURE) for m in range(len(scene.materials))], np.int32)
+            exp = render(insts, scene, b.lights[spec["light"]], Wd, Hd, cx, cy, first, table)
+            kp = _place_keypoints(exp, rng, Wd, Hd, cx, cy, exp["clip_win"] if spec["family"].startswith("clip") else None)
             kuv, kvis = keypoints(kp, exp["depth"], Wd, Hd, cx, cy)
             fr = dict(exp, family=spec["family"], order=order, light=spec["light"], insts=insts, first=first,
-                      count=len(insts), kp=kp, kp_uv=kuv, kp_vis=kvis)
+                      count=len(insts), kp=kp, kp_uv=kuv, kp_vis=kvis, table=table)
             for a in fr.values():
                 if isinstance(a, np.ndarray):
                     a.setflags(write=False)
@@ -1051,7 +1528,8 @@ def batch(Wd, Hd):
     models.setflags(write=False)
     V = np.broadcast_to(np.eye(4), (n, 4, 4)).copy()
     P = np.broadcast_to(projection(cx, cy), (n, 4, 4)).copy()
-    return dict(scene=scene, V=V, P=P, models=models, frames=frames, W=Wd, H=Hd, lights=b.lights, rejected=b.rejected)
+    return dict(scene=scene, V=V, P=P, models=models, frames=frames, W=Wd, H=Hd, lights=b.lights, rejected=b.rejected,
+                undecided_clips=b.undecided_clips, w0_searched=b.w0_searched)
 
 
 @functools.lru_cache(maxsize=None)
@@ -1063,7 +1541,7 @@ def oracle_frames(Wd, Hd):
     o = Oracle(pack_scene(b["scene"]), Wd, Hd, near=NEAR, far=FAR)
     out = []
     for f, fr in enumerate(b["frames"]):
-        st = o.frame_state(models16=b["models"][f], light=b["lights"][fr["light"]])
+        st = o.frame_state(models16=b["models"][f], light=b["lights"][fr["light"]], texture_per_material=fr["table"])
         r = st.render(b["V"][f], b["P"][f], extra=True, covered=True)
         r["keypoints_uv"], r["keypoints_vis"] = st.keypoints(b["V"][f], b["P"][f], fr["kp"], r["depth"])
         out.append(r)

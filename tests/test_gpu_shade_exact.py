@@ -3,9 +3,12 @@ tests/shade_exact.py: ids, rgb, depth bits, f16 normals, points, label stats,
 label coverage and keypoints of every family's frames equal what integers and
 rationals say on every decided pixel (no oracle involved), every output is
 bit-exact against the oracle on all pixels besides, csg_amodal_spans' per-label
-masks and stats equal the alpha-tested, range-tested exact masks, and the alpha
-trim engages on the trim family's cards.  All frames of a size, with their light
-sets, are one batch; the CPU side of the same frames is tests/test_shade_exact.py."""
+masks and stats equal the alpha-tested, range-tested exact masks, csg_crop_amodal's
+masks of whole-frame windows equal them on the near-clipped frames, and the alpha
+trim engages on the trim family's cards and under a table that keeps the alpha
+bytes, and leaves clipped cards alone.  All frames of a size, with their light sets
+and texture tables, are one batch; the CPU side of the same frames is
+tests/test_shade_exact.py."""
 import os
 
 import numpy as np
@@ -13,11 +16,13 @@ import pytest
 
 from tests import shade_exact as sx
 from tests.test_gpu_amodal_rle import _decode, _run
+from tests.test_gpu_crop_amodal import _amodal, _explicit
 from tests.test_gpu_parity import _assert_extra, _assert_same
 
 pytestmark = pytest.mark.gpu
 SIZES = [pytest.param(s, id=f"{s[0]}x{s[1]}") for s in sx.SIZES]
 WANT = ("rgb", "instance", "depth", "normals", "points", "stats", "covered", "keypoints")
+CROP = 96                   # the smallest crop side that holds a whole frame of either size
 
 
 def _renderer(b, n):
@@ -32,6 +37,8 @@ def _setup(r, b):
         r.set_instance_transforms(f, b["models"][f])
         r.set_dr_light(f, b["lights"][fr["light"]])
         r.set_keypoints(f, fr["kp"])
+        if fr["table"] is not None:
+            r.set_dr_textures(f, fr["table"])
 
 
 @pytest.fixture(scope="module", params=SIZES)
@@ -53,7 +60,11 @@ def run(request):
         _setup(r, b)
         gpu = r.render(fr, want=WANT)
         amodal = _run(r, fr, cap)
-    return dict(W=W, H=H, b=b, gpu=gpu, amodal=amodal, cap=cap, frames=fr)
+        # every label's amodal crop of the window (0, 0, CROP) on the near-clipped frames: sample (i, j) is pixel (i, j)
+        clip = [f for f, x in enumerate(b["frames"]) if x["family"].startswith("clip")]
+        crops = _amodal(r, fr[clip], _explicit([[(l, 0.0, 0.0, float(CROP)) for l in range(sx.N_LABELS)]] * len(clip), sx.N_LABELS),
+                        CROP)
+    return dict(W=W, H=H, b=b, gpu=gpu, amodal=amodal, cap=cap, frames=fr, clip=clip, crops=crops)
 
 
 def test_every_output_equals_the_exact_reference(run):
@@ -103,12 +114,28 @@ def test_amodal_spans_equal_the_exact_masks(run):
                 assert np.array_equal(st[f, l], fr["amodal_stats"][l]), f"{what} label {l}: stats"
 
 
-def test_the_trim_engages_on_the_trim_family(run):
-    """The trim family's frames alone, with the trim on (the default) and off: the same exact images, and
-    fewer bin entries with it on (the counter tests/test_gpu_alpha_trim.py uses)."""
-    b, W, H = run["b"], run["W"], run["H"]
-    which = [f for f, fr in enumerate(b["frames"]) if fr["family"] == "trim"]
-    assert len(which) == 2
+def test_amodal_crops_equal_the_exact_masks_on_clipped_frames(run):
+    """csg_crop_amodal holds the third copy of the clip table: whole-frame windows on the clip family."""
+    W, H = run["W"], run["H"]
+    assert len(run["clip"]) == 8 and run["crops"].shape == (8, sx.N_LABELS, CROP, CROP)
+    for n, f in enumerate(run["clip"]):
+        fr = run["b"]["frames"][f]
+        what = f'{W}x{H} {fr["family"]}/{fr["order"]}'
+        for l in range(sx.N_LABELS):
+            got = run["crops"][n, l]
+            assert set(np.unique(got).tolist()) <= {0, 255}, what
+            bad = np.argwhere(((got[:H, :W] == 255) != fr["masks"][l]) & ~fr["und_label"][l])
+            assert len(bad) == 0, f"{what} label {l}: {len(bad)} samples differ, first at (y, x) {bad[:5].tolist()}"
+            assert not got[H:].any() and not got[:, W:].any(), f"{what} label {l}: set outside the frame"
+
+
+@pytest.fixture(scope="module")
+def trims(run):
+    """The frames with alpha-tested cards (trim, clip_tex, swap), each alone, with the trim on (the default) and
+    off, a fresh context per switch value: the same exact images -> {(trim, f): (records, bin entries)} (the
+    counters tests/test_gpu_alpha_trim.py uses)."""
+    b = run["b"]
+    which = [f for f, fr in enumerate(b["frames"]) if fr["family"] in ("trim", "clip_tex") or fr["family"].startswith("swap")]
     work = {}
     old = os.environ.get("CSG_ALPHA_TRIM")
     for trim in (True, False):
@@ -131,6 +158,39 @@ def test_the_trim_engages_on_the_trim_family(run):
                 assert np.array_equal(out["instance"][0][ok], fr["ids"][ok]), (trim, f)
                 assert np.array_equal(out["rgb"][0][ok], fr["rgb"][ok]), (trim, f)
     for f in which:
-        print(f"{W}x{H} trim frame {f}: records {work[False, f][0]} -> {work[True, f][0]}, "
-              f"bin entries {work[False, f][1]} -> {work[True, f][1]}")
+        print(f'{run["W"]}x{run["H"]} {b["frames"][f]["family"]}/{b["frames"][f]["order"]}: records {work[False, f][0]} -> '
+              f"{work[True, f][0]}, bin entries {work[False, f][1]} -> {work[True, f][1]}")
+    return work
+
+
+def test_the_trim_engages_on_the_trim_family(run, trims):
+    """The trim family's frames alone, with the trim on (the default) and off: the same exact images, and
+    fewer bin entries with it on."""
+    which = [f for f, fr in enumerate(run["b"]["frames"]) if fr["family"] == "trim"]
+    assert len(which) == 2
+    work = trims
+    for f in which:
         assert work[True, f][0] <= work[False, f][0] and work[True, f][1] < work[False, f][1]
+
+
+def test_the_trim_leaves_clipped_cards_alone(run, trims):
+    """The alpha-tested cards across the near plane: the same exact images with the trim on and off, and the
+    same records and bin entries (a clipped triangle is never trimmed)."""
+    which = [f for f, fr in enumerate(run["b"]["frames"]) if fr["family"] == "clip_tex"]
+    assert len(which) == 2
+    work = trims
+    for f in which:
+        assert work[True, f] == work[False, f] and work[True, f][0] > 0
+
+
+def test_the_trim_follows_the_texture_table(run, trims):
+    """Texture tables on the cards of the swap family: the exact images with the trim on and off under every
+    table (the moved block's box must be the swapped texture's, not the authored one), and the trim still
+    engaged under the authored table, KEEP_TEXTURE and the table that changes RGB alone."""
+    which = [f for f, fr in enumerate(run["b"]["frames"]) if fr["family"].startswith("swap")]
+    assert len(which) == 14
+    work = trims
+    for f in which:
+        assert work[True, f][0] <= work[False, f][0] and work[True, f][1] <= work[False, f][1]
+        if run["b"]["frames"][f]["family"] in ("swap_id", "swap_keep", "swap_rgb"):
+            assert work[True, f][1] < work[False, f][1], run["b"]["frames"][f]["family"]

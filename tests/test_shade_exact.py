@@ -10,7 +10,12 @@ to a scratch copy) fails ``test_oracle_matches_the_exact_reference``; DESIGN.md
 centre's ``- 0.5``; ``(int)`` for ``floorf``; ``>=`` for ``>`` in the alpha test;
 drop ``+ 32768``; affine uv; ties to the larger uid; ``<`` for ``<=`` at 1/far;
 the normal's sign inverted; drop ``+ 127``; drop ``+ 0.5`` in q; and, beyond that
-list, a depth key without its low 5 bits (caught by cross_near alone).
+list, a depth key without its low 5 bits (caught by cross_near alone).  In the
+clip family: the intersection interpolated from the wrong end; the fan's second
+sub-triangle not drawn; the fan started at the last emitted vertex; ``<`` for
+``<=`` at 1/near; ``>`` for ``>=`` at W = near (with ``all_in``); the trivial
+reject in screen space; the normal's flip from the first sub-triangle's
+orientation.  In the swap family: the texture table ignored by the alpha test.
 """
 from fractions import Fraction as Fr
 
@@ -48,6 +53,16 @@ def test_reference_by_hand():
     assert s(0.5, 0.5)[0][0, 0] == 25
     # a weight of 1/256: 10 (255/256) + 20 (1/256) = 10.04 -> 10;  without + 32768 it would still be 10, so also 19.96 -> 20
     assert s(0.25 + 1 / 512, 0.75)[0][0, 0] == 10 and s(0.75 - 1 / 512, 0.75)[0][0, 0] == 20
+    # the near plane: W = 1, 1, -1 with the third vertex virtually 16 px to the right.  1 / W falls from 1 at x = 16 px
+    # to -1 at 32 px, so it is 2 = 1 / near 8 px to the left of the edge, where the two slanted edges, produced
+    # backwards by half their length, arrive: code 3, polygon v0, v1, I12, I20, tt = 1/4 on both crossings
+    c = sx.clip_exact(sx.tri([(4096, 1024), (4096, 3072), (8192, 2048)], (1.0, 1.0, -1.0)))
+    assert c["code"] == 3 and c["poly"] == [(4096, 1024), (4096, 3072), (2048, 3584), (2048, 512)]
+    assert c["tt"] == [0.25, 0.75] and all(c["tt_exact"]) and len(c["subs"]) == 2
+    cov = sx.cover_of(sx.tri([(4096, 1024), (4096, 3072), (8192, 2048)], (1.0, 1.0, -1.0)), 32, 16)
+    assert cov[7, 8:16].all() and not cov[7, :8].any() and not cov[7, 16:].any() and cov[2, 8] and not cov[1, 8] and cov[13, 8]
+    c = sx.clip_exact(sx.tri([(4096, 1024), (4096, 3072), (8192, 2048)], (0.5, 1.0, 0.25)))     # W = near is inside: tt = 1 into it
+    assert c["code"] == 3 and c["tt"][1] == 1.0 and c["poly"][3] == c["poly"][0] and sx.area2(c["subs"][1]) == 0
 
 
 def _frames(size):
@@ -98,6 +113,8 @@ def test_conditions_of_the_reference(size):
                 assert np.array_equal(fr[key], prev[key]), (what, key)
             assert np.array_equal(fr["depth"].view(np.uint32), prev["depth"].view(np.uint32))
             assert all(sx.area2(t["xy"]) == -sx.area2(p["xy"]) for (_, _, ts), (_, _, ps) in zip(fr["insts"], prev["insts"])
+                       for t, p in zip(ts, ps) if "clip0" not in t)       # (a vertex of W = 0 has no screen position:)
+            assert all(sx.det_exact(t) == -sx.det_exact(p) != 0 for (_, _, ts), (_, _, ps) in zip(fr["insts"], prev["insts"])
                        for t, p in zip(ts, ps))
         # the normal's sign: facing the camera is "flipped iff det > 0", in both orders, and both occur
         flips = [d["shade"]["flipped"] for d in fr["drawn"]]
@@ -190,3 +207,193 @@ def test_ties_and_alpha_decide_the_winner(size):
         assert (win[i4 & ~i3] == first + 4).sum() > 5
         # (d): instance 5 (alpha-tested, holes) in front of its duplicate 6, which shows through the holes
         assert (win == first + 5).sum() > 10 and (win == first + 6).sum() > 10
+
+
+def _tagged(fr, tag):
+    """[(instance index in the frame, triangle index, label, triangle)] of the triangles built for ``tag``."""
+    return [(i, k, l, t) for i, (l, _, tris) in enumerate(fr["insts"]) for k, t in enumerate(tris) if t.get("tag") == tag]
+
+
+def _wins(fr, i, k):
+    return fr["uid"] == (((fr["first"] + i) << 20) | k)
+
+
+@pytest.mark.parametrize("size", SIZES)
+def test_the_clip_family_holds_its_cases(size):
+    """Near-clipped triangles: every case the family is built for occurs in the generated frames."""
+    W, H, b, _ = _frames(size)
+    frames = [fr for fr in b["frames"] if fr["family"].startswith("clip")]
+    assert [(fr["family"], fr["order"]) for fr in frames] == [(n, o) for n in ("clip", "clip_edge", "clip_tex", "clip_pair")
+                                                                      for o in (0, 1)]
+    near = Fr(sx.NEAR)
+    owed = 0
+    seen = {}                                       # (code, det > 0) -> kinds of outside vertices seen
+    for fr in frames:
+        what = f'{W}x{H} {fr["family"]}/{fr["order"]}'
+        if fr["family"] != "clip_tex":
+            assert not fr["undecided"].any(), what                  # untextured: nothing is left out
+        owed += int(fr["clip_win"].sum()) if fr["order"] == 0 else 0
+        flips = [d["shade"]["flipped"] for d in fr["drawn"] if d["n_won"]]
+        assert any(flips) and not all(flips), what
+        on_clipped = sum(bool(fr["clip_win"][int(v), int(u)]) for (u, v), vis in zip(fr["kp_uv"][:4], fr["kp_vis"][:4]) if vis)
+        assert on_clipped >= 2, what                                # keypoints at and just behind a clipped surface
+        per_code = {}
+        for i, (_, _, tris) in enumerate(fr["insts"]):
+            for k, t in enumerate(tris):
+                if not sx.is_clipped(t):
+                    continue
+                c = sx.clip_exact(t)
+                assert c is not None, what
+                code = c["code"]
+                assert len(c["subs"]) == {0: 0, 1: 1, 2: 1, 4: 1, 3: 2, 5: 2, 6: 2}[code], what
+                assert all(abs(x) < sx.CLIP_GUARD and abs(y) < sx.CLIP_GUARD for x, y in c["poly"]), what
+                if not _wins(fr, i, k).any():
+                    continue
+                per_code[code] = per_code.get(code, 0) + 1
+                out = [w for w in t["w"] if w < sx.NEAR]
+                kind = "front" if all(w > 0 for w in out) else "behind" if all(w < 0 for w in out) else "mixed"
+                seen.setdefault((code, sx.det_exact(t) > 0), set()).add(kind)
+        if fr["family"] == "clip":
+            assert all(per_code.get(c, 0) >= 2 for c in (1, 2, 4, 3, 5, 6)), (what, per_code)
+            assert fr["aims"]["w_ratio"] >= 32.0, what
+    print(f"{W}x{H}: {owed} pixels won by clipped triangles; inside masks and orientations {sorted(seen)}; "
+          f'{b["undecided_clips"]} candidates with an undecided clip vertex, W = 0 found after {b["w0_searched"]}')
+    assert owed >= (1500 if (W, H) == (96, 64) else 600)
+    for code in (1, 2, 4, 3, 5, 6):                                 # each mask in both orientations, outside in front and behind
+        assert (code, True) in seen and (code, False) in seen, (code, seen)
+        assert {"front", "behind"} <= seen[code, True] | seen[code, False], (code, seen)
+
+    fr = frames[0]                                                  # clip / 0
+    first_deg = second_deg = 0
+    for i, k, _, t in _tagged(fr, "near_vertex"):                   # a vertex at exactly W = near, one other outside
+        c = sx.clip_exact(t)
+        assert sx.NEAR in t["w"] and len(c["subs"]) == 2 and (0.0 in c["tt"] or 1.0 in c["tt"])
+        deg = [sx.area2(s) == 0 for s in c["subs"]]
+        assert sum(deg) == 1 and sx.plane_z(t, W, H)[1].sum() >= 10     # one is dropped, the other drawn
+        first_deg, second_deg = first_deg + deg[0], second_deg + deg[1]
+    assert first_deg >= 2 and second_deg >= 2 and any(1.0 in sx.clip_exact(t)["tt"] for _, _, _, t in _tagged(fr, "near_vertex"))
+    (_, _, _, t), = _tagged(fr, "near_alone")                       # both others outside: three times the same vertex
+    assert len(set(sx.clip_exact(t)["poly"])) == 1 and not sx.cover_of(t, W, H).any()
+    (i, k, _, t), = _tagged(fr, "near_flat")                        # all three at W = near: inside, drawn, 1 / W = 2 kept
+    assert set(t["w"]) == {sx.NEAR} and _wins(fr, i, k).sum() >= 20 and fr["aims"]["z_near_exact"] >= 20
+    (_, _, l, t), = _tagged(fr, "invisible")
+    assert sorted(t["w"]) == [-2.0, -1.0, -1.0] and l == 5
+    assert fr["covered"][5] == 0 and not fr["masks"][5].any() and not fr["beyond"][5].any() and not (fr["ids"] == 5).any()
+
+    fr = frames[2]                                                  # clip_edge / 0
+    assert fr["aims"]["z_near_exact"] >= 20
+    for axis in "xy":
+        for kind in ("incl", "excl"):
+            hit = 0
+            for i, k, _, t in _tagged(fr, f"edge_{axis}_{kind}"):
+                N, _, _, pq = sx._grid_ints(t, W, H)
+                line = (N << (sx.PQ - pq)) == sx.Z_NEAR             # the centres with 1 / W = 2 exactly: one column or row
+                cov = sx.cover_of(t, W, H)
+                ax = 0 if axis == "x" else 1                        # (the axis of the image the line runs along)
+                assert line.any() and (line.all(ax) | ~line.any(ax)).all() and line.any(ax).sum() == 1
+                assert all(sx.clip_exact(t)["tt_exact"])
+                if kind == "incl":                                  # a left / top edge: its centres are covered, and kept by <=
+                    assert (cov & line).sum() >= 5 and (_wins(fr, i, k) & line).any()
+                else:                                               # a right / bottom edge: they are not, their neighbours are
+                    assert not (cov & line).any() and (cov & np.roll(line, -1, 1 - ax)).sum() >= 5
+                hit += 1
+            assert hit >= 2, (axis, kind)
+    fx = lambda t: [v[0] for v in t["xy"]]                          # noqa: E731
+    (i, k, _, t), = _tagged(fr, "hom_sides")                        # virtual vertices left of, right of and above the frame
+    assert min(fx(t)) < 0 and max(fx(t)) > W * 256 and min(v[1] for v in t["xy"]) < 0 and min(t["w"]) < 0
+    assert all(not (0 <= x <= W * 256 and 0 <= y <= H * 256) for x, y in t["xy"]) and _wins(fr, i, k).sum() >= 100
+    (i, k, _, t), = _tagged(fr, "hom_above")                        # all three above it: a reject in screen space would take it
+    assert all(y < 0 for _, y in t["xy"]) and min(t["w"]) < 0 and _wins(fr, i, k).sum() >= 20
+    for tag in ("hom_sides", "hom_above"):                          # item 2's reject, in rationals, keeps both
+        v = sx._clip_space(_tagged(fr, tag)[0][3])
+        assert not any(all(f(p) for p in v) for f in (lambda p: p[2] < near, lambda p: p[2] > Fr(sx.FAR), lambda p: p[0] < 0,
+                                                      lambda p: p[0] > W * p[2], lambda p: p[1] < 0, lambda p: p[1] > H * p[2]))
+    w0 = _tagged(fr, "w0")                                          # a vertex with W = 0 (the seeded search finds them)
+    assert len(w0) >= 1 and all(0.0 in t["w"] and "clip0" in t for _, _, _, t in w0)
+    assert sum(int(_wins(fr, i, k).sum()) for i, k, _, _ in w0) >= 10
+
+    fr = frames[4]                                                  # clip_tex / 0
+    a = fr["aims"]
+    assert a["alpha_tested"] >= 100 and 0 < a["alpha_killed"] < a["alpha_tested"] and a["textured"] > a["alpha_tested"]
+    cards = _tagged(fr, "card")
+    assert len(cards) == 4 and all(sx.is_clipped(t) and t["uv"] is not None for _, _, _, t in cards)
+    for i in sorted({i for i, _, _, _ in cards}):                   # per card: two triangles, one texture
+        l, m, tris = fr["insts"][i]
+        mt = b["scene"].materials[m]
+        tex = b["scene"].textures[mt.texture].rgba
+        cols = np.nonzero((tex[..., 3] == 255).any(0))[0].tolist()
+        assert mt.alpha_test and (tex[..., 3] == 255).sum() == 8 and len(cols) == 4 and cols[1] == cols[0] + 1 and cols[3] == cols[2] + 1
+        vis, cut = cols[0], cols[2]                                 # two 2 x 2 blocks: columns vis, vis + 1 and cut, cut + 1
+        tx, _, alpha = (np.concatenate(x) for x in zip(*(sx.texels_of(t, tex, W, H) for t in tris)))
+        drawn = alpha > mt.alpha_threshold
+        print(f"{W}x{H} card {i}: texel columns {int(tx.min())} .. {int(tx.max())} read, {sorted(set(tx[drawn].tolist()))} drawn, "
+              f"blocks at {vis} and {cut}")
+        assert drawn.sum() >= 10 and set(tx[drawn].tolist()) <= {vis - 1, vis, vis + 1}      # the visible side's block is drawn,
+        assert tx.max() + 1 < cut < 10 and tx.min() >= -1           # the other, on the card but beyond the clip line, is never read
+        assert fr["masks"][l].any()
+    assert all(sx.is_clipped(t) for _, m, ts in fr["insts"] for t in ts if b["scene"].materials[m].alpha_test)   # none to trim
+    fr = frames[6]                                                  # clip_pair / 0
+    for tag, both_clipped in (("pair_cc", True), ("pair_cu", False)):
+        (ia, ka, la, ta), (ib, kb, lb, tb) = _tagged(fr, tag)
+        assert la != lb and sx.is_clipped(ta) and sx.is_clipped(tb) == both_clipped
+        (_, ra, _), (_, rb, _) = sx.plane_z(ta, W, H), sx.plane_z(tb, W, H)
+        common = ra & rb                                            # in range under both: inside the clipped region of ta
+        wa, wb = int((_wins(fr, ia, ka) & common).sum()), int((_wins(fr, ib, kb) & common).sum())
+        print(f"{W}x{H} {tag}: {int(common.sum())} common pixels, won {wa} / {wb}")
+        assert wa >= sx.pair_need(H) and wb >= sx.pair_need(H), (tag, wa, wb)
+        assert (fr["ids"][common] == la).any() and (fr["ids"][common] == lb).any()
+
+
+@pytest.mark.parametrize("size", SIZES)
+def test_the_swap_family_holds_its_cases(size):
+    """Texture tables: the frames share their instances and differ in the table alone, and each table does
+    to the expected image what it is there for."""
+    W, H, b, _ = _frames(size)
+    sc = b["scene"]
+    for order in (0, 1):
+        fam = {fr["family"]: fr for fr in b["frames"] if fr["family"].startswith("swap") and fr["order"] == order}
+        assert set(fam) == {"swap_id", "swap_keep", "swap_rgb", "swap_alpha", "swap_4x4", "swap_npot", "swap_none"}
+        one = fam["swap_id"]
+        assert all((fr["first"], fr["count"], fr["light"]) == (one["first"], one["count"], one["light"]) and
+                   fr["insts"] is not None and [t for _, _, ts in fr["insts"] for t in ts] == [t for _, _, ts in one["insts"] for t in ts]
+                   for fr in fam.values())
+        tables = [tuple(fr["table"].tolist()) for fr in fam.values()]
+        assert len(set(tables)) == len(tables) == 7 and all(len(t) == len(sc.materials) for t in tables)
+        assert set(fam["swap_keep"]["table"].tolist()) == {sx.KEEP_TEXTURE}
+        base = sx.render(one["insts"], sc, b["lights"][0], W, H, W // 2, H // 2, one["first"])     # no table at all
+
+        def same(a, c, keys=("ids", "rgb", "normals", "masks", "undecided", "covered")):
+            return all(np.array_equal(a[k], c[k]) for k in keys) and np.array_equal(a["depth"].view(np.uint32), c["depth"].view(np.uint32))
+        assert same(one, base) and same(fam["swap_keep"], base)
+        ma = [m for m, mt in enumerate(sc.materials) if mt.alpha_test and one["table"][m] >= 0]
+        mo = [m for m, mt in enumerate(sc.materials) if not mt.alpha_test and one["table"][m] >= 0]
+        assert len(ma) == 1 and len(mo) == 1
+        ma, mo = ma[0], mo[0]
+        tex = lambda name, m: sc.textures[fam[name]["table"][m]].rgba      # noqa: E731
+        decided = lambda a, c: ~a["undecided"] & ~c["undecided"]           # noqa: E731
+        # other RGB, the same alpha: the same pixels are drawn, in other colours
+        r = fam["swap_rgb"]
+        assert np.array_equal(tex("swap_rgb", ma)[..., 3], tex("swap_id", ma)[..., 3]) and tex("swap_rgb", ma).shape == (8, 16, 4)
+        assert same(r, base, ("ids", "masks", "covered", "normals")) and ((r["rgb"] != base["rgb"]).any(-1) & decided(r, base)).sum() >= 20
+        # the opaque block elsewhere: other pixels are drawn
+        r = fam["swap_alpha"]
+        assert tex("swap_alpha", ma).shape == (8, 16, 4) and not np.array_equal(tex("swap_alpha", ma)[..., 3], tex("swap_id", ma)[..., 3])
+        moved = int(((r["ids"] != base["ids"]) & decided(r, base)).sum())
+        print(f"{W}x{H} swap_alpha/{order}: {moved} decided pixels change their id")
+        assert moved >= 20 and not np.array_equal(r["covered"], base["covered"])
+        # other sizes
+        assert tex("swap_4x4", ma).shape == (4, 4, 4) and tex("swap_npot", ma).shape == (7, 13, 4) and tex("swap_id", ma).shape == (8, 16, 4)
+        for name in ("swap_4x4", "swap_npot"):
+            r = fam[name]
+            assert r["aims"]["alpha_tested"] >= 200 and 0 < r["aims"]["alpha_killed"] < r["aims"]["alpha_tested"]
+            assert ((r["ids"] != base["ids"]) & decided(r, base)).sum() >= 20
+        # no texture on the opaque material: its pixels show the base colour alone, everything else stays
+        r = fam["swap_none"]
+        assert r["table"][mo] == -1 and same(r, base, ("ids", "masks", "covered", "normals"))
+        own = np.zeros((H, W), bool)
+        for i, (_, m, ts) in enumerate(r["insts"]):
+            for k in range(len(ts)):
+                own |= _wins(r, i, k) if m == mo else False
+        assert own.sum() >= 50 and np.array_equal(r["rgb"][~own], base["rgb"][~own]) and (r["rgb"][own] != base["rgb"][own]).any()
+        assert len({tuple(c) for c in r["rgb"][own].tolist()}) <= 2      # two triangles, one colour each
+        assert r["aims"]["textured"] < base["aims"]["textured"]
