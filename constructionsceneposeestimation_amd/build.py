@@ -17,8 +17,9 @@ ROOT = os.path.dirname(PKG)
 LIB = os.path.join(PKG, "libcsg.so")
 SOURCES = [os.path.join(PKG, "csrc", "csg_kernels.hip"), os.path.join(PKG, "csrc", "csg_encode.hip"),
            os.path.join(PKG, "csrc", "csg_crops.hip"), os.path.join(PKG, "csrc", "csg_spans.hip"),
-           os.path.join(PKG, "csrc", "csg_points.hip"), os.path.join(PKG, "csrc", "csg_amodal_spans.hip"), os.path.join(PKG, "csrc", "csg_api.cpp")]
-DEPS = SOURCES + [os.path.join(PKG, "csrc", "csg_kernels.h"), os.path.join(PKG, "csrc", "csg_encode.h"),
+           os.path.join(PKG, "csrc", "csg_points.hip"), os.path.join(PKG, "csrc", "csg_amodal_spans.hip"),
+           os.path.join(PKG, "csrc", "csg_api.cpp"), os.path.join(PKG, "csrc", "csg_passes.cpp")]
+DEPS = SOURCES + [os.path.join(PKG, "csrc", "csg_ctx.h"), os.path.join(PKG, "csrc", "csg_kernels.h"), os.path.join(PKG, "csrc", "csg_encode.h"),
                   os.path.join(PKG, "csrc", "csg_deflate.h"), os.path.join(PKG, "csrc", "csg_widen.h"),
                   os.path.join(PKG, "csrc", "csg_crops.h"), os.path.join(PKG, "csrc", "csg_spans.h"),
                   os.path.join(PKG, "csrc", "csg_points.h"),

@@ -1,5 +1,5 @@
 // csg_amodal_spans.h — host launcher of the full-frame amodal span kernels
-// (csg_amodal_spans.hip), called by csg_api.cpp for csg_amodal_spans.
+// (csg_amodal_spans.hip), called by csg_passes.cpp for csg_amodal_spans.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -5,62 +5,20 @@
 // for `max_frames`, and the launch sequence of csg_kernels.hip.  All
 // validation that protects the GPU from out-of-bounds indices happens here,
 // on the host, before anything is uploaded.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
-#include <cstddef>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <map>
 #include <memory>
-#include <string>
 #include <utility>
-#include <vector>
 
-#include "../../include/csg_api.h"
 #include "csg_alpha_box.h"
-#include "csg_amodal_spans.h"
-#include "csg_crops.h"
-#include "csg_encode.h"
-#include "csg_kernels.h"
-#include "csg_points.h"
-#include "csg_spans.h"
+#include "csg_ctx.h"
 #include "csg_widen.h"
 
 using namespace csg;
-
-namespace {
-
-// A device allocation owned by one object: freed by release() or at the end
-// of its scope (a local scratch buffer cannot leak on an early error return).
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { release(); }
-  hipError_t alloc(size_t count) {
-    if (count <= n && p) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-    if (count == 0) return hipSuccess;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T));
-    if (e == hipSuccess) n = count;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-};
 
 // Default frames per launch chain: the whole batch.  Measured on C3 (1080p,
 // 60 frames): chains of 2/4/8/20 frames cost 3.7x/2.0x/1.6x/1.3x the time of
@@ -74,240 +32,9 @@ constexpr uint32_t kAutoChainFrames = 0xFFFFFFFFu;
 // frames per step uses 7,200 epochs on one rank.
 constexpr uint32_t kMaxSets = 65536;
 
-struct HostTexture {
-  std::vector<uint8_t> rgba;
-  uint32_t w = 0, h = 0;
-  bool present = false;
-};
-
-}  // namespace
-
-struct csg_ctx {
-  csg_config cfg{};
-  std::string err;
-  hipStream_t stream = nullptr;
-  uint32_t tiles_x = 0, tiles_y = 0, n_tiles = 0;
-
-  // scene
-  bool have_scene = false;
-  uint32_t n_inst = 0, n_meshes = 0, n_materials = 0;
-  uint64_t n_tris_total = 0;
-  DevBuf<float> tri_pos, tri_uv;       // de-indexed triangle soup (see SceneDev)
-  // Alpha trim (csg_alpha_box.h): one opaque uv box per soup triangle, built by sync_scene_state from the
-  // mesh's authored alpha texture and threshold (h_abox_tex: that texture per mesh, -1: no box built).
-  // CSG_ALPHA_TRIM=0 uploads "full" boxes and sets no InstSetDev::trim: nothing is trimmed (A/B, tests).
-  DevBuf<float> abox;                   // [T][4] u_lo u_hi v_lo v_hi
-  std::vector<float> h_tri_uv;          // host copy of tri_uv (the boxes are rebuilt when textures change)
-  std::vector<int32_t> h_abox_tex;      // per mesh
-  bool alpha_trim = true;
-  DevBuf<InstDesc> inst;
-  std::vector<MatDesc> h_mats;
-  std::vector<MatDesc> h_set_mats;      // [sets][n_materials] as uploaded
-  std::vector<MeshDesc> h_meshes;
-  DevBuf<Chunk> chunks;
-  uint32_t n_chunks = 0;
-  uint32_t uid_shift = kUidShift;       // SceneDev::uid_shift
-  std::vector<HostTexture> textures;
-  bool tex_dirty = true;
-  DevBuf<uint8_t> texels;
-  DevBuf<uint32_t> aquad;
-  DevBuf<uint32_t> acls;                // alpha-test class of each alpha quad (see build_alpha_classes)
-  std::vector<int> acls_thr;            // per texture: the threshold acls was built for
-  DevBuf<TexDesc> texd;
-  LightDev light{{0.26f, 0.29f, 0.34f}, {0.78f, 0.78f, 0.78f}, {0.7071f, 0.f, 0.7071f},
-                 191u | (217u << 8) | (255u << 16)};   // default (csg_set_light)
-  // domain randomisation per transform set (csg_set_dr_light / csg_set_dr_textures)
-  std::vector<LightDev> dr_light;
-  std::vector<uint8_t> dr_light_valid;
-  std::vector<int32_t> dr_tex;          // [sets][n_materials]; kKeepTexture = the material's own
-  bool dr_dirty = true;
-  DevBuf<LightDev> lights;
-  DevBuf<MatDesc> set_mats;
-  uint32_t n_table_sets = 0;
-  std::vector<float> h_models;          // [sets][I][16]
-  std::vector<uint8_t> set_valid;
-  DevBuf<float> models;
-  bool models_dirty = true;
-  uint32_t n_kp = 0;
-  std::vector<float> h_kp;              // [sets][K][3]
-  std::vector<uint8_t> kp_valid;
-  DevBuf<float> kp;
-  bool kp_dirty = true;
-  // object frames (csg_set_object_frames): per set and label a 3x4 world -> unit-box matrix
-  uint32_t n_lab = 1;                   // label-table length: largest instance label + 1, at least 1
-  std::vector<float> h_of;              // [sets][n_lab][12], zeros where never set
-  uint32_t of_sets = 0;                 // sets h_of holds
-  DevBuf<float> of;                     // [of_table_sets][n_lab][12] (sync_object_frames)
-  uint32_t of_table_sets = 0;
-  bool of_dirty = true;
-
-  // per-batch work buffers: record and bin pools shared by the frames of a
-  // launch chain, each frame's region (Slab) planned by k_plan from its hints
-  // or the per-frame caps rec_cap / bin_cap
-  uint32_t rec_cap = 0, bin_cap = 0, work_frames = 0;
-  uint64_t rec_pool = 0, bin_pool = 0;            // pool entries allocated
-  bool use_hints = false;                         // csg_size_work sized the pools from frame hints
-  uint32_t hint_fallbacks = 0;                    // re-renders the hinted pools caused (csg_work_info)
-  uint64_t plan_rec_pool = 0, plan_bin_pool = 0;  // ... to these
-  DevBuf<Slab> slab;                              // [chain frames] (k_plan)
-  DevBuf<uint64_t> plan_need;                     // [2] pool entries the batch's largest chain asked for (k_plan)
-  DevBuf<FrameDev> frames;
-  // Pinned staging ring for host frame records: a batch's records are copied
-  // into the next slot, and a slot is reused only after the H2D copy that read
-  // it has completed (its event), so back-to-back async batches never render
-  // each other's cameras.
-  static constexpr uint32_t kStaging = 4;
-  FrameDev* h_stage[kStaging] = {};
-  hipEvent_t stage_ev[kStaging] = {};
-  bool stage_busy[kStaging] = {};
-  uint32_t stage_next = 0;
-  // The stream of the most recent enqueue.  The work buffers are shared, so a
-  // batch on a different stream first waits for the previous stream to drain;
-  // csg_synchronize waits on it.
-  hipStream_t last_stream = nullptr;
-  DevBuf<uint32_t> fset;                // [chain frames] checked transform set of each frame (k_clip)
-  DevBuf<float> clip, pv;
-  DevBuf<Rec> recs;
-  DevBuf<uint32_t> rect, rec_count, tile_count, tile_off, bins, overflow;
-  DevBuf<uint32_t> bcount;              // [chain frames][bin_blocks][n_tiles] count grid
-  DevBuf<InstSetDev> iset;              // [n_table_sets][n_inst] resolved materials (sync_scene_state)
-  std::vector<InstDesc> h_inst;         // host copy of the instance table
-  // internal outputs (host-output mode / scratch)
-  DevBuf<uint8_t> o_rgb;
-  DevBuf<int32_t> o_inst;
-  DevBuf<float> o_depth, o_kp_uv, kp_w, o_points, cam;
-  DevBuf<uint16_t> o_normals;
-  DevBuf<uint16_t> o_objc;              // object coordinates (host-output mode)
-  DevBuf<int32_t> o_kp_vis;
-  DevBuf<uint32_t> kp_pix, kp_tiles;
-  DevBuf<uint32_t> o_stats;
-  DevBuf<uint8_t> o_dvis;               // depth visualisation (host-output mode)
-  DevBuf<float> o_drange;
-  DevBuf<uint32_t> o_cov;               // label coverage (host-output mode)
-  DevBuf<uint32_t> drange;              // [2][chain frames] min / max depth bits (k_raster's resolve)
-  DevBuf<uint32_t> jet;                 // JET colour map, 256 x (r | g << 8 | b << 16)
-  // images of the last batch (for the file encoders) and the encoders' buffers
-  const uint8_t* last_rgb = nullptr;
-  const float* last_depth = nullptr;
-  const float* last_points = nullptr;
-  const uint8_t* last_dvis = nullptr;
-  DevBuf<EncPng> enc_rgb, enc_dpng, enc_d16;
-  DevBuf<uint2> enc_rowsum;
-  DevBuf<uint32_t> enc_rows_rgb, enc_rows_dpng, enc_rows_csv, enc_rows_pcd, enc_rows_d16, enc_rows_ply, enc_ply_n;
-  DevBuf<uint8_t> enc_d16img;           // [F][H][W] big-endian 16-bit depth samples
-  DevBuf<uint64_t> enc_fsize, enc_foff, enc_zoff;
-  DevBuf<uint8_t> enc_zbuf, enc_out;
-  DevBuf<uint8_t> dstat_part;           // depth-statistics partial sums
-  DevBuf<double> o_dstats;              // depth statistics (host-output mode)
-  float depth16_scale = 250.0f;         // counts per metre of the batch's 16-bit depth PNGs
-  uint64_t enc_total = 0;               // bytes of the last batch's files (0: none)
-  uint32_t enc_nfiles = 0;
-  std::vector<uint64_t> h_foff;
-
-  // timing: ring of per-batch event quintuples (recorded, never waited on in the loop)
-  bool timing = true;
-  static constexpr uint32_t kRing = 4096;
-  std::vector<hipEvent_t> ring;         // kRing * 5
-  std::vector<uint32_t> ring_frames;
-  uint64_t ring_count = 0;
-  hipEvent_t* ev = nullptr;             // events of the most recent batch
-  uint32_t last_F = 0;
-  uint32_t dbg = 0;                     // CSG_DEBUG ablation bits (profiling builds of the pipeline only)
-  // k_count / k_bin workgroups per frame (CSG_BINBLOCKS: A/B only; set in
-  // csg_create from the tile count).  16 at 1080p's 4,080 tiles of 32 x 16
-  // keeps the [blocks][tiles] count grid the size 32 blocks gave 32 x 32 tiles
-  // (C3: binning 2.27 vs 2.69 ms per 960 frames with 16 vs 32 blocks; at 2,880
-  // frames per step 8 / 16 / 24 blocks: binning 5.8 / 6.2 / 6.3 ms, k_raster
-  // 97.3 / 97.1 / 96.9 ms); 8 above 8,192 tiles (C5 at 4K, 16,200 tiles, 480
-  // frames: binning 4.3 / 4.7 / 4.4 / 5.2 ms with 8 / 16 / 4 / 2 blocks;
-  // profiles/r05/ab/tile_shape.md)
-  uint32_t bin_blocks = 32;
-  uint32_t chain_frames = 0;            // frames per launch chain (cfg.frames_per_launch; CSG_CHAIN overrides)
-  // Host outputs: each launch chain's slice is copied to the host on copy_stream
-  // while the next chains render (created with the first host-output batch).
-  static constexpr uint32_t kCopyEv = 16;
-  hipStream_t copy_stream = nullptr;
-  hipEvent_t copy_ev[kCopyEv] = {};
-  hipEvent_t copy_done = nullptr;
-  // The host wire of the instance ids (csg_widen.h): a host-output batch's ids
-  // cross PCIe as (id + 1) in ids_bytes (1 with at most 255 labels, 2 with at
-  // most 65,535; 4 = int32 as rendered, no narrowing) and are widened to the
-  // caller's int32 by WidenPool threads while later chains render.
-  // CSG_NARROW_IDS=0 keeps int32 on the wire (A/B, tests).
-  uint32_t ids_bytes = 4;               // set by csg_upload_scene from the label range
-  bool narrow_ids = true;
-  bool split_pageable = true;           // CSG_SPLIT_PAGEABLE=0: pageable host outputs as one chain (A/B, tests)
-  DevBuf<uint8_t> o_ids_n;              // [F][H][W] narrowed ids (device)
-  uint8_t* h_ids_n = nullptr;           // ... their pinned host landing buffer
-  size_t h_ids_n_bytes = 0;
-  // Amodal crop masks (csg_crop_amodal).  The label -> chunks table is built with the scene.  The pass has
-  // scratch of its own, grown to the job and never shared with a render: device copies of the frame
-  // records and the bit image, and a pinned staging ring for the host records (a slot is reused only
-  // after its H2D copy has completed).  am_done marks the end of the last pass: a pass on another
-  // stream waits for it on the device, a reallocation on the host.
-  DevBuf<uint32_t> lab_off, lab_chunks;   // [n_lab + 1], [chunks that carry a label >= 0]
-  uint32_t lab_max_chunks = 0;            // the most chunks one label has
-  DevBuf<FrameDev> am_frames;
-  DevBuf<uint32_t> am_bits;
-  DevBuf<uint32_t> am_keys;               // csg_crop_amodal_geometry without a depth output: the key image
-  FrameDev* am_stage[kStaging] = {};
-  size_t am_stage_n[kStaging] = {};
-  hipEvent_t am_stage_ev[kStaging] = {};
-  uint32_t am_stage_next = 0;
-  hipEvent_t am_done = nullptr;
-  hipStream_t am_stream = nullptr;
-  bool am_busy = false;
-  // Full-frame amodal spans (csg_amodal_spans): host copies of the label -> chunks table (the item list
-  // of a job is built from them and the job's `eligible`), and the pass's scratch under am_done's
-  // ordering: the bit planes of one frame range, their "touched" words, the span counts, and the item
-  // and label -> plane tables with their pinned staging (as_stage_ev: the slot's last H2D copy).
-  std::vector<uint32_t> h_lab_off, h_lab_chunks;
-  DevBuf<uint32_t> as_planes, as_touched, as_cnt, as_tables;
-  uint32_t* as_stage = nullptr;
-  size_t as_stage_n = 0;
-  hipEvent_t as_stage_ev = nullptr;
-  // Mask spans (csg_mask_spans): the pass's own scratch, the span counts [n][L][groups of 64 columns],
-  // grown to the job; ms_done orders passes on different streams as am_done does the amodal passes.
-  DevBuf<uint32_t> ms_cnt;
-  hipEvent_t ms_done = nullptr;
-  hipStream_t ms_stream = nullptr;
-  bool ms_busy = false;
-  // Object points (csg_sample_object_points): the pass's own scratch, the pixel counts [n][L][chunks] and
-  // the totals [n][L] behind them, grown to the job; op_done orders passes on different streams as ms_done does.
-  DevBuf<uint32_t> op_cnt;
-  hipEvent_t op_done = nullptr;
-  hipStream_t op_stream = nullptr;
-  bool op_busy = false;
-  // csg_keep_instance / csg_last_instance: host-output batches keep their ids on the device
-  bool keep_ids = false;
-  const int32_t* last_inst = nullptr;
-  uint32_t last_inst_frames = 0;
-  // the last sizing pass (csg_size_work)
-  uint32_t sized_frames = 0, sized_max_rec = 0, sized_max_bin = 0;
-  double sized_mean_rec = 0.0, sized_mean_bin = 0.0;
-
-  int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    err = buf;
-    return code;
-  }
-};
-
-#define HIP_TRY(ctx, expr)                                                                           \
-  do {                                                                                               \
-    hipError_t _e = (expr);                                                                          \
-    if (_e != hipSuccess)                                                                            \
-      return (ctx)->fail(_e == hipErrorOutOfMemory ? CSG_ERR_OOM : CSG_ERR_DEVICE, "%s: %s", #expr,  \
-                         hipGetErrorString(_e));                                                     \
-  } while (0)
-
 // Wait for everything this context enqueued, on its own stream and on the
 // caller's stream of the most recent batch.
-static int drain(csg_ctx* c) {
+int csg::drain(csg_ctx* c) {
   if (c->last_stream && c->last_stream != c->stream) HIP_TRY(c, hipStreamSynchronize(c->last_stream));
   if (c->stream) HIP_TRY(c, hipStreamSynchronize(c->stream));
   return CSG_OK;
@@ -399,8 +126,6 @@ int csg_create(const csg_config* cfg, csg_ctx** out) {
   c->ring.assign((size_t)csg_ctx::kRing * 5, nullptr);
   c->ring_frames.assign(csg_ctx::kRing, 0);
   for (size_t k = 0; k < c->ring.size() && e == hipSuccess; ++k) e = hipEventCreate(&c->ring[k]);
-  for (uint32_t k = 0; k < csg_ctx::kStaging && e == hipSuccess; ++k)
-    e = hipEventCreateWithFlags(&c->stage_ev[k], hipEventDisableTiming);
   // the overflow / error word lives as long as the context: it is sticky across
   // asynchronous batches and cleared only when csg_synchronize or
   // csg_render_batch has read it
@@ -422,6 +147,8 @@ int csg_create(const csg_config* cfg, csg_ctx** out) {
   return CSG_OK;
 }
 
+// Everything the context owns but the streams and the timing ring frees itself (DevBuf, PinnedBuf, Event)
+// once nothing on the device can still use it.
 void csg_destroy(csg_ctx* c) {
   if (!c) return;
   if (c->last_stream && c->last_stream != c->stream) (void)hipStreamSynchronize(c->last_stream);
@@ -429,49 +156,13 @@ void csg_destroy(csg_ctx* c) {
   // (every batch's stream waits for its copies and id widening on the copy
   // stream, copy_done; synchronized here too before the buffers they read go)
   if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
-  c->tri_pos.release(); c->tri_uv.release(); c->abox.release(); c->inst.release(); c->set_mats.release(); c->iset.release(); c->lights.release();
-  c->chunks.release();
-  c->texels.release();
-  c->aquad.release();
-  c->acls.release();
-  c->texd.release(); c->models.release(); c->kp.release(); c->frames.release(); c->clip.release();
-  c->pv.release(); c->recs.release(); c->rect.release(); c->rec_count.release(); c->tile_count.release();
-  c->slab.release(); c->plan_need.release();
-  c->tile_off.release(); c->bins.release(); c->bcount.release(); c->overflow.release(); c->o_rgb.release();
-  c->o_inst.release(); c->o_depth.release(); c->o_kp_uv.release(); c->o_kp_vis.release(); c->o_stats.release();
-  c->kp_w.release(); c->kp_pix.release(); c->kp_tiles.release();
-  c->o_points.release(); c->o_normals.release(); c->cam.release(); c->fset.release();
-  c->of.release(); c->o_objc.release();
-  c->o_dvis.release(); c->o_drange.release(); c->o_cov.release(); c->drange.release(); c->jet.release();
-  for (uint32_t k = 0; k < csg_ctx::kStaging; ++k) {
-    if (c->h_stage[k]) (void)hipHostFree(c->h_stage[k]);
-    if (c->stage_ev[k]) (void)hipEventDestroy(c->stage_ev[k]);
-  }
-  if (c->am_busy) (void)hipEventSynchronize(c->am_done);   // a pass on a stream of the caller's
-  c->lab_off.release(); c->lab_chunks.release(); c->am_frames.release(); c->am_bits.release(); c->am_keys.release();
-  for (uint32_t k = 0; k < csg_ctx::kStaging; ++k) {
-    if (c->am_stage[k]) (void)hipHostFree(c->am_stage[k]);
-    if (c->am_stage_ev[k]) (void)hipEventDestroy(c->am_stage_ev[k]);
-  }
-  c->as_planes.release(); c->as_touched.release(); c->as_cnt.release(); c->as_tables.release();
-  if (c->as_stage) (void)hipHostFree(c->as_stage);
-  if (c->as_stage_ev) (void)hipEventDestroy(c->as_stage_ev);
-  if (c->am_done) (void)hipEventDestroy(c->am_done);
-  if (c->ms_busy) (void)hipEventSynchronize(c->ms_done);   // a span pass on a stream of the caller's
-  c->ms_cnt.release();
-  if (c->ms_done) (void)hipEventDestroy(c->ms_done);
-  if (c->op_busy) (void)hipEventSynchronize(c->op_done);   // a point pass on a stream of the caller's
-  c->op_cnt.release();
-  if (c->op_done) (void)hipEventDestroy(c->op_done);
-  for (auto& e : c->ring)
-    if (e) (void)hipEventDestroy(e);
-  if (c->h_ids_n) (void)hipHostFree(c->h_ids_n);
-  c->o_ids_n.release();
-  for (auto& e : c->copy_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (c->copy_done) (void)hipEventDestroy(c->copy_done);
+  (void)c->am.wait_host(c);   // passes on streams of the caller's
+  (void)c->ms.wait_host(c);
+  (void)c->op.wait_host(c);
   if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
   if (c->stream) (void)hipStreamDestroy(c->stream);
+  for (auto& e : c->ring)
+    if (e) (void)hipEventDestroy(e);
   delete c;
 }
 
@@ -482,11 +173,8 @@ int csg_upload_scene(csg_ctx* c, const csg_mesh* meshes, uint32_t n_meshes, cons
     return c->fail(CSG_ERR_INVALID, "upload_scene: empty scene");
   if (n_inst >= kMaxInstances) return c->fail(CSG_ERR_LIMIT, "upload_scene: %u instances >= %u", n_inst, kMaxInstances);
   HIP_TRY(c, hipSetDevice(c->cfg.device));
-  {  // batches in flight read the scene and the work buffers this replaces
-    const int rc = drain(c);
-    if (rc) return rc;
-    if (c->am_busy) HIP_TRY(c, hipEventSynchronize(c->am_done));   // so does an amodal pass on any stream
-  }
+  CSG_TRY(drain(c));              // batches in flight read the scene and the work buffers this replaces
+  CSG_TRY(c->am.wait_host(c));    // so does an amodal pass on any stream
   std::vector<float> pos, uvs;
   std::vector<uint32_t> tris, uvt;
   std::vector<MeshDesc> md(n_meshes);
@@ -827,14 +515,13 @@ static bool same_alpha(const csg_ctx* c, int a, int b) {
   return true;
 }
 
-static int sync_scene_state(csg_ctx* c) {
+extern "C++" int csg::sync_scene_state(csg_ctx* c) {   // (csg_ctx.h; C++ linkage inside the extern "C" block)
   const uint32_t n_sets = (uint32_t)c->set_valid.size();
   if (c->tex_dirty || c->dr_dirty || c->models_dirty || (c->kp_dirty && c->n_kp) || c->n_table_sets != n_sets) {
     // the device tables are rewritten (and may be reallocated) below: batches
     // in flight still read them
-    const int rc = drain(c);
-    if (rc) return rc;
-    if (c->am_busy) HIP_TRY(c, hipEventSynchronize(c->am_done));   // so does an amodal pass, on any stream
+    CSG_TRY(drain(c));
+    CSG_TRY(c->am.wait_host(c));   // so does an amodal pass, on any stream
   }
   const bool tex_changed = c->tex_dirty;
   const bool iset_dirty = c->tex_dirty || c->dr_dirty || c->n_table_sets != n_sets || !c->iset.p;
@@ -965,12 +652,11 @@ static int sync_scene_state(csg_ctx* c) {
 // one row block per transform set (the sets k_clip lets through, b.n_sets), so
 // b.fset indexes it; sets without a table -- and sets past the transform sets,
 // which no frame can name -- hold zeros.
-static int sync_object_frames(csg_ctx* c) {
+extern "C++" int csg::sync_object_frames(csg_ctx* c) {
   const uint32_t n_sets = (uint32_t)c->set_valid.size();
   if (!c->of_dirty && c->of_table_sets == n_sets && c->of.p) return CSG_OK;
-  const int rc = drain(c);   // batches in flight read the table this rewrites
-  if (rc) return rc;
-  if (c->am_busy) HIP_TRY(c, hipEventSynchronize(c->am_done));   // so does an amodal geometry pass, on any stream
+  CSG_TRY(drain(c));              // batches in flight read the table this rewrites
+  CSG_TRY(c->am.wait_host(c));    // so does an amodal geometry pass, on any stream
   const size_t per = (size_t)c->n_lab * 12;
   std::vector<float> t((size_t)n_sets * per, 0.f);
   const size_t have = std::min<size_t>(c->of_sets, n_sets) * per;
@@ -1026,10 +712,7 @@ static int ensure_work(csg_ctx* c) {
     target_pools(c, maxF, rp, bp);
     if (rp == c->rec_pool && bp == c->bin_pool) return CSG_OK;
   }
-  {  // buffers are reallocated below
-    const int rc = drain(c);
-    if (rc) return rc;
-  }
+  CSG_TRY(drain(c));   // buffers are reallocated below
   if (!c->rec_cap) c->rec_cap = c->cfg.records_per_frame ? c->cfg.records_per_frame : full_record_cap(c);
   c->rec_cap = (c->rec_cap + 3u) & ~3u;   // 16-B aligned rect rows per frame (k_count / k_bin load 4 at once)
   if (!c->bin_cap)
@@ -1042,9 +725,7 @@ static int ensure_work(csg_ctx* c) {
     c->recs.release(); c->rect.release(); c->bins.release();
   }
   HIP_TRY(c, c->frames.alloc(c->cfg.max_frames));   // the whole batch's frame records
-  for (uint32_t k = 0; k < csg_ctx::kStaging; ++k)
-    if (!c->h_stage[k])
-      HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_stage[k]), sizeof(FrameDev) * c->cfg.max_frames));
+  for (auto& slot : c->stage) HIP_TRY(c, slot.buf.alloc(c->cfg.max_frames));   // ... and their staging
   HIP_TRY(c, c->fset.alloc(maxF));
   HIP_TRY(c, c->clip.alloc((size_t)maxF * c->n_inst * 12));
   HIP_TRY(c, c->pv.alloc((size_t)maxF * 12));
@@ -1065,7 +746,7 @@ static int ensure_work(csg_ctx* c) {
   return CSG_OK;
 }
 
-static SceneDev scene_dev(const csg_ctx* c) {
+extern "C++" SceneDev csg::scene_dev(const csg_ctx* c) {
   SceneDev s{};
   s.tri_pos = c->tri_pos.p; s.tri_uv = c->tri_uv.p; s.tri_abox = reinterpret_cast<const float4*>(c->abox.p);
   s.inst = c->inst.p;
@@ -1080,7 +761,37 @@ static SceneDev scene_dev(const csg_ctx* c) {
   return s;
 }
 
-// Page-locked host memory (hipHostMalloc / hipHostRegister): only then is a
+// The scene tables and work buffers a launch chain reads and writes; outputs and keypoints: the caller's.
+static BatchDev batch_dev(const csg_ctx* c, const FrameDev* frames) {
+  BatchDev b{};
+  b.frames = frames;
+  b.fset = c->fset.p;
+  b.n_sets = (uint32_t)c->set_valid.size();    // = sets in the models, materials and lights tables
+  b.n_kp_sets = (uint32_t)c->kp_valid.size();
+  b.models = c->models.p;
+  b.mats = c->set_mats.p;
+  b.iset = c->iset.p;
+  b.lights = c->lights.p;
+  b.n_mat = c->n_materials;
+  b.clip = c->clip.p;
+  b.pv = c->pv.p;
+  b.cam = c->cam.p;
+  b.recs = c->recs.p;
+  b.rect = c->rect.p;
+  b.slab = c->slab.p;
+  b.rec_count = c->rec_count.p;
+  b.tile_count = c->tile_count.p;
+  b.bcount = c->bcount.p;
+  b.bin_blocks = c->bin_blocks;
+  b.tile_off = c->tile_off.p;
+  b.bins = c->bins.p;
+  b.overflow = c->overflow.p;
+  b.dbg = c->dbg;
+  b.tile_words = (c->n_tiles + 31u) / 32u;
+  return b;
+}
+
+// Page-locked host memory (csg_host_alloc / hipHostRegister): only then is a
 // D2H hipMemcpyAsync asynchronous; a pageable destination is staged and blocks.
 static bool host_pinned(const void* p) {
   hipPointerAttribute_t a{};
@@ -1151,45 +862,18 @@ static int enqueue_batch(csg_ctx* c, const csg_frame* frames, uint32_t F, int fr
         return c->fail(CSG_ERR_INVALID, "frame %u: keypoint set %u not uploaded", f, set);
     }
   }
-  BatchDev b{};
   const FrameDev* dframes;
   if (frames_on_device) {
     dframes = reinterpret_cast<const FrameDev*>(frames);
   } else {
     static_assert(sizeof(FrameDev) == sizeof(csg_frame), "frame layout");
-    const uint32_t slot = c->stage_next;
-    c->stage_next = (slot + 1) % csg_ctx::kStaging;
-    if (c->stage_busy[slot]) HIP_TRY(c, hipEventSynchronize(c->stage_ev[slot]));   // its last H2D copy is done
-    memcpy(c->h_stage[slot], frames, sizeof(FrameDev) * F);
-    HIP_TRY(c, hipMemcpyAsync(c->frames.p, c->h_stage[slot], sizeof(FrameDev) * F, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipEventRecord(c->stage_ev[slot], st));
-    c->stage_busy[slot] = true;
+    StageSlot<FrameDev>& slot = c->stage[c->stage_next];
+    c->stage_next = (c->stage_next + 1) % kStaging;
+    HIP_TRY(c, slot.upload(c->frames.p, F, st, [&](FrameDev* h) { memcpy(h, frames, sizeof(FrameDev) * F); }));
     dframes = c->frames.p;
   }
-  b.frames = dframes;
-  b.fset = c->fset.p;
-  b.n_sets = (uint32_t)c->set_valid.size();    // = sets in the models, materials and lights tables
-  b.n_kp_sets = (uint32_t)c->kp_valid.size();
-  b.models = c->models.p;
-  b.mats = c->set_mats.p;
-  b.iset = c->iset.p;
-  b.lights = c->lights.p;
-  b.n_mat = c->n_materials;
-  b.clip = c->clip.p;
-  b.pv = c->pv.p;
-  b.cam = c->cam.p;
-  b.recs = c->recs.p;
-  b.rect = c->rect.p;
-  b.slab = c->slab.p;
-  b.rec_count = c->rec_count.p;
-  b.tile_count = c->tile_count.p;
-  b.bcount = c->bcount.p;
-  b.bin_blocks = c->bin_blocks;
-  b.tile_off = c->tile_off.p;
-  b.bins = c->bins.p;
-  b.overflow = c->overflow.p;
+  BatchDev b = batch_dev(c, dframes);
   b.n_labels = out->n_labels;
-  b.dbg = c->dbg;
   b.kp = c->kp.p;
   b.n_kp = want_kp ? c->n_kp : 0;
   if (dev) {
@@ -1273,7 +957,6 @@ static int enqueue_batch(csg_ctx* c, const csg_frame* frames, uint32_t F, int fr
     if (dev) dstats = out->depth_stats;
     else { HIP_TRY(c, c->o_dstats.alloc((size_t)F * 6)); dstats = c->o_dstats.p; }
   }
-  b.tile_words = (c->n_tiles + 31u) / 32u;
   if (want_kp) {
     HIP_TRY(c, c->kp_w.alloc((size_t)c->chain_frames * c->n_kp));
     HIP_TRY(c, c->kp_pix.alloc((size_t)c->chain_frames * c->n_kp));
@@ -1311,24 +994,17 @@ static int enqueue_batch(csg_ctx* c, const csg_frame* frames, uint32_t F, int fr
     if (pinned || c->split_pageable) G = std::min(G, std::max(kMinCopyChain, (F + kCopyChunks - 1) / kCopyChunks));
     if (!c->copy_stream) {
       HIP_TRY(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-      for (auto& e : c->copy_ev) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      HIP_TRY(c, hipEventCreateWithFlags(&c->copy_done, hipEventDisableTiming));
+      for (auto& e : c->copy_ev) HIP_TRY(c, e.ensure());
+      HIP_TRY(c, c->copy_done.ensure());
     }
   }
   std::shared_ptr<WidenLatch> latch;
   if (narrow) {
     const size_t nb = (size_t)F * npx * c->ids_bytes;
     HIP_TRY(c, c->o_ids_n.alloc(nb));
-    if (c->h_ids_n_bytes < nb) {
-      if (c->h_ids_n) {   // the previous batch's widening (on the copy stream) may still read it
-        HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
-        HIP_TRY(c, hipHostFree(c->h_ids_n));
-        c->h_ids_n = nullptr;
-        c->h_ids_n_bytes = 0;
-      }
-      HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_ids_n), nb, hipHostMallocDefault));
-      c->h_ids_n_bytes = nb;
-    }
+    // the previous batch's widening (on the copy stream) may still read the landing buffer
+    if (c->h_ids_n.p && c->h_ids_n.n < nb) HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
+    HIP_TRY(c, c->h_ids_n.alloc(nb));
     latch = std::make_shared<WidenLatch>();
   }
   HIP_TRY(c, hipMemsetAsync(c->plan_need.p, 0, 2 * sizeof(uint64_t), st));   // k_plan: max over the chains
@@ -1394,7 +1070,7 @@ static int enqueue_batch(csg_ctx* c, const csg_frame* frames, uint32_t F, int fr
     c->last_F = Fc;
     if (narrow) launch_narrow_ids(b.inst, (size_t)c0 * npx, (size_t)(c0 + Fc) * npx, c->ids_bytes, c->o_ids_n.p, st);
     if (!dev) {   // this chain's outputs to the host, on the copy stream, behind its kernels
-      hipEvent_t e = c->copy_ev[chain % csg_ctx::kCopyEv];
+      hipEvent_t e = c->copy_ev[chain % csg_ctx::kCopyEv].e;
       hipStream_t cs = c->copy_stream;
       HIP_TRY(c, hipEventRecord(e, st));
       HIP_TRY(c, hipStreamWaitEvent(cs, e, 0));
@@ -1406,8 +1082,8 @@ static int enqueue_batch(csg_ctx* c, const csg_frame* frames, uint32_t F, int fr
       if (out->rgb) HIP_TRY(c, copy(out->rgb, b.rgb, npx * 3));
       if (narrow) {   // (id + 1) bytes to the landing buffer, then widened into the caller's int32 ids
         const size_t pf = npx * c->ids_bytes;
-        HIP_TRY(c, copy(c->h_ids_n, c->o_ids_n.p, pf));
-        auto* w = new WidenChain{c->h_ids_n + (size_t)c0 * pf, c->ids_bytes, out->instance + (size_t)c0 * npx,
+        HIP_TRY(c, copy(c->h_ids_n.p, c->o_ids_n.p, pf));
+        auto* w = new WidenChain{c->h_ids_n.p + (size_t)c0 * pf, c->ids_bytes, out->instance + (size_t)c0 * npx,
                                  (size_t)Fc * npx, latch};
         const hipError_t he = hipLaunchHostFunc(cs, widen_submit_cb, w);
         if (he != hipSuccess) delete w;
@@ -1442,8 +1118,8 @@ static int enqueue_batch(csg_ctx* c, const csg_frame* frames, uint32_t F, int fr
       if (he != hipSuccess) delete l;
       HIP_TRY(c, he);
     }
-    HIP_TRY(c, hipEventRecord(c->copy_done, c->copy_stream));
-    HIP_TRY(c, hipStreamWaitEvent(st, c->copy_done, 0));
+    HIP_TRY(c, hipEventRecord(c->copy_done.e, c->copy_stream));
+    HIP_TRY(c, hipStreamWaitEvent(st, c->copy_done.e, 0));
   }
   return CSG_OK;
 }
@@ -1736,10 +1412,7 @@ int csg_host_free(csg_ctx* c, void* p) {
 int csg_get_batch_stats(csg_ctx* c, csg_batch_stats* st) {
   if (!c || !st) return CSG_ERR_INVALID;
   memset(st, 0, sizeof(*st));
-  {
-    const int rc = drain(c);
-    if (rc) return rc;
-  }
+  CSG_TRY(drain(c));
   const uint32_t F = c->last_F;
   st->frames = F;
   if (!F) return CSG_OK;
@@ -1770,10 +1443,7 @@ int csg_get_batch_stats(csg_ctx* c, csg_batch_stats* st) {
 
 int csg_timing_reset(csg_ctx* c) {
   if (!c) return CSG_ERR_INVALID;
-  {
-    const int rc = drain(c);
-    if (rc) return rc;
-  }
+  CSG_TRY(drain(c));
   c->ring_count = 0;
   return CSG_OK;
 }
@@ -1839,30 +1509,7 @@ static int measure_work(csg_ctx* c, const csg_frame* frames, uint32_t n, bool on
         HIP_TRY(c, hipMemcpy(hframes.p, frames + c0, sizeof(FrameDev) * Fc, hipMemcpyHostToDevice));
         df = hframes.p;
       }
-      BatchDev b{};
-      b.frames = df;
-      b.fset = c->fset.p;
-      b.n_sets = (uint32_t)c->set_valid.size();
-      b.n_kp_sets = (uint32_t)c->kp_valid.size();
-      b.models = c->models.p;
-      b.mats = c->set_mats.p;
-      b.iset = c->iset.p;
-      b.lights = c->lights.p;
-      b.n_mat = c->n_materials;
-      b.clip = c->clip.p;
-      b.pv = c->pv.p;
-      b.cam = c->cam.p;
-      b.recs = c->recs.p;
-      b.rect = c->rect.p;
-      b.slab = c->slab.p;
-      b.rec_count = c->rec_count.p;
-      b.tile_count = c->tile_count.p;
-      b.bcount = c->bcount.p;
-      b.bin_blocks = c->bin_blocks;
-      b.tile_off = c->tile_off.p;
-      b.overflow = c->overflow.p;
-      b.dbg = c->dbg;
-      b.tile_words = (c->n_tiles + 31u) / 32u;
+      const BatchDev b = batch_dev(c, df);   // (no bin pool: k_bin is not run)
       HIP_TRY(c, hipMemsetAsync(c->rec_count.p, 0, sizeof(uint32_t) * Fc * kCounterStride, st));
       // uniform slabs at the probe cap; no bin cap (no bin pool: k_bin is not run)
       launch_plan(df, Fc, cap, 0x7FFFFFFCu, (uint64_t)P * cap, (uint64_t)P * 0x7FFFFFFCull, 0, c->slab.p,
@@ -2057,7 +1704,6 @@ int csg_project_keypoints(csg_ctx* c, const float* pts, uint32_t n, const float*
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   HIP_TRY(c, hipMemcpy(uv_out, duv.p, (size_t)n * 8, hipMemcpyDeviceToHost));
   HIP_TRY(c, hipMemcpy(vis_out, dvis.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  dp.release(); dpv.release(); duv.release(); dvis.release();
   return CSG_OK;
 }
 
@@ -2081,200 +1727,11 @@ int csg_instance_bounds(csg_ctx* c, uint32_t set_id, float* out) {
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   HIP_TRY(c, hipMemcpy(init.data(), d.p, n * 4, hipMemcpyDeviceToHost));
-  d.release();
   for (size_t k = 0; k < n; ++k) {
     const uint32_t o = init[k];
     const uint32_t u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
     memcpy(&out[k], &u, 4);
   }
-  return CSG_OK;
-}
-
-// Object crops: a stand-alone pass over device arrays (no scene state, no
-// work buffers), so it only validates the job and enqueues the kernels.
-int csg_crop_objects(csg_ctx* c, const csg_crop_job* job, uint32_t n_frames, void* stream) {
-  return csg_crop_objects_filtered(c, job, CSG_CROP_FILTER_BILINEAR, n_frames, stream);
-}
-
-int csg_crop_objects_filtered(csg_ctx* c, const csg_crop_job* job, uint32_t rgb_filter, uint32_t n_frames,
-                              void* stream) {
-  static_assert(sizeof(CropSlot) == sizeof(csg_crop_info) && sizeof(csg_crop_info) == 32, "csg_crop_info layout");
-  static_assert(offsetof(CropSlot, side) == offsetof(csg_crop_info, side) &&
-                offsetof(CropSlot, frame) == offsetof(csg_crop_info, frame), "csg_crop_info layout");
-  if (!c) return CSG_ERR_INVALID;
-  if (!job) return c->fail(CSG_ERR_INVALID, "crop_objects: null job");
-  if (n_frames == 0) return c->fail(CSG_ERR_INVALID, "crop_objects: no frames");
-  if (rgb_filter != CSG_CROP_FILTER_BILINEAR && rgb_filter != CSG_CROP_FILTER_AREA)
-    return c->fail(CSG_ERR_INVALID, "crop_objects: rgb_filter %u is neither CSG_CROP_FILTER_BILINEAR nor _AREA",
-                   rgb_filter);
-  if (job->size < 16 || job->size > 512 || (job->size & 3u))
-    return c->fail(CSG_ERR_INVALID, "crop_objects: size %u is not a multiple of 4 in 16..512", job->size);
-  if (job->per_frame < 1 || job->per_frame > 64)
-    return c->fail(CSG_ERR_INVALID, "crop_objects: per_frame %u outside 1..64", job->per_frame);
-  if (job->min_pixels < 1) return c->fail(CSG_ERR_INVALID, "crop_objects: min_pixels must be at least 1");
-  if (!std::isfinite(job->pad) || !(job->pad >= 1.0f))
-    return c->fail(CSG_ERR_INVALID, "crop_objects: pad %g is not a finite value >= 1", (double)job->pad);
-  if (!job->info) return c->fail(CSG_ERR_INVALID, "crop_objects: info is NULL");
-  if (!job->instance) return c->fail(CSG_ERR_INVALID, "crop_objects: the instance image is always needed");
-  if (job->crop_rgb && !job->rgb) return c->fail(CSG_ERR_INVALID, "crop_objects: crop_rgb needs rgb");
-  if (job->crop_coords && !job->obj_coords)
-    return c->fail(CSG_ERR_INVALID, "crop_objects: crop_coords needs obj_coords");
-  if (job->crop_depth && !job->depth) return c->fail(CSG_ERR_INVALID, "crop_objects: crop_depth needs depth");
-  if (!job->explicit_boxes && !job->inst_stats)
-    return c->fail(CSG_ERR_INVALID, "crop_objects: planning needs inst_stats (or explicit_boxes = 1)");
-  if (((uintptr_t)job->crop_rgb & 3u) || ((uintptr_t)job->crop_mask & 3u) || ((uintptr_t)job->crop_coords & 7u) ||
-      ((uintptr_t)job->crop_depth & 15u) || ((uintptr_t)job->info & 3u))
-    return c->fail(CSG_ERR_INVALID, "crop_objects: crop_rgb, crop_mask and info must be 4-byte aligned, crop_coords "
-                                    "8-byte, crop_depth 16-byte");
-  HIP_TRY(c, hipSetDevice(c->cfg.device));
-  hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
-  CropArgs a{};
-  a.W = c->cfg.width;
-  a.H = c->cfg.height;
-  a.S = job->size;
-  a.K = job->per_frame;
-  a.min_pixels = job->min_pixels;
-  a.pad = job->pad;
-  a.n_labels = job->n_labels;
-  a.explicit_boxes = job->explicit_boxes ? 1 : 0;
-  a.rgb_filter = rgb_filter;
-  a.rgb = job->rgb;
-  a.instance = job->instance;
-  a.obj_coords = job->obj_coords;
-  a.depth = job->depth;
-  a.stats = job->inst_stats;
-  a.eligible = job->eligible;
-  a.crop_rgb = job->crop_rgb;
-  a.crop_mask = job->crop_mask;
-  a.crop_coords = job->crop_coords;
-  a.crop_depth = job->crop_depth;
-  a.info = reinterpret_cast<CropSlot*>(job->info);
-  if (!a.explicit_boxes) launch_crop_plan(a, n_frames, st);
-  if (a.crop_rgb || a.crop_mask || a.crop_coords || a.crop_depth) launch_crop_sample(a, n_frames, st);
-  if (a.rgb_filter == CSG_CROP_FILTER_AREA && a.crop_rgb) launch_crop_area(a, n_frames, st);   // behind the plan
-  HIP_TRY(c, hipGetLastError());
-  return CSG_OK;
-}
-
-// Mask spans: a stand-alone pass over a device id image (no scene state, no work buffers); validates
-// the job, grows the pass's own count scratch and enqueues count, scan and emit.
-int csg_mask_spans(csg_ctx* c, const csg_span_job* job, uint32_t n_frames, void* stream) {
-  static_assert(sizeof(SpanRec) == sizeof(csg_span) && sizeof(csg_span) == 8, "csg_span layout");
-  static_assert(kSpanMaxLabels == CSG_SPAN_MAX_LABELS, "label limit");
-  if (!c) return CSG_ERR_INVALID;
-  if (!job) return c->fail(CSG_ERR_INVALID, "mask_spans: null job");
-  if (n_frames == 0) return c->fail(CSG_ERR_INVALID, "mask_spans: no frames");
-  if (!job->instance || !job->spans || !job->span_offsets)
-    return c->fail(CSG_ERR_INVALID, "mask_spans: instance, spans and span_offsets must not be NULL");
-  if (job->width < 1 || job->width > 8192 || job->height < 1 || job->height > 8192)
-    return c->fail(CSG_ERR_INVALID, "mask_spans: frame %u x %u outside 1..8192", job->width, job->height);
-  if (job->capacity == 0) return c->fail(CSG_ERR_INVALID, "mask_spans: capacity must be at least 1");
-  if (job->n_labels == 0) return c->fail(CSG_ERR_INVALID, "mask_spans: n_labels must be at least 1");
-  if (job->n_labels > CSG_SPAN_MAX_LABELS)
-    return c->fail(CSG_ERR_LIMIT, "mask_spans: n_labels %u above CSG_SPAN_MAX_LABELS %u", job->n_labels,
-                   CSG_SPAN_MAX_LABELS);
-  if (((uintptr_t)job->spans & 7u) || ((uintptr_t)job->span_offsets & 3u))
-    return c->fail(CSG_ERR_INVALID, "mask_spans: spans must be 8-byte aligned, span_offsets 4-byte");
-  HIP_TRY(c, hipSetDevice(c->cfg.device));
-  hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
-  SpanArgs a{};
-  a.W = job->width;
-  a.H = job->height;
-  a.L = job->n_labels;
-  a.G = (job->width + 63u) / 64u;
-  a.C = job->capacity;
-  a.instance = job->instance;
-  a.spans = reinterpret_cast<SpanRec*>(job->spans);
-  a.offsets = job->span_offsets;
-  const size_t n_cnt = (size_t)n_frames * a.L * a.G;
-  if (!c->ms_done) HIP_TRY(c, hipEventCreateWithFlags(&c->ms_done, hipEventDisableTiming));
-  if (c->ms_busy) {
-    if (c->ms_cnt.n < n_cnt) HIP_TRY(c, hipEventSynchronize(c->ms_done));         // the last pass still reads what is freed below
-    else if (c->ms_stream != st) HIP_TRY(c, hipStreamWaitEvent(st, c->ms_done, 0));   // ... or what this pass overwrites
-  }
-  HIP_TRY(c, c->ms_cnt.alloc(n_cnt));
-  a.cnt = c->ms_cnt.p;
-  launch_span_count(a, n_frames, st);
-  launch_span_scan(a, n_frames, st);
-  launch_span_emit(a, n_frames, st);
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipEventRecord(c->ms_done, st));
-  c->ms_stream = st;
-  c->ms_busy = true;
-  return CSG_OK;
-}
-
-// Object points: a stand-alone pass over device arrays (no scene state, no work buffers); validates the
-// job, grows the pass's own count scratch and enqueues count, scan and emit.
-int csg_sample_object_points(csg_ctx* c, const csg_point_job* job, uint32_t n_frames, void* stream) {
-  static_assert(kPointMaxLabels == CSG_SPAN_MAX_LABELS, "label limit");
-  if (!c) return CSG_ERR_INVALID;
-  if (!job) return c->fail(CSG_ERR_INVALID, "sample_object_points: null job");
-  if (n_frames == 0) return c->fail(CSG_ERR_INVALID, "sample_object_points: no frames");
-  if (job->width < 1 || job->width > 8192 || job->height < 1 || job->height > 8192)
-    return c->fail(CSG_ERR_INVALID, "sample_object_points: frame %u x %u outside 1..8192", job->width, job->height);
-  if (job->n_labels == 0) return c->fail(CSG_ERR_INVALID, "sample_object_points: n_labels must be at least 1");
-  if (job->n_labels > CSG_SPAN_MAX_LABELS)
-    return c->fail(CSG_ERR_LIMIT, "sample_object_points: n_labels %u above CSG_SPAN_MAX_LABELS %u", job->n_labels,
-                   CSG_SPAN_MAX_LABELS);
-  if (job->per_frame < 1 || job->per_frame > 64)
-    return c->fail(CSG_ERR_INVALID, "sample_object_points: per_frame %u outside 1..64", job->per_frame);
-  if (job->samples < 16 || job->samples > 16384 || (job->samples & 3u))
-    return c->fail(CSG_ERR_INVALID, "sample_object_points: samples %u is not a multiple of 4 in 16..16384",
-                   job->samples);
-  if (!job->instance || !job->info)
-    return c->fail(CSG_ERR_INVALID, "sample_object_points: instance and info are always needed");
-  if (!job->pt_count && !job->pt_choose && !job->pt_xyz && !job->pt_rgb && !job->pt_coords)
-    return c->fail(CSG_ERR_INVALID, "sample_object_points: no output");
-  if (job->pt_xyz && (!job->depth || !job->intrinsics))
-    return c->fail(CSG_ERR_INVALID, "sample_object_points: pt_xyz needs depth and intrinsics");
-  if (job->pt_rgb && !job->rgb) return c->fail(CSG_ERR_INVALID, "sample_object_points: pt_rgb needs rgb");
-  if (job->pt_coords && !job->obj_coords)
-    return c->fail(CSG_ERR_INVALID, "sample_object_points: pt_coords needs obj_coords");
-  if ((((uintptr_t)job->instance | (uintptr_t)job->info | (uintptr_t)job->depth | (uintptr_t)job->intrinsics |
-        (uintptr_t)job->frame_keys | (uintptr_t)job->pt_count | (uintptr_t)job->pt_choose | (uintptr_t)job->pt_xyz |
-        (uintptr_t)job->pt_rgb) & 3u) || (((uintptr_t)job->obj_coords | (uintptr_t)job->pt_coords) & 1u))
-    return c->fail(CSG_ERR_INVALID, "sample_object_points: obj_coords and pt_coords must be 2-byte aligned, every "
-                                    "other pointer but rgb 4-byte");
-  HIP_TRY(c, hipSetDevice(c->cfg.device));
-  hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
-  PointArgs a{};
-  a.W = job->width;
-  a.H = job->height;
-  a.P = job->width * job->height;
-  a.L = job->n_labels;
-  a.K = job->per_frame;
-  a.N = job->samples;
-  a.CH = (a.P + kPointChunk - 1u) / kPointChunk;
-  a.seed = job->seed;
-  a.instance = job->instance;
-  a.info = reinterpret_cast<const CropSlot*>(job->info);
-  a.depth = job->pt_xyz ? job->depth : nullptr;   // a source nobody asked for is never read
-  a.intrinsics = job->pt_xyz ? job->intrinsics : nullptr;
-  a.rgb = job->pt_rgb ? job->rgb : nullptr;
-  a.obj_coords = job->pt_coords ? job->obj_coords : nullptr;
-  a.frame_keys = job->frame_keys;
-  a.pt_count = job->pt_count;
-  a.pt_choose = job->pt_choose;
-  a.pt_xyz = job->pt_xyz;
-  a.pt_rgb = job->pt_rgb;
-  a.pt_coords = job->pt_coords;
-  const size_t n_tot = (size_t)n_frames * a.L, n_cnt = n_tot * a.CH;
-  if (!c->op_done) HIP_TRY(c, hipEventCreateWithFlags(&c->op_done, hipEventDisableTiming));
-  if (c->op_busy) {
-    if (c->op_cnt.n < n_cnt + n_tot) HIP_TRY(c, hipEventSynchronize(c->op_done));   // the last pass still reads what is freed below
-    else if (c->op_stream != st) HIP_TRY(c, hipStreamWaitEvent(st, c->op_done, 0));   // ... or what this pass overwrites
-  }
-  HIP_TRY(c, c->op_cnt.alloc(n_cnt + n_tot));
-  a.cnt = c->op_cnt.p;
-  a.total = c->op_cnt.p + n_cnt;
-  launch_pts_count(a, n_frames, st);
-  launch_pts_scan(a, n_frames, st);
-  launch_pts_emit(a, n_frames, st);
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipEventRecord(c->op_done, st));
-  c->op_stream = st;
-  c->op_busy = true;
   return CSG_OK;
 }
 
@@ -2290,284 +1747,6 @@ int csg_last_instance(csg_ctx* c, const int32_t** instance, uint32_t* n_frames) 
   *instance = c->last_inst;
   *n_frames = c->last_inst_frames;
   return CSG_OK;
-}
-
-}  // extern "C"
-
-// The shared front of the amodal passes (csg_crop_amodal, csg_crop_amodal_geometry): orders this pass
-// behind the last one, grows the pass's scratch (device frame records, n_bits words of bit image, n_keys
-// keys) and copies the caller's frame records through the pinned ring to am_frames on `st`.
-static int am_begin(csg_ctx* c, const csg_frame* frames, uint32_t n_frames, size_t n_bits, size_t n_keys,
-                    hipStream_t st) {
-  static_assert(sizeof(FrameDev) == sizeof(csg_frame), "frame layout");
-  if (!c->am_done) HIP_TRY(c, hipEventCreateWithFlags(&c->am_done, hipEventDisableTiming));
-  if (c->am_busy) {
-    if (c->am_frames.n < n_frames || c->am_bits.n < n_bits || c->am_keys.n < n_keys)
-      HIP_TRY(c, hipEventSynchronize(c->am_done));           // the last pass still reads what is freed below
-    else if (c->am_stream != st)
-      HIP_TRY(c, hipStreamWaitEvent(st, c->am_done, 0));     // ... or what this pass overwrites
-  }
-  HIP_TRY(c, c->am_frames.alloc(n_frames));
-  HIP_TRY(c, c->am_bits.alloc(n_bits));
-  HIP_TRY(c, c->am_keys.alloc(n_keys));
-  const uint32_t ring = c->am_stage_next;
-  c->am_stage_next = (ring + 1) % csg_ctx::kStaging;
-  if (!c->am_stage_ev[ring]) HIP_TRY(c, hipEventCreateWithFlags(&c->am_stage_ev[ring], hipEventDisableTiming));
-  else HIP_TRY(c, hipEventSynchronize(c->am_stage_ev[ring]));   // the slot's last H2D copy is done
-  if (c->am_stage_n[ring] < n_frames) {
-    if (c->am_stage[ring]) HIP_TRY(c, hipHostFree(c->am_stage[ring]));
-    c->am_stage[ring] = nullptr;
-    c->am_stage_n[ring] = 0;
-    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->am_stage[ring]), sizeof(FrameDev) * n_frames));
-    c->am_stage_n[ring] = n_frames;
-  }
-  memcpy(c->am_stage[ring], frames, sizeof(FrameDev) * n_frames);
-  HIP_TRY(c, hipMemcpyAsync(c->am_frames.p, c->am_stage[ring], sizeof(FrameDev) * n_frames, hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipEventRecord(c->am_stage_ev[ring], st));
-  return CSG_OK;
-}
-
-// ... and their end: am_done marks the pass's completion on `st`.
-static int am_end(csg_ctx* c, hipStream_t st) {
-  HIP_TRY(c, hipEventRecord(c->am_done, st));
-  c->am_stream = st;
-  c->am_busy = true;
-  return CSG_OK;
-}
-
-extern "C" {
-
-// Amodal crop masks: reads the scene tables (synced here as a render syncs them) and the caller's
-// `info`; everything it writes besides the output is scratch of its own.
-int csg_crop_amodal(csg_ctx* c, const csg_amodal_job* job, uint32_t n_frames, void* stream) {
-  if (!c) return CSG_ERR_INVALID;
-  if (!job) return c->fail(CSG_ERR_INVALID, "crop_amodal: null job");
-  if (n_frames == 0) return c->fail(CSG_ERR_INVALID, "crop_amodal: no frames");
-  if (job->size < 16 || job->size > 512 || (job->size & 3u))
-    return c->fail(CSG_ERR_INVALID, "crop_amodal: size %u is not a multiple of 4 in 16..512", job->size);
-  if (job->per_frame < 1 || job->per_frame > 64)
-    return c->fail(CSG_ERR_INVALID, "crop_amodal: per_frame %u outside 1..64", job->per_frame);
-  if (!job->frames) return c->fail(CSG_ERR_INVALID, "crop_amodal: frames is NULL");
-  if (!job->info) return c->fail(CSG_ERR_INVALID, "crop_amodal: info is NULL");
-  if (!job->crop_amodal) return c->fail(CSG_ERR_INVALID, "crop_amodal: crop_amodal is NULL");
-  if (((uintptr_t)job->crop_amodal & 3u) || ((uintptr_t)job->info & 3u))
-    return c->fail(CSG_ERR_INVALID, "crop_amodal: crop_amodal and info must be 4-byte aligned");
-  if (!c->have_scene) return c->fail(CSG_ERR_INVALID, "crop_amodal: no scene uploaded");
-  for (uint32_t f = 0; f < n_frames; ++f)
-    if (job->frames[f].xform_set >= c->set_valid.size())
-      return c->fail(CSG_ERR_INVALID, "crop_amodal: frame %u: transform set %u is not resident (%u sets)", f,
-                     job->frames[f].xform_set, (unsigned)c->set_valid.size());
-  HIP_TRY(c, hipSetDevice(c->cfg.device));
-  hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
-  int rc = sync_scene_state(c);
-  if (rc) return rc;
-  const uint32_t S = job->size, K = job->per_frame, words = (S * S + 31u) / 32u;
-  const size_t n_bits = (size_t)n_frames * K * words;
-  rc = am_begin(c, job->frames, n_frames, n_bits, 0, st);
-  if (rc) return rc;
-  HIP_TRY(c, hipMemsetAsync(c->am_bits.p, 0, n_bits * sizeof(uint32_t), st));
-  AmodalDev a{};
-  a.S = S;
-  a.K = K;
-  a.n_labels = c->n_lab;
-  a.n_sets = (uint32_t)c->set_valid.size();
-  a.words = words;
-  a.frames = c->am_frames.p;
-  a.info = reinterpret_cast<const CropSlot*>(job->info);
-  a.lab_off = c->lab_off.p;
-  a.lab_chunks = c->lab_chunks.p;
-  a.chunks = c->chunks.p;
-  a.models = c->models.p;
-  a.iset = c->iset.p;
-  a.bits = c->am_bits.p;
-  a.out = job->crop_amodal;
-  launch_crop_amodal(scene_dev(c), a, n_frames, c->lab_max_chunks, st);
-  HIP_TRY(c, hipGetLastError());
-  return am_end(c, st);
-}
-
-// Amodal depth and object coordinates: the same pass keeping, per sample, the largest 1/W instead of a
-// bit.  The keys (4 B per sample) live in crop_amodal_depth when it is given -- the finish pass converts
-// them in place --, else in scratch of the pass's own, bounded at kAmKeyCap bytes: the job then runs as
-// frame ranges on the stream, each zeroing, filling and finishing the same scratch.
-int csg_crop_amodal_geometry(csg_ctx* c, const csg_amodal_geometry_job* job, uint32_t n_frames, void* stream) {
-  constexpr size_t kAmKeyCap = 64u << 20;
-  if (!c) return CSG_ERR_INVALID;
-  if (!job) return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: null job");
-  if (n_frames == 0) return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: no frames");
-  if (job->size < 16 || job->size > 512 || (job->size & 3u))
-    return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: size %u is not a multiple of 4 in 16..512", job->size);
-  if (job->per_frame < 1 || job->per_frame > 64)
-    return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: per_frame %u outside 1..64", job->per_frame);
-  if (!job->frames) return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: frames is NULL");
-  if (!job->info) return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: info is NULL");
-  if (!job->crop_amodal && !job->crop_amodal_depth && !job->crop_amodal_coords)
-    return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: crop_amodal, crop_amodal_depth and crop_amodal_coords "
-                                    "are all NULL");
-  if (((uintptr_t)job->crop_amodal & 3u) || ((uintptr_t)job->info & 3u) || ((uintptr_t)job->crop_amodal_depth & 15u) ||
-      ((uintptr_t)job->crop_amodal_coords & 7u))
-    return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: crop_amodal and info must be 4-byte aligned, "
-                                    "crop_amodal_coords 8-byte, crop_amodal_depth 16-byte");
-  if (!c->have_scene) return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: no scene uploaded");
-  for (uint32_t f = 0; f < n_frames; ++f)
-    if (job->frames[f].xform_set >= c->set_valid.size())
-      return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: frame %u: transform set %u is not resident (%u sets)", f,
-                     job->frames[f].xform_set, (unsigned)c->set_valid.size());
-  HIP_TRY(c, hipSetDevice(c->cfg.device));
-  hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
-  int rc = sync_scene_state(c);
-  if (rc) return rc;
-  if (job->crop_amodal_coords) {
-    rc = sync_object_frames(c);
-    if (rc) return rc;
-  }
-  const uint32_t S = job->size, K = job->per_frame;
-  const size_t per_frame = (size_t)K * S * S;   // samples, and keys, of one frame
-  uint32_t range = n_frames;                    // frames per range; the depth output holds every key
-  if (!job->crop_amodal_depth) {
-    size_t cap = kAmKeyCap;
-    if (const char* e = getenv("CSG_AMODAL_KEY_CAP")) cap = (size_t)strtoull(e, nullptr, 10);   // (tests: bytes)
-    range = (uint32_t)std::min<size_t>(n_frames, std::max<size_t>(1, cap / (per_frame * sizeof(uint32_t))));
-  }
-  rc = am_begin(c, job->frames, n_frames, 0, job->crop_amodal_depth ? 0 : (size_t)range * per_frame, st);
-  if (rc) return rc;
-  AmodalDev a{};
-  a.S = S;
-  a.K = K;
-  a.n_labels = c->n_lab;
-  a.n_sets = (uint32_t)c->set_valid.size();
-  a.words = S * S;
-  a.lab_off = c->lab_off.p;
-  a.lab_chunks = c->lab_chunks.p;
-  a.chunks = c->chunks.p;
-  a.models = c->models.p;
-  a.iset = c->iset.p;
-  AmodalGeomOut g{};
-  g.W = c->cfg.width;
-  g.H = c->cfg.height;
-  g.table = c->of.p;
-  for (uint32_t f0 = 0; f0 < n_frames; f0 += range) {   // every array from the range's first frame
-    const uint32_t nf = std::min(range, n_frames - f0);
-    const size_t at = (size_t)f0 * per_frame;
-    a.frames = c->am_frames.p + f0;
-    a.info = reinterpret_cast<const CropSlot*>(job->info) + (size_t)f0 * K;
-    g.mask = job->crop_amodal ? job->crop_amodal + at : nullptr;
-    g.depth = job->crop_amodal_depth ? job->crop_amodal_depth + at : nullptr;
-    g.coords = job->crop_amodal_coords ? job->crop_amodal_coords + at * 3 : nullptr;
-    a.bits = g.depth ? reinterpret_cast<uint32_t*>(g.depth) : c->am_keys.p;
-    HIP_TRY(c, hipMemsetAsync(a.bits, 0, (size_t)nf * per_frame * sizeof(uint32_t), st));
-    launch_crop_amodal_geometry(scene_dev(c), a, g, nf, c->lab_max_chunks, st);
-  }
-  HIP_TRY(c, hipGetLastError());
-  return am_end(c, st);
-}
-
-// Full-frame amodal spans: the scene tables and the caller's frames as the other amodal passes read
-// them; bit planes, counts and tables are scratch of the pass's own.  The planes are bounded at
-// kAmPlaneCap bytes: a job that needs more runs as frame ranges on the stream, each zeroing, filling and
-// reading the same scratch.
-int csg_amodal_spans(csg_ctx* c, const csg_amodal_span_job* job, uint32_t n_frames, void* stream) {
-  constexpr size_t kAmPlaneCap = 64u << 20;
-  if (!c) return CSG_ERR_INVALID;
-  if (!job) return c->fail(CSG_ERR_INVALID, "amodal_spans: null job");
-  if (n_frames == 0) return c->fail(CSG_ERR_INVALID, "amodal_spans: no frames");
-  if (!job->frames) return c->fail(CSG_ERR_INVALID, "amodal_spans: frames is NULL");
-  if (!job->spans || !job->span_offsets)
-    return c->fail(CSG_ERR_INVALID, "amodal_spans: spans and span_offsets must not be NULL");
-  if (job->capacity == 0) return c->fail(CSG_ERR_INVALID, "amodal_spans: capacity must be at least 1");
-  if (((uintptr_t)job->spans & 7u) || ((uintptr_t)job->span_offsets & 3u) || ((uintptr_t)job->amodal_stats & 3u))
-    return c->fail(CSG_ERR_INVALID, "amodal_spans: spans must be 8-byte aligned, span_offsets and amodal_stats 4-byte");
-  if (!c->have_scene) return c->fail(CSG_ERR_INVALID, "amodal_spans: no scene uploaded");
-  if (c->n_lab > CSG_SPAN_MAX_LABELS)
-    return c->fail(CSG_ERR_LIMIT, "amodal_spans: %u labels above CSG_SPAN_MAX_LABELS %u", c->n_lab, CSG_SPAN_MAX_LABELS);
-  for (uint32_t f = 0; f < n_frames; ++f)
-    if (job->frames[f].xform_set >= c->set_valid.size())
-      return c->fail(CSG_ERR_INVALID, "amodal_spans: frame %u: transform set %u is not resident (%u sets)", f,
-                     job->frames[f].xform_set, (unsigned)c->set_valid.size());
-  HIP_TRY(c, hipSetDevice(c->cfg.device));
-  hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
-  int rc = sync_scene_state(c);
-  if (rc) return rc;
-  const uint32_t L = c->n_lab, W = c->cfg.width, H = c->cfg.height;
-  const uint32_t G = (W + 63u) / 64u, HW = (H + 31u) / 32u;
-  // the job's tables: label -> plane, and one (chunk, plane) item per chunk of an eligible label
-  std::vector<uint32_t> plane_of(L, kNoPlane), items_c, items_p;
-  uint32_t P = 0;
-  for (uint32_t l = 0; l < L; ++l) {
-    if (job->eligible && !job->eligible[l]) continue;
-    plane_of[l] = P;
-    for (uint32_t k = c->h_lab_off[l]; k < c->h_lab_off[l + 1]; ++k) {
-      items_c.push_back(c->h_lab_chunks[k]);
-      items_p.push_back(P);
-    }
-    ++P;
-  }
-  const uint32_t n_items = (uint32_t)items_c.size();
-  const size_t n_tab = (size_t)L + 2u * n_items;
-  const size_t per_frame = (size_t)P * HW * W;   // words of one frame's planes
-  size_t cap = kAmPlaneCap;
-  if (const char* e = getenv("CSG_AMODAL_PLANE_CAP")) cap = (size_t)strtoull(e, nullptr, 10);   // (tests: bytes)
-  uint32_t range = std::min<uint32_t>(n_frames, 65535u);   // grid z limit
-  if (per_frame) range = (uint32_t)std::min<size_t>(range, std::max<size_t>(1, cap / (per_frame * sizeof(uint32_t))));
-  const size_t n_planes = (size_t)range * per_frame, n_touched = (size_t)range * std::max(P, 1u);
-  const size_t n_cnt = (size_t)range * L * G;
-  if (!c->am_done) HIP_TRY(c, hipEventCreateWithFlags(&c->am_done, hipEventDisableTiming));
-  if (c->am_busy && (c->as_planes.n < n_planes || c->as_touched.n < n_touched || c->as_cnt.n < n_cnt ||
-                     c->as_tables.n < n_tab))
-    HIP_TRY(c, hipEventSynchronize(c->am_done));   // the last pass still reads what is freed below
-  HIP_TRY(c, c->as_planes.alloc(n_planes));
-  HIP_TRY(c, c->as_touched.alloc(n_touched));
-  HIP_TRY(c, c->as_cnt.alloc(n_cnt));
-  HIP_TRY(c, c->as_tables.alloc(n_tab));
-  rc = am_begin(c, job->frames, n_frames, 0, 0, st);   // (waits for a pass on another stream)
-  if (rc) return rc;
-  if (!c->as_stage_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->as_stage_ev, hipEventDisableTiming));
-  else HIP_TRY(c, hipEventSynchronize(c->as_stage_ev));   // the staging's last H2D copy is done
-  if (c->as_stage_n < n_tab) {
-    if (c->as_stage) HIP_TRY(c, hipHostFree(c->as_stage));
-    c->as_stage = nullptr;
-    c->as_stage_n = 0;
-    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->as_stage), sizeof(uint32_t) * n_tab));
-    c->as_stage_n = n_tab;
-  }
-  memcpy(c->as_stage, plane_of.data(), sizeof(uint32_t) * L);
-  if (n_items) {
-    memcpy(c->as_stage + L, items_c.data(), sizeof(uint32_t) * n_items);
-    memcpy(c->as_stage + L + n_items, items_p.data(), sizeof(uint32_t) * n_items);
-  }
-  HIP_TRY(c, hipMemcpyAsync(c->as_tables.p, c->as_stage, sizeof(uint32_t) * n_tab, hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipEventRecord(c->as_stage_ev, st));
-  AmodalSpanDev a{};
-  a.W = W;
-  a.H = H;
-  a.L = L;
-  a.P = P;
-  a.G = G;
-  a.HW = HW;
-  a.C = job->capacity;
-  a.n_sets = (uint32_t)c->set_valid.size();
-  a.n_items = n_items;
-  a.plane_of = c->as_tables.p;
-  a.item_chunk = c->as_tables.p + L;
-  a.item_plane = c->as_tables.p + L + n_items;
-  a.chunks = c->chunks.p;
-  a.models = c->models.p;
-  a.iset = c->iset.p;
-  a.planes = c->as_planes.p;
-  a.touched = c->as_touched.p;
-  a.cnt = c->as_cnt.p;
-  for (uint32_t f0 = 0; f0 < n_frames; f0 += range) {   // every array from the range's first frame
-    const uint32_t nf = std::min(range, n_frames - f0);
-    a.frames = c->am_frames.p + f0;
-    a.spans = reinterpret_cast<SpanRec*>(job->spans) + (size_t)f0 * a.C;
-    a.offsets = job->span_offsets + (size_t)f0 * (L + 1u);
-    a.stats = job->amodal_stats ? job->amodal_stats + (size_t)f0 * L * 5u : nullptr;
-    if (per_frame) HIP_TRY(c, hipMemsetAsync(a.planes, 0, (size_t)nf * per_frame * sizeof(uint32_t), st));
-    HIP_TRY(c, hipMemsetAsync(a.touched, 0, n_touched * sizeof(uint32_t), st));
-    launch_amodal_spans(scene_dev(c), a, nf, st);
-  }
-  HIP_TRY(c, hipGetLastError());
-  return am_end(c, st);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // csg_crops.h — host launchers of the object-crop kernels (csg_crops.hip),
-// called by csg_api.cpp for csg_crop_objects and csg_crop_objects_filtered.
+// called by csg_passes.cpp for csg_crop_objects and csg_crop_objects_filtered.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

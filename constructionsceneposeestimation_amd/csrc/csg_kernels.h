@@ -1,4 +1,4 @@
-// Internal interface between the C-ABI host code (csg_api.cpp) and the
+// Internal interface between the C-ABI host code (csg_api.cpp, csg_passes.cpp) and the
 // gfx950 kernels (csg_kernels.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>

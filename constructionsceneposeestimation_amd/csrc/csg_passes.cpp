@@ -1,0 +1,445 @@
+// The stand-alone passes of libcsg.so (see include/csg_api.h): object crops, mask spans, object points
+// and the three amodal passes.  Each validates its job on the host, orders itself behind the last pass
+// that used its scratch (PassOrder, csg_ctx.h), grows that scratch and enqueues its kernels on the
+// caller's stream.  None of them touches a render's work buffers.
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "csg_amodal_spans.h"
+#include "csg_crops.h"
+#include "csg_ctx.h"
+#include "csg_points.h"
+#include "csg_spans.h"
+
+using namespace csg;
+
+// The checks several passes share; `who` is the entry point's name in the message.
+static int check_size(csg_ctx* c, const char* who, uint32_t size) {
+  if (size < 16 || size > 512 || (size & 3u))
+    return c->fail(CSG_ERR_INVALID, "%s: size %u is not a multiple of 4 in 16..512", who, size);
+  return CSG_OK;
+}
+
+static int check_per_frame(csg_ctx* c, const char* who, uint32_t per_frame) {
+  if (per_frame < 1 || per_frame > 64)
+    return c->fail(CSG_ERR_INVALID, "%s: per_frame %u outside 1..64", who, per_frame);
+  return CSG_OK;
+}
+
+static int check_frame_dims(csg_ctx* c, const char* who, uint32_t width, uint32_t height) {
+  if (width < 1 || width > 8192 || height < 1 || height > 8192)
+    return c->fail(CSG_ERR_INVALID, "%s: frame %u x %u outside 1..8192", who, width, height);
+  return CSG_OK;
+}
+
+static int check_labels(csg_ctx* c, const char* who, uint32_t n_labels) {
+  if (n_labels == 0) return c->fail(CSG_ERR_INVALID, "%s: n_labels must be at least 1", who);
+  if (n_labels > CSG_SPAN_MAX_LABELS)
+    return c->fail(CSG_ERR_LIMIT, "%s: n_labels %u above CSG_SPAN_MAX_LABELS %u", who, n_labels, CSG_SPAN_MAX_LABELS);
+  return CSG_OK;
+}
+
+static int check_resident(csg_ctx* c, const char* who, const csg_frame* frames, uint32_t n_frames) {
+  for (uint32_t f = 0; f < n_frames; ++f)
+    if (frames[f].xform_set >= c->set_valid.size())
+      return c->fail(CSG_ERR_INVALID, "%s: frame %u: transform set %u is not resident (%u sets)", who, f,
+                     frames[f].xform_set, (unsigned)c->set_valid.size());
+  return CSG_OK;
+}
+
+// The stream a pass runs on: the caller's, or the context's.
+static int pass_stream(csg_ctx* c, void* stream, hipStream_t* st) {
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  *st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+  return CSG_OK;
+}
+
+// The caller's frame records, through the pinned ring, to am_frames on `st`.
+static int am_stage_frames(csg_ctx* c, const csg_frame* frames, uint32_t n_frames, hipStream_t st) {
+  static_assert(sizeof(FrameDev) == sizeof(csg_frame), "frame layout");
+  StageSlot<FrameDev>& slot = c->am_stage[c->am_stage_next];
+  c->am_stage_next = (c->am_stage_next + 1) % kStaging;
+  HIP_TRY(c, slot.upload(c->am_frames.p, n_frames, st,
+                         [&](FrameDev* h) { memcpy(h, frames, sizeof(FrameDev) * n_frames); }));
+  return CSG_OK;
+}
+
+// The shared front of the amodal crop passes: orders this pass behind the last amodal pass, grows the
+// scratch (device frame records, n_bits words of bit image, n_keys keys) and uploads the frame records.
+static int am_begin(csg_ctx* c, const csg_frame* frames, uint32_t n_frames, size_t n_bits, size_t n_keys,
+                    hipStream_t st) {
+  CSG_TRY(c->am.begin(c, st, c->am_frames.n < n_frames || c->am_bits.n < n_bits || c->am_keys.n < n_keys));
+  HIP_TRY(c, c->am_frames.alloc(n_frames));
+  HIP_TRY(c, c->am_bits.alloc(n_bits));
+  HIP_TRY(c, c->am_keys.alloc(n_keys));
+  return am_stage_frames(c, frames, n_frames, st);
+}
+
+extern "C" {
+
+// Object crops: a stand-alone pass over device arrays (no scene state, no
+// work buffers), so it only validates the job and enqueues the kernels.
+int csg_crop_objects(csg_ctx* c, const csg_crop_job* job, uint32_t n_frames, void* stream) {
+  return csg_crop_objects_filtered(c, job, CSG_CROP_FILTER_BILINEAR, n_frames, stream);
+}
+
+int csg_crop_objects_filtered(csg_ctx* c, const csg_crop_job* job, uint32_t rgb_filter, uint32_t n_frames,
+                              void* stream) {
+  static_assert(sizeof(CropSlot) == sizeof(csg_crop_info) && sizeof(csg_crop_info) == 32, "csg_crop_info layout");
+  static_assert(offsetof(CropSlot, side) == offsetof(csg_crop_info, side) &&
+                offsetof(CropSlot, frame) == offsetof(csg_crop_info, frame), "csg_crop_info layout");
+  if (!c) return CSG_ERR_INVALID;
+  if (!job) return c->fail(CSG_ERR_INVALID, "crop_objects: null job");
+  if (n_frames == 0) return c->fail(CSG_ERR_INVALID, "crop_objects: no frames");
+  if (rgb_filter != CSG_CROP_FILTER_BILINEAR && rgb_filter != CSG_CROP_FILTER_AREA)
+    return c->fail(CSG_ERR_INVALID, "crop_objects: rgb_filter %u is neither CSG_CROP_FILTER_BILINEAR nor _AREA",
+                   rgb_filter);
+  CSG_TRY(check_size(c, "crop_objects", job->size));
+  CSG_TRY(check_per_frame(c, "crop_objects", job->per_frame));
+  if (job->min_pixels < 1) return c->fail(CSG_ERR_INVALID, "crop_objects: min_pixels must be at least 1");
+  if (!std::isfinite(job->pad) || !(job->pad >= 1.0f))
+    return c->fail(CSG_ERR_INVALID, "crop_objects: pad %g is not a finite value >= 1", (double)job->pad);
+  if (!job->info) return c->fail(CSG_ERR_INVALID, "crop_objects: info is NULL");
+  if (!job->instance) return c->fail(CSG_ERR_INVALID, "crop_objects: the instance image is always needed");
+  if (job->crop_rgb && !job->rgb) return c->fail(CSG_ERR_INVALID, "crop_objects: crop_rgb needs rgb");
+  if (job->crop_coords && !job->obj_coords)
+    return c->fail(CSG_ERR_INVALID, "crop_objects: crop_coords needs obj_coords");
+  if (job->crop_depth && !job->depth) return c->fail(CSG_ERR_INVALID, "crop_objects: crop_depth needs depth");
+  if (!job->explicit_boxes && !job->inst_stats)
+    return c->fail(CSG_ERR_INVALID, "crop_objects: planning needs inst_stats (or explicit_boxes = 1)");
+  if (((uintptr_t)job->crop_rgb & 3u) || ((uintptr_t)job->crop_mask & 3u) || ((uintptr_t)job->crop_coords & 7u) ||
+      ((uintptr_t)job->crop_depth & 15u) || ((uintptr_t)job->info & 3u))
+    return c->fail(CSG_ERR_INVALID, "crop_objects: crop_rgb, crop_mask and info must be 4-byte aligned, crop_coords "
+                                    "8-byte, crop_depth 16-byte");
+  hipStream_t st;
+  CSG_TRY(pass_stream(c, stream, &st));
+  CropArgs a{};
+  a.W = c->cfg.width;
+  a.H = c->cfg.height;
+  a.S = job->size;
+  a.K = job->per_frame;
+  a.min_pixels = job->min_pixels;
+  a.pad = job->pad;
+  a.n_labels = job->n_labels;
+  a.explicit_boxes = job->explicit_boxes ? 1 : 0;
+  a.rgb_filter = rgb_filter;
+  a.rgb = job->rgb;
+  a.instance = job->instance;
+  a.obj_coords = job->obj_coords;
+  a.depth = job->depth;
+  a.stats = job->inst_stats;
+  a.eligible = job->eligible;
+  a.crop_rgb = job->crop_rgb;
+  a.crop_mask = job->crop_mask;
+  a.crop_coords = job->crop_coords;
+  a.crop_depth = job->crop_depth;
+  a.info = reinterpret_cast<CropSlot*>(job->info);
+  if (!a.explicit_boxes) launch_crop_plan(a, n_frames, st);
+  if (a.crop_rgb || a.crop_mask || a.crop_coords || a.crop_depth) launch_crop_sample(a, n_frames, st);
+  if (a.rgb_filter == CSG_CROP_FILTER_AREA && a.crop_rgb) launch_crop_area(a, n_frames, st);   // behind the plan
+  HIP_TRY(c, hipGetLastError());
+  return CSG_OK;
+}
+
+// Mask spans: a stand-alone pass over a device id image (no scene state, no work buffers); validates
+// the job, grows the pass's own count scratch and enqueues count, scan and emit.
+int csg_mask_spans(csg_ctx* c, const csg_span_job* job, uint32_t n_frames, void* stream) {
+  static_assert(sizeof(SpanRec) == sizeof(csg_span) && sizeof(csg_span) == 8, "csg_span layout");
+  static_assert(kSpanMaxLabels == CSG_SPAN_MAX_LABELS, "label limit");
+  if (!c) return CSG_ERR_INVALID;
+  if (!job) return c->fail(CSG_ERR_INVALID, "mask_spans: null job");
+  if (n_frames == 0) return c->fail(CSG_ERR_INVALID, "mask_spans: no frames");
+  if (!job->instance || !job->spans || !job->span_offsets)
+    return c->fail(CSG_ERR_INVALID, "mask_spans: instance, spans and span_offsets must not be NULL");
+  CSG_TRY(check_frame_dims(c, "mask_spans", job->width, job->height));
+  if (job->capacity == 0) return c->fail(CSG_ERR_INVALID, "mask_spans: capacity must be at least 1");
+  CSG_TRY(check_labels(c, "mask_spans", job->n_labels));
+  if (((uintptr_t)job->spans & 7u) || ((uintptr_t)job->span_offsets & 3u))
+    return c->fail(CSG_ERR_INVALID, "mask_spans: spans must be 8-byte aligned, span_offsets 4-byte");
+  hipStream_t st;
+  CSG_TRY(pass_stream(c, stream, &st));
+  SpanArgs a{};
+  a.W = job->width;
+  a.H = job->height;
+  a.L = job->n_labels;
+  a.G = (job->width + 63u) / 64u;
+  a.C = job->capacity;
+  a.instance = job->instance;
+  a.spans = reinterpret_cast<SpanRec*>(job->spans);
+  a.offsets = job->span_offsets;
+  const size_t n_cnt = (size_t)n_frames * a.L * a.G;
+  CSG_TRY(c->ms.begin(c, st, c->ms_cnt.n < n_cnt));
+  HIP_TRY(c, c->ms_cnt.alloc(n_cnt));
+  a.cnt = c->ms_cnt.p;
+  launch_span_count(a, n_frames, st);
+  launch_span_scan(a, n_frames, st);
+  launch_span_emit(a, n_frames, st);
+  HIP_TRY(c, hipGetLastError());
+  return c->ms.end(c, st);
+}
+
+// Object points: a stand-alone pass over device arrays (no scene state, no work buffers); validates the
+// job, grows the pass's own count scratch and enqueues count, scan and emit.
+int csg_sample_object_points(csg_ctx* c, const csg_point_job* job, uint32_t n_frames, void* stream) {
+  static_assert(kPointMaxLabels == CSG_SPAN_MAX_LABELS, "label limit");
+  if (!c) return CSG_ERR_INVALID;
+  if (!job) return c->fail(CSG_ERR_INVALID, "sample_object_points: null job");
+  if (n_frames == 0) return c->fail(CSG_ERR_INVALID, "sample_object_points: no frames");
+  CSG_TRY(check_frame_dims(c, "sample_object_points", job->width, job->height));
+  CSG_TRY(check_labels(c, "sample_object_points", job->n_labels));
+  CSG_TRY(check_per_frame(c, "sample_object_points", job->per_frame));
+  if (job->samples < 16 || job->samples > 16384 || (job->samples & 3u))
+    return c->fail(CSG_ERR_INVALID, "sample_object_points: samples %u is not a multiple of 4 in 16..16384",
+                   job->samples);
+  if (!job->instance || !job->info)
+    return c->fail(CSG_ERR_INVALID, "sample_object_points: instance and info are always needed");
+  if (!job->pt_count && !job->pt_choose && !job->pt_xyz && !job->pt_rgb && !job->pt_coords)
+    return c->fail(CSG_ERR_INVALID, "sample_object_points: no output");
+  if (job->pt_xyz && (!job->depth || !job->intrinsics))
+    return c->fail(CSG_ERR_INVALID, "sample_object_points: pt_xyz needs depth and intrinsics");
+  if (job->pt_rgb && !job->rgb) return c->fail(CSG_ERR_INVALID, "sample_object_points: pt_rgb needs rgb");
+  if (job->pt_coords && !job->obj_coords)
+    return c->fail(CSG_ERR_INVALID, "sample_object_points: pt_coords needs obj_coords");
+  if ((((uintptr_t)job->instance | (uintptr_t)job->info | (uintptr_t)job->depth | (uintptr_t)job->intrinsics |
+        (uintptr_t)job->frame_keys | (uintptr_t)job->pt_count | (uintptr_t)job->pt_choose | (uintptr_t)job->pt_xyz |
+        (uintptr_t)job->pt_rgb) & 3u) || (((uintptr_t)job->obj_coords | (uintptr_t)job->pt_coords) & 1u))
+    return c->fail(CSG_ERR_INVALID, "sample_object_points: obj_coords and pt_coords must be 2-byte aligned, every "
+                                    "other pointer but rgb 4-byte");
+  hipStream_t st;
+  CSG_TRY(pass_stream(c, stream, &st));
+  PointArgs a{};
+  a.W = job->width;
+  a.H = job->height;
+  a.P = job->width * job->height;
+  a.L = job->n_labels;
+  a.K = job->per_frame;
+  a.N = job->samples;
+  a.CH = (a.P + kPointChunk - 1u) / kPointChunk;
+  a.seed = job->seed;
+  a.instance = job->instance;
+  a.info = reinterpret_cast<const CropSlot*>(job->info);
+  a.depth = job->pt_xyz ? job->depth : nullptr;   // a source nobody asked for is never read
+  a.intrinsics = job->pt_xyz ? job->intrinsics : nullptr;
+  a.rgb = job->pt_rgb ? job->rgb : nullptr;
+  a.obj_coords = job->pt_coords ? job->obj_coords : nullptr;
+  a.frame_keys = job->frame_keys;
+  a.pt_count = job->pt_count;
+  a.pt_choose = job->pt_choose;
+  a.pt_xyz = job->pt_xyz;
+  a.pt_rgb = job->pt_rgb;
+  a.pt_coords = job->pt_coords;
+  const size_t n_tot = (size_t)n_frames * a.L, n_cnt = n_tot * a.CH;
+  CSG_TRY(c->op.begin(c, st, c->op_cnt.n < n_cnt + n_tot));
+  HIP_TRY(c, c->op_cnt.alloc(n_cnt + n_tot));
+  a.cnt = c->op_cnt.p;
+  a.total = c->op_cnt.p + n_cnt;
+  launch_pts_count(a, n_frames, st);
+  launch_pts_scan(a, n_frames, st);
+  launch_pts_emit(a, n_frames, st);
+  HIP_TRY(c, hipGetLastError());
+  return c->op.end(c, st);
+}
+
+// Amodal crop masks: reads the scene tables (synced here as a render syncs them) and the caller's
+// `info`; everything it writes besides the output is scratch of its own.
+int csg_crop_amodal(csg_ctx* c, const csg_amodal_job* job, uint32_t n_frames, void* stream) {
+  if (!c) return CSG_ERR_INVALID;
+  if (!job) return c->fail(CSG_ERR_INVALID, "crop_amodal: null job");
+  if (n_frames == 0) return c->fail(CSG_ERR_INVALID, "crop_amodal: no frames");
+  CSG_TRY(check_size(c, "crop_amodal", job->size));
+  CSG_TRY(check_per_frame(c, "crop_amodal", job->per_frame));
+  if (!job->frames) return c->fail(CSG_ERR_INVALID, "crop_amodal: frames is NULL");
+  if (!job->info) return c->fail(CSG_ERR_INVALID, "crop_amodal: info is NULL");
+  if (!job->crop_amodal) return c->fail(CSG_ERR_INVALID, "crop_amodal: crop_amodal is NULL");
+  if (((uintptr_t)job->crop_amodal & 3u) || ((uintptr_t)job->info & 3u))
+    return c->fail(CSG_ERR_INVALID, "crop_amodal: crop_amodal and info must be 4-byte aligned");
+  if (!c->have_scene) return c->fail(CSG_ERR_INVALID, "crop_amodal: no scene uploaded");
+  CSG_TRY(check_resident(c, "crop_amodal", job->frames, n_frames));
+  hipStream_t st;
+  CSG_TRY(pass_stream(c, stream, &st));
+  CSG_TRY(sync_scene_state(c));
+  const uint32_t S = job->size, K = job->per_frame, words = (S * S + 31u) / 32u;
+  const size_t n_bits = (size_t)n_frames * K * words;
+  CSG_TRY(am_begin(c, job->frames, n_frames, n_bits, 0, st));
+  HIP_TRY(c, hipMemsetAsync(c->am_bits.p, 0, n_bits * sizeof(uint32_t), st));
+  AmodalDev a{};
+  a.S = S;
+  a.K = K;
+  a.n_labels = c->n_lab;
+  a.n_sets = (uint32_t)c->set_valid.size();
+  a.words = words;
+  a.frames = c->am_frames.p;
+  a.info = reinterpret_cast<const CropSlot*>(job->info);
+  a.lab_off = c->lab_off.p;
+  a.lab_chunks = c->lab_chunks.p;
+  a.chunks = c->chunks.p;
+  a.models = c->models.p;
+  a.iset = c->iset.p;
+  a.bits = c->am_bits.p;
+  a.out = job->crop_amodal;
+  launch_crop_amodal(scene_dev(c), a, n_frames, c->lab_max_chunks, st);
+  HIP_TRY(c, hipGetLastError());
+  return c->am.end(c, st);
+}
+
+// Amodal depth and object coordinates: the same pass keeping, per sample, the largest 1/W instead of a
+// bit.  The keys (4 B per sample) live in crop_amodal_depth when it is given -- the finish pass converts
+// them in place --, else in scratch of the pass's own, bounded at kAmKeyCap bytes: the job then runs as
+// frame ranges on the stream, each zeroing, filling and finishing the same scratch.
+int csg_crop_amodal_geometry(csg_ctx* c, const csg_amodal_geometry_job* job, uint32_t n_frames, void* stream) {
+  constexpr size_t kAmKeyCap = 64u << 20;
+  if (!c) return CSG_ERR_INVALID;
+  if (!job) return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: null job");
+  if (n_frames == 0) return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: no frames");
+  CSG_TRY(check_size(c, "crop_amodal_geometry", job->size));
+  CSG_TRY(check_per_frame(c, "crop_amodal_geometry", job->per_frame));
+  if (!job->frames) return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: frames is NULL");
+  if (!job->info) return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: info is NULL");
+  if (!job->crop_amodal && !job->crop_amodal_depth && !job->crop_amodal_coords)
+    return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: crop_amodal, crop_amodal_depth and crop_amodal_coords "
+                                    "are all NULL");
+  if (((uintptr_t)job->crop_amodal & 3u) || ((uintptr_t)job->info & 3u) || ((uintptr_t)job->crop_amodal_depth & 15u) ||
+      ((uintptr_t)job->crop_amodal_coords & 7u))
+    return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: crop_amodal and info must be 4-byte aligned, "
+                                    "crop_amodal_coords 8-byte, crop_amodal_depth 16-byte");
+  if (!c->have_scene) return c->fail(CSG_ERR_INVALID, "crop_amodal_geometry: no scene uploaded");
+  CSG_TRY(check_resident(c, "crop_amodal_geometry", job->frames, n_frames));
+  hipStream_t st;
+  CSG_TRY(pass_stream(c, stream, &st));
+  CSG_TRY(sync_scene_state(c));
+  if (job->crop_amodal_coords) CSG_TRY(sync_object_frames(c));
+  const uint32_t S = job->size, K = job->per_frame;
+  const size_t per_frame = (size_t)K * S * S;   // samples, and keys, of one frame
+  uint32_t range = n_frames;                    // frames per range; the depth output holds every key
+  if (!job->crop_amodal_depth) {
+    size_t cap = kAmKeyCap;
+    if (const char* e = getenv("CSG_AMODAL_KEY_CAP")) cap = (size_t)strtoull(e, nullptr, 10);   // (tests: bytes)
+    range = (uint32_t)std::min<size_t>(n_frames, std::max<size_t>(1, cap / (per_frame * sizeof(uint32_t))));
+  }
+  CSG_TRY(am_begin(c, job->frames, n_frames, 0, job->crop_amodal_depth ? 0 : (size_t)range * per_frame, st));
+  AmodalDev a{};
+  a.S = S;
+  a.K = K;
+  a.n_labels = c->n_lab;
+  a.n_sets = (uint32_t)c->set_valid.size();
+  a.words = S * S;
+  a.lab_off = c->lab_off.p;
+  a.lab_chunks = c->lab_chunks.p;
+  a.chunks = c->chunks.p;
+  a.models = c->models.p;
+  a.iset = c->iset.p;
+  AmodalGeomOut g{};
+  g.W = c->cfg.width;
+  g.H = c->cfg.height;
+  g.table = c->of.p;
+  for (uint32_t f0 = 0; f0 < n_frames; f0 += range) {   // every array from the range's first frame
+    const uint32_t nf = std::min(range, n_frames - f0);
+    const size_t at = (size_t)f0 * per_frame;
+    a.frames = c->am_frames.p + f0;
+    a.info = reinterpret_cast<const CropSlot*>(job->info) + (size_t)f0 * K;
+    g.mask = job->crop_amodal ? job->crop_amodal + at : nullptr;
+    g.depth = job->crop_amodal_depth ? job->crop_amodal_depth + at : nullptr;
+    g.coords = job->crop_amodal_coords ? job->crop_amodal_coords + at * 3 : nullptr;
+    a.bits = g.depth ? reinterpret_cast<uint32_t*>(g.depth) : c->am_keys.p;
+    HIP_TRY(c, hipMemsetAsync(a.bits, 0, (size_t)nf * per_frame * sizeof(uint32_t), st));
+    launch_crop_amodal_geometry(scene_dev(c), a, g, nf, c->lab_max_chunks, st);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return c->am.end(c, st);
+}
+
+// Full-frame amodal spans: the scene tables and the caller's frames as the other amodal passes read
+// them; bit planes, counts and tables are scratch of the pass's own.  The planes are bounded at
+// kAmPlaneCap bytes: a job that needs more runs as frame ranges on the stream, each zeroing, filling and
+// reading the same scratch.
+int csg_amodal_spans(csg_ctx* c, const csg_amodal_span_job* job, uint32_t n_frames, void* stream) {
+  constexpr size_t kAmPlaneCap = 64u << 20;
+  if (!c) return CSG_ERR_INVALID;
+  if (!job) return c->fail(CSG_ERR_INVALID, "amodal_spans: null job");
+  if (n_frames == 0) return c->fail(CSG_ERR_INVALID, "amodal_spans: no frames");
+  if (!job->frames) return c->fail(CSG_ERR_INVALID, "amodal_spans: frames is NULL");
+  if (!job->spans || !job->span_offsets)
+    return c->fail(CSG_ERR_INVALID, "amodal_spans: spans and span_offsets must not be NULL");
+  if (job->capacity == 0) return c->fail(CSG_ERR_INVALID, "amodal_spans: capacity must be at least 1");
+  if (((uintptr_t)job->spans & 7u) || ((uintptr_t)job->span_offsets & 3u) || ((uintptr_t)job->amodal_stats & 3u))
+    return c->fail(CSG_ERR_INVALID, "amodal_spans: spans must be 8-byte aligned, span_offsets and amodal_stats 4-byte");
+  if (!c->have_scene) return c->fail(CSG_ERR_INVALID, "amodal_spans: no scene uploaded");
+  if (c->n_lab > CSG_SPAN_MAX_LABELS)
+    return c->fail(CSG_ERR_LIMIT, "amodal_spans: %u labels above CSG_SPAN_MAX_LABELS %u", c->n_lab, CSG_SPAN_MAX_LABELS);
+  CSG_TRY(check_resident(c, "amodal_spans", job->frames, n_frames));
+  hipStream_t st;
+  CSG_TRY(pass_stream(c, stream, &st));
+  CSG_TRY(sync_scene_state(c));
+  const uint32_t L = c->n_lab, W = c->cfg.width, H = c->cfg.height;
+  const uint32_t G = (W + 63u) / 64u, HW = (H + 31u) / 32u;
+  // the job's table: label -> plane, then one (chunk, plane) item per chunk of an eligible label, as all
+  // the items' chunks followed by all their planes
+  std::vector<uint32_t> tab(L, kNoPlane), items_p;
+  uint32_t P = 0;
+  for (uint32_t l = 0; l < L; ++l) {
+    if (job->eligible && !job->eligible[l]) continue;
+    tab[l] = P;
+    for (uint32_t k = c->h_lab_off[l]; k < c->h_lab_off[l + 1]; ++k) {
+      tab.push_back(c->h_lab_chunks[k]);
+      items_p.push_back(P);
+    }
+    ++P;
+  }
+  const uint32_t n_items = (uint32_t)items_p.size();
+  tab.insert(tab.end(), items_p.begin(), items_p.end());
+  const size_t n_tab = tab.size();
+  const size_t per_frame = (size_t)P * HW * W;   // words of one frame's planes
+  size_t cap = kAmPlaneCap;
+  if (const char* e = getenv("CSG_AMODAL_PLANE_CAP")) cap = (size_t)strtoull(e, nullptr, 10);   // (tests: bytes)
+  uint32_t range = std::min<uint32_t>(n_frames, 65535u);   // grid z limit
+  if (per_frame) range = (uint32_t)std::min<size_t>(range, std::max<size_t>(1, cap / (per_frame * sizeof(uint32_t))));
+  const size_t n_planes = (size_t)range * per_frame, n_touched = (size_t)range * std::max(P, 1u);
+  const size_t n_cnt = (size_t)range * L * G;
+  CSG_TRY(c->am.begin(c, st, c->as_planes.n < n_planes || c->as_touched.n < n_touched || c->as_cnt.n < n_cnt ||
+                              c->as_tables.n < n_tab || c->am_frames.n < n_frames));
+  HIP_TRY(c, c->as_planes.alloc(n_planes));
+  HIP_TRY(c, c->as_touched.alloc(n_touched));
+  HIP_TRY(c, c->as_cnt.alloc(n_cnt));
+  HIP_TRY(c, c->as_tables.alloc(n_tab));
+  HIP_TRY(c, c->am_frames.alloc(n_frames));
+  CSG_TRY(am_stage_frames(c, job->frames, n_frames, st));
+  HIP_TRY(c, c->as_stage.upload(c->as_tables.p, n_tab, st,
+                                [&](uint32_t* h) { memcpy(h, tab.data(), sizeof(uint32_t) * n_tab); }));
+  AmodalSpanDev a{};
+  a.W = W;
+  a.H = H;
+  a.L = L;
+  a.P = P;
+  a.G = G;
+  a.HW = HW;
+  a.C = job->capacity;
+  a.n_sets = (uint32_t)c->set_valid.size();
+  a.n_items = n_items;
+  a.plane_of = c->as_tables.p;
+  a.item_chunk = c->as_tables.p + L;
+  a.item_plane = c->as_tables.p + L + n_items;
+  a.chunks = c->chunks.p;
+  a.models = c->models.p;
+  a.iset = c->iset.p;
+  a.planes = c->as_planes.p;
+  a.touched = c->as_touched.p;
+  a.cnt = c->as_cnt.p;
+  for (uint32_t f0 = 0; f0 < n_frames; f0 += range) {   // every array from the range's first frame
+    const uint32_t nf = std::min(range, n_frames - f0);
+    a.frames = c->am_frames.p + f0;
+    a.spans = reinterpret_cast<SpanRec*>(job->spans) + (size_t)f0 * a.C;
+    a.offsets = job->span_offsets + (size_t)f0 * (L + 1u);
+    a.stats = job->amodal_stats ? job->amodal_stats + (size_t)f0 * L * 5u : nullptr;
+    if (per_frame) HIP_TRY(c, hipMemsetAsync(a.planes, 0, (size_t)nf * per_frame * sizeof(uint32_t), st));
+    HIP_TRY(c, hipMemsetAsync(a.touched, 0, n_touched * sizeof(uint32_t), st));
+    launch_amodal_spans(scene_dev(c), a, nf, st);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return c->am.end(c, st);
+}
+
+}  // extern "C"

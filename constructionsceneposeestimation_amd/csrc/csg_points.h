@@ -1,5 +1,5 @@
 // csg_points.h — host launchers of the object-point kernels (csg_points.hip),
-// called by csg_api.cpp for csg_sample_object_points.
+// called by csg_passes.cpp for csg_sample_object_points.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

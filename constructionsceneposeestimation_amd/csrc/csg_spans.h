@@ -1,5 +1,5 @@
 // csg_spans.h — host launchers of the mask-span kernels (csg_spans.hip),
-// called by csg_api.cpp for csg_mask_spans.
+// called by csg_passes.cpp for csg_mask_spans.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -314,10 +314,15 @@ def test_arguments(cone):
                      size_large=dict(size=516), size_odd=dict(size=18), k_zero=dict(per_frame=0),
                      k_large=dict(per_frame=65), misaligned=dict(crop_amodal=out.data_ptr() + 2),
                      set_not_resident=dict(frames=bad_set.ctypes.data))
+        exact = dict(size_odd="crop_amodal: size 18 is not a multiple of 4 in 16..512",   # shared checks: whole text
+                     k_large="crop_amodal: per_frame 65 outside 1..64",
+                     set_not_resident="crop_amodal: frame 0: transform set 1 is not resident (1 sets)")
         for name, kw in cases.items():
             assert call(r.ctx, **kw) == -1, name
             msg = lib.csg_last_error(r.ctx).decode()
             assert msg.startswith("crop_amodal:"), (name, msg)
+            if name in exact:
+                assert msg == exact[name], name
         r.synchronize()
         assert (out.cpu().numpy() == FILL).all()              # nothing was enqueued
         assert call(r.ctx) == 0                               # the same call without a fault is accepted

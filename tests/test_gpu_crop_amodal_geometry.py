@@ -404,10 +404,15 @@ def test_arguments(cone):
                      depth_misaligned=dict(crop_amodal_depth=good["crop_amodal_depth"] + 8),
                      coords_misaligned=dict(crop_amodal_coords=good["crop_amodal_coords"] + 4),
                      set_not_resident=dict(frames=bad_set.ctypes.data))
+        exact = dict(size_odd="crop_amodal_geometry: size 18 is not a multiple of 4 in 16..512",   # shared checks
+                     k_large="crop_amodal_geometry: per_frame 65 outside 1..64",
+                     set_not_resident="crop_amodal_geometry: frame 0: transform set 1 is not resident (1 sets)")
         for name, kw in cases.items():
             assert call(r.ctx, **kw) == -1, name
             msg = lib.csg_last_error(r.ctx).decode()
             assert msg.startswith("crop_amodal_geometry:"), (name, msg)
+            if name in exact:
+                assert msg == exact[name], name
         r.synchronize()
         for name, t in bufs.items():
             assert (t.cpu().numpy() == FILL).all(), f"{name} was written by a refused call"

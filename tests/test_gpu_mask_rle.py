@@ -84,6 +84,39 @@ def test_many_frames_and_a_wide_image(ctx):
     _check(_run(ctx, ids, 4, top + 3), ref, top + 3, "7 frames of 9 x 200")
 
 
+def test_scratch_growth_across_two_streams(cone):
+    """Three jobs back to back without a host synchronisation, each with outputs of its own, on a fresh
+    context: a small one on the context's stream; one on a second stream whose count scratch grows from 4
+    to 2,304 words (the pass waits on the host for the first); the small one again on the context's stream
+    (nothing grows, the stream differs: it waits on the device for the second)."""
+    import torch
+    from constructionsceneposeestimation_amd.renderer import Renderer
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(11)
+    small = rng.integers(-1, 2, (1, 9, 70)).astype(np.int32)
+    big = rng.integers(-1, LIMIT, (3, 67, 130)).astype(np.int32)
+    jobs = [(small, 2), (big, LIMIT), (small, 2)]
+    assert [len(i) * L * ((i.shape[2] + 63) // 64) for i, L in jobs] == [4, 2304, 4]
+    refs = [[restate_spans(x, L) for x in ids] for ids, L in jobs]
+    caps = [max(int(o[-1]) for o, _ in ref) + 3 for ref in refs]
+    bufs = [(torch.from_numpy(ids).to(dev), _filled((len(ids) * cap + GUARD, 2)), _filled((len(ids), L + 1)))
+            for (ids, L), cap in zip(jobs, caps)]
+    torch.cuda.synchronize(dev)                       # inputs and prefill are in place
+    with Renderer(cone, 64, 64, max_frames=1) as r:
+        side = torch.cuda.Stream(dev)
+        for k, ((ids, L), cap, (d_ids, d_sp, d_off)) in enumerate(zip(jobs, caps, bufs)):
+            r.mask_spans(len(ids), instance=d_ids.data_ptr(), spans=d_sp.data_ptr(), span_offsets=d_off.data_ptr(),
+                         capacity=cap, n_labels=L, height=ids.shape[1], width=ids.shape[2],
+                         stream=side.cuda_stream if k == 1 else 0)
+        side.synchronize()
+        r.synchronize()
+        for k, ((ids, L), cap, (_, d_sp, d_off), ref) in enumerate(zip(jobs, caps, bufs, refs)):
+            n = len(ids)
+            sp = d_sp.cpu().numpy().view(np.uint32)
+            _check((d_off.cpu().numpy().view(np.uint32), sp[:n * cap].reshape(n, cap, 2), sp[n * cap:]), ref, cap,
+                   f"job {k}")
+
+
 def test_host_delivery_of_empty_and_uneven_frames(ctx):
     import torch
     ids = np.full((3, 6, 70), -1, np.int32)
@@ -121,6 +154,12 @@ def test_argument_checks(ctx):
         assert call(**kw) == INVALID, kw
     assert call(n_labels=LIMIT + 1) == LIMIT_ERR
     assert b"CSG_SPAN_MAX_LABELS" in ctx.lib.csg_last_error(ctx.ctx)
+    # the texts of the checks this entry point shares with others, byte for byte
+    assert ctx.lib.csg_last_error(ctx.ctx) == b"mask_spans: n_labels 257 above CSG_SPAN_MAX_LABELS 256"
+    assert call(n_labels=0) == INVALID
+    assert ctx.lib.csg_last_error(ctx.ctx) == b"mask_spans: n_labels must be at least 1"
+    assert call(width=8193) == INVALID
+    assert ctx.lib.csg_last_error(ctx.ctx) == b"mask_spans: frame 8193 x 5 outside 1..8192"
     with pytest.raises(_lib.CsgError):
         ctx.mask_spans(1, instance=d_ids.data_ptr(), spans=d_sp.data_ptr(), span_offsets=d_off.data_ptr(), capacity=0,
                        n_labels=L, height=H, width=W)

@@ -348,6 +348,12 @@ def test_arguments(small):
     with pytest.raises(CsgError, match="status -1: crop_objects"):
         small["r"].crop_objects(0, size=S, per_frame=K, instance=small["dev"]["instance"].data_ptr(), info=ip,
                                 explicit=True)
+    r = small["r"]                                    # the texts of the checks shared with other entry points
+    for size, per_frame, text in ((18, K, b"crop_objects: size 18 is not a multiple of 4 in 16..512"),
+                                  (S, 65, b"crop_objects: per_frame 65 outside 1..64")):
+        with pytest.raises(CsgError):
+            _crop_small(small, size, per_frame, bufs, ip)
+        assert r.lib.csg_last_error(r.ctx) == text
     untouched = _to_host(bufs)
     assert all((untouched[k] == 7).all() for k in IMAGES)                # the refused calls wrote nothing
     _crop_small(small, S, K, bufs, ip)

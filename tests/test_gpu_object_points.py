@@ -157,6 +157,44 @@ def test_repeatable_on_any_stream_any_subset_and_any_alignment(ctx):
         _check(_run(ctx, ids, labels, L, N, seed=2, names=("pt_count", "pt_choose"), lead=lead), exp, f"lead {lead}")
 
 
+def test_scratch_growth_across_two_streams(cone):
+    """Three jobs back to back without a host synchronisation, each with outputs of its own, on a fresh
+    context: a small one on the context's stream; a large one on a second stream, whose count scratch
+    grows (the pass waits on the host for the first); the small one again on the context's stream (nothing
+    grows, the stream differs: it waits on the device for the second)."""
+    import torch
+    from constructionsceneposeestimation_amd.renderer import Renderer
+    N = 16
+    rng = np.random.default_rng(12)
+
+    def job(names, H, W, L, K, seed):
+        pats = patterns(H, W, L, N)
+        ids = np.stack([pats[k][0] for k in names])
+        labels = np.stack([slot_labels(K, L, pats[k][1], rng) for k in names])
+        src = random_sources(len(names), H, W, rng)
+        return dict(ids=ids, labels=labels, L=L, K=K, seed=seed, src=src,
+                    exp=restate_points(ids, labels, L, N, seed=seed, **src))
+
+    small = job(["random"], 9, 200, 4, 1, 3)
+    big = job(["random", "checkerboard", f"count_{2 * N - 1}"], 130, 517, 256, 64, 5)
+    jobs = [small, big, small]
+    keep = [{"instance": _dev(j["ids"]), "info": _dev(_info(j["labels"])), **{k: _dev(v) for k, v in j["src"].items()}}
+            for j in jobs]
+    bufs = [_out_buffers(NAMES, len(j["ids"]), j["K"], N) for j in jobs]
+    torch.cuda.synchronize()                          # inputs and prefill are in place
+    with Renderer(cone, 64, 64, max_frames=1) as r:
+        side = torch.cuda.Stream(torch.device("cuda", 0))
+        for k, (j, src, out) in enumerate(zip(jobs, keep, bufs)):
+            n, H, W = j["ids"].shape
+            r.sample_points(n, samples=N, per_frame=j["K"], seed=j["seed"], n_labels=j["L"], height=H, width=W,
+                            stream=side.cuda_stream if k == 1 else 0, **{a: p for a, (_, p) in src.items()},
+                            **{a: t.data_ptr() for a, t in out.items()})
+        side.synchronize()
+        r.synchronize()
+        for k, (j, out) in enumerate(zip(jobs, bufs)):
+            _check(_to_host(out, len(j["ids"]), j["K"], N, f"job {k}"), j["exp"], f"job {k}")
+
+
 def test_frame_keys(ctx):
     H, W, L, N, K = 67, 131, 256, 16, 64
     pats = patterns(H, W, L, N)
@@ -212,6 +250,14 @@ def test_argument_checks(ctx):
         assert call(**{name: ok[name] + step}) == INVALID, name
     assert call(n_labels=257) == LIMIT_ERR
     assert b"CSG_SPAN_MAX_LABELS" in ctx.lib.csg_last_error(ctx.ctx)
+    # the texts of the checks this entry point shares with others, byte for byte
+    assert ctx.lib.csg_last_error(ctx.ctx) == b"sample_object_points: n_labels 257 above CSG_SPAN_MAX_LABELS 256"
+    assert call(n_labels=0) == INVALID
+    assert ctx.lib.csg_last_error(ctx.ctx) == b"sample_object_points: n_labels must be at least 1"
+    assert call(height=0) == INVALID
+    assert ctx.lib.csg_last_error(ctx.ctx) == b"sample_object_points: frame 3 x 0 outside 1..8192"
+    assert call(per_frame=65) == INVALID
+    assert ctx.lib.csg_last_error(ctx.ctx) == b"sample_object_points: per_frame 65 outside 1..64"
     with pytest.raises(_lib.CsgError):
         ctx.sample_points(1, samples=N, per_frame=K, instance=ok["instance"], info=ok["info"], pt_rgb=ok["pt_rgb"],
                           n_labels=L, height=H, width=W)                           # pt_rgb without rgb

@@ -35,7 +35,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-PLANE_CAP = 64 << 20   # csg_amodal_spans' default scratch bound (csg_api.cpp)
+PLANE_CAP = 64 << 20   # csg_amodal_spans' default scratch bound (csg_passes.cpp)
 
 
 def build_count_lib(path):

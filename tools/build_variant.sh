@@ -1,7 +1,8 @@
 #!/bin/bash
 # Build an A/B variant of libcsg.so into constructionsceneposeestimation_amd/libcsg_<name>.so:
 # the kernels (csg_kernels.hip/.h) from git revision <rev> ("-" = working tree)
-# with the working tree's C-ABI host code, plus extra hipcc flags.
+# with the working tree's other sources -- the whole csrc directory, compiled
+# from the source list build.py exports --, plus extra hipcc flags.
 #   tools/build_variant.sh base HEAD          tools/build_variant.sh occ6 - -DCSG_OCC=6
 # Use with CSG_LIB=<path> (see _lib.py).
 set -e
@@ -9,13 +10,16 @@ cd "$(dirname "$0")/.."
 name=$1; rev=${2:--}; shift 2 || true
 src=constructionsceneposeestimation_amd/csrc
 tmp=$(mktemp -d)
-mkdir -p $tmp/pkg/csrc $tmp/include
+mkdir -p $tmp/pkg $tmp/include
 cp include/csg_api.h $tmp/include/
-cp $src/csg_api.cpp $src/csg_kernels.hip $src/csg_kernels.h $src/csg_encode.hip $src/csg_encode.h $src/csg_deflate.h $src/csg_widen.h $tmp/pkg/csrc/
+cp -r $src $tmp/pkg/csrc
 if [ "$rev" != "-" ]; then
   for f in csg_kernels.hip csg_kernels.h; do git show $rev:$src/$f > $tmp/pkg/csrc/$f; done
 fi
+sources=$(python3 -c "import os
+from constructionsceneposeestimation_amd.build import SOURCES
+print(' '.join(os.path.join('$tmp/pkg/csrc', os.path.basename(s)) for s in SOURCES))")
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -shared -ffp-contract=off --offload-arch=gfx950 -Wall -pthread "$@" \
-  -o constructionsceneposeestimation_amd/libcsg_$name.so $tmp/pkg/csrc/csg_kernels.hip $tmp/pkg/csrc/csg_encode.hip $tmp/pkg/csrc/csg_api.cpp
+  -o constructionsceneposeestimation_amd/libcsg_$name.so $sources
 rm -rf $tmp
 echo built constructionsceneposeestimation_amd/libcsg_$name.so
