@@ -32,6 +32,7 @@ EXPORTED = (
     "csg_get_work_info", "csg_host_id_bytes", "csg_set_object_frames", "csg_crop_objects", "csg_encode_files",
     "csg_crop_objects_filtered", "csg_crop_amodal", "csg_crop_amodal_geometry", "csg_mask_spans",
     "csg_keep_instance", "csg_last_instance", "csg_amodal_spans", "csg_sample_object_points",
+    "csg_encode_span_masks",
 )
 
 
@@ -143,6 +144,13 @@ class AmodalSpanJob(C.Structure):
                 ("span_offsets", C.c_void_p), ("amodal_stats", C.c_void_p)]
 
 
+class MaskPngJob(C.Structure):
+    """csg_mask_png_job (csg_encode_span_masks)."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n_frames", C.c_uint32), ("n_labels", C.c_uint32),
+                ("capacity", C.c_uint32), ("n_items", C.c_uint32), ("spans", C.c_void_p), ("span_offsets", C.c_void_p),
+                ("items", C.c_void_p), ("out", C.c_void_p), ("out_capacity", C.c_uint64), ("file_offsets", C.c_void_p)]
+
+
 class PointJob(C.Structure):
     """csg_point_job (csg_sample_object_points)."""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n_labels", C.c_uint32), ("per_frame", C.c_uint32),
@@ -234,6 +242,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     lib.csg_mask_spans.argtypes = [vp, C.POINTER(SpanJob), u32, vp]
     lib.csg_amodal_spans.argtypes = [vp, C.POINTER(AmodalSpanJob), u32, vp]
     lib.csg_sample_object_points.argtypes = [vp, C.POINTER(PointJob), u32, vp]
+    lib.csg_encode_span_masks.argtypes = [vp, C.POINTER(MaskPngJob), vp]
     lib.csg_keep_instance.argtypes = [vp, i32]
     lib.csg_last_instance.argtypes = [vp, C.POINTER(vp), C.POINTER(u32)]
     if lib.csg_abi_version() != ABI_VERSION:

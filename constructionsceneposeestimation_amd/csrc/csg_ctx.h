@@ -13,6 +13,7 @@
 #include "../../include/csg_api.h"
 #include "csg_encode.h"
 #include "csg_kernels.h"
+#include "csg_mask_png.h"
 
 namespace csg {
 
@@ -303,6 +304,15 @@ struct csg_ctx {
   // the totals [n][L] behind them, grown to the job, under an order of its own.
   DevBuf<uint32_t> op_cnt;
   csg::PassOrder op;
+  // Mask PNGs (csg_encode_span_masks): the pass's own scratch -- the items behind their staging slot, and
+  // of one range of items the bit planes, the per-row numbers, the per-file layout and the zlib staging --
+  // grown to the job, under an order of its own.
+  DevBuf<csg::MaskItem> mp_items;
+  csg::StageSlot<csg::MaskItem> mp_stage;
+  DevBuf<uint32_t> mp_planes, mp_rows;
+  DevBuf<csg::MaskFile> mp_files;
+  DevBuf<uint8_t> mp_z;
+  csg::PassOrder mp;
   // csg_keep_instance / csg_last_instance: host-output batches keep their ids on the device
   bool keep_ids = false;
   const int32_t* last_inst = nullptr;

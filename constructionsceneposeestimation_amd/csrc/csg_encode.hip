@@ -46,6 +46,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "csg_bitio.h"
 #include "csg_deflate.h"
 #include "csg_encode.h"
 
@@ -473,39 +474,6 @@ __global__ void k_file_layout(const uint64_t* __restrict__ fsize, uint32_t n_fil
 // ---------------------------------------------------------------------------
 // PNG emission
 // ---------------------------------------------------------------------------
-// LSB-first bits into zeroed staging words from bit `pos`: the first word
-// (possibly shared with the previous row) and the last (possibly shared with
-// the next) with atomicOr, words in between with plain stores.
-struct WordBits {
-  uint32_t* w;
-  uint64_t acc;
-  uint32_t n, wi;
-  bool first;
-  __device__ void init(uint32_t* words, uint32_t pos) {
-    w = words;
-    wi = pos >> 5;
-    n = pos & 31u;
-    acc = 0;
-    first = true;
-  }
-  __device__ __forceinline__ void put(uint32_t v, uint32_t len) {
-    acc |= (uint64_t)v << n;
-    n += len;
-    if (n >= 32u) {
-      const uint32_t word = (uint32_t)acc;
-      if (first) atomicOr(&w[wi], word);
-      else w[wi] = word;
-      first = false;
-      ++wi;
-      acc >>= 32;
-      n -= 32u;
-    }
-  }
-  __device__ void finish() {
-    if (n) atomicOr(&w[wi], (uint32_t)acc);
-  }
-};
-
 template <uint32_t kBpp>
 __global__ __launch_bounds__(kRowsPerBlock) void k_png_emit(const uint8_t* __restrict__ img, uint32_t W, uint32_t H,
                                                             const EncPng* __restrict__ png,
@@ -558,50 +526,6 @@ __global__ __launch_bounds__(64) void k_png_ends(const EncPng* __restrict__ png,
     if (at & 3u) atomicOr(&words[(at >> 2) + 1], (uint32_t)(sv >> 32));
   }
 }
-
-// Bytes to an arbitrary offset: byte stores up to a dword boundary, then
-// whole dwords, the tail again as bytes.
-struct ByteOut {
-  uint8_t* base;
-  uint64_t pos;
-  uint32_t acc, na;
-  __device__ void init(uint8_t* b, uint64_t p) {
-    base = b;
-    pos = p;
-    acc = 0;
-    na = 0;
-  }
-  __device__ __forceinline__ void put(uint32_t c) {
-    if (na == 0 && (pos & 3u)) {
-      base[pos++] = (uint8_t)c;
-      return;
-    }
-    acc |= (c & 255u) << (8u * na);
-    ++pos;
-    if (++na == 4u) {
-      *reinterpret_cast<uint32_t*>(base + pos - 4u) = acc;
-      acc = 0;
-      na = 0;
-    }
-  }
-  __device__ void be32(uint32_t v) {
-    put(v >> 24);
-    put((v >> 16) & 255u);
-    put((v >> 8) & 255u);
-    put(v & 255u);
-  }
-  __device__ void finish() {
-    for (uint32_t k = 0; k < na; ++k) base[pos - na + k] = (uint8_t)(acc >> (8u * k));
-    na = 0;
-    acc = 0;
-  }
-};
-
-struct Crc {
-  const uint32_t* T;
-  uint32_t c;
-  __device__ __forceinline__ void add(uint32_t b) { c = T[(c ^ b) & 255u] ^ (c >> 8); }
-};
 
 __global__ __launch_bounds__(64) void k_png_pack(const EncPng* __restrict__ png, const uint8_t* __restrict__ zbuf,
                                                  const uint64_t* __restrict__ zbase, uint8_t* out,

@@ -1,5 +1,5 @@
-// The stand-alone passes of libcsg.so (see include/csg_api.h): object crops, mask spans, object points
-// and the three amodal passes.  Each validates its job on the host, orders itself behind the last pass
+// The stand-alone passes of libcsg.so (see include/csg_api.h): object crops, mask spans, mask PNGs, object
+// points and the three amodal passes.  Each validates its job on the host, orders itself behind the last pass
 // that used its scratch (PassOrder, csg_ctx.h), grows that scratch and enqueues its kernels on the
 // caller's stream.  None of them touches a render's work buffers.
 #include <stdlib.h>
@@ -180,6 +180,77 @@ int csg_mask_spans(csg_ctx* c, const csg_span_job* job, uint32_t n_frames, void*
   launch_span_emit(a, n_frames, st);
   HIP_TRY(c, hipGetLastError());
   return c->ms.end(c, st);
+}
+
+// Mask PNGs: a stand-alone pass over the span arrays (no scene state, no work buffers); validates the
+// job, uploads the items, grows the pass's own scratch and enqueues the kernels.  The bit planes are
+// bounded at kMaskPlaneCap bytes: a job that needs more runs as ranges of items on the stream, each
+// filling and reading the same scratch and continuing file_offsets where the last one ended.
+int csg_encode_span_masks(csg_ctx* c, const csg_mask_png_job* job, void* stream) {
+  constexpr size_t kMaskPlaneCap = 64u << 20;
+  static_assert(sizeof(MaskItem) == sizeof(csg_mask_item) && sizeof(csg_mask_item) == 8, "csg_mask_item layout");
+  if (!c) return CSG_ERR_INVALID;
+  if (!job) return c->fail(CSG_ERR_INVALID, "encode_span_masks: null job");
+  if (!job->spans || !job->span_offsets || !job->items || !job->out || !job->file_offsets)
+    return c->fail(CSG_ERR_INVALID, "encode_span_masks: spans, span_offsets, items, out and file_offsets must not "
+                                    "be NULL");
+  if (job->n_frames == 0) return c->fail(CSG_ERR_INVALID, "encode_span_masks: no frames");
+  if (job->n_items == 0) return c->fail(CSG_ERR_INVALID, "encode_span_masks: no items");
+  CSG_TRY(check_frame_dims(c, "encode_span_masks", job->width, job->height));
+  if (job->capacity == 0) return c->fail(CSG_ERR_INVALID, "encode_span_masks: capacity must be at least 1");
+  CSG_TRY(check_labels(c, "encode_span_masks", job->n_labels));
+  if (((uintptr_t)job->spans & 7u) || ((uintptr_t)job->span_offsets & 3u) || ((uintptr_t)job->file_offsets & 7u))
+    return c->fail(CSG_ERR_INVALID, "encode_span_masks: spans and file_offsets must be 8-byte aligned, span_offsets "
+                                    "4-byte");
+  for (uint32_t i = 0; i < job->n_items; ++i)
+    if (job->items[i].frame >= job->n_frames || job->items[i].label >= job->n_labels)
+      return c->fail(CSG_ERR_INVALID, "encode_span_masks: item %u names frame %u of %u, label %u of %u", i,
+                     job->items[i].frame, job->n_frames, job->items[i].label, job->n_labels);
+  hipStream_t st;
+  CSG_TRY(pass_stream(c, stream, &st));
+  MaskPngArgs a{};
+  a.W = job->width;
+  a.H = job->height;
+  a.L = job->n_labels;
+  a.C = job->capacity;
+  a.KW = 2u * ((a.W + 63u) / 64u);
+  const size_t per_item = (size_t)a.KW * a.H;   // words of one item's plane
+  size_t cap = kMaskPlaneCap;
+  if (const char* e = getenv("CSG_MASK_PNG_PLANE_CAP")) cap = (size_t)strtoull(e, nullptr, 10);   // (tests: bytes)
+  const uint32_t range = (uint32_t)std::min<size_t>(std::min<uint32_t>(job->n_items, 65535u),   // grid y limit
+                                                    std::max<size_t>(1, cap / (per_item * sizeof(uint32_t))));
+  // the streams of a range that fits out_capacity fit the staging: each is shorter than its file, and
+  // starts at a multiple of 4
+  const uint64_t worst = ((uint64_t)mpng::max_zlib_bytes(a.W, a.H) + 3u) & ~3ull;
+  const uint64_t zcap = (std::min<uint64_t>(job->out_capacity + 4ull * range, worst * range) + 15u) & ~15ull;
+  const size_t n_planes = (size_t)range * per_item, n_rows = (size_t)3 * range * a.H;
+  CSG_TRY(c->mp.begin(c, st, c->mp_items.n < job->n_items || c->mp_planes.n < n_planes || c->mp_rows.n < n_rows ||
+                              c->mp_files.n < range + 1u || c->mp_z.n < zcap));
+  HIP_TRY(c, c->mp_items.alloc(job->n_items));
+  HIP_TRY(c, c->mp_planes.alloc(n_planes));
+  HIP_TRY(c, c->mp_rows.alloc(n_rows));
+  HIP_TRY(c, c->mp_files.alloc(range + 1u));
+  HIP_TRY(c, c->mp_z.alloc(zcap));
+  HIP_TRY(c, c->mp_stage.upload(c->mp_items.p, job->n_items, st,
+                                [&](MaskItem* h) { memcpy(h, job->items, sizeof(MaskItem) * job->n_items); }));
+  a.spans = reinterpret_cast<const SpanRec*>(job->spans);
+  a.offsets = job->span_offsets;
+  a.items = c->mp_items.p;
+  a.planes = c->mp_planes.p;
+  a.rows = c->mp_rows.p;
+  a.files = c->mp_files.p;
+  a.zbuf = c->mp_z.p;
+  a.zcap = zcap;
+  a.out = job->out;
+  a.out_capacity = job->out_capacity;
+  a.file_offsets = job->file_offsets;
+  for (uint32_t i0 = 0; i0 < job->n_items; i0 += range) {
+    a.first = i0;
+    a.n = std::min(range, job->n_items - i0);
+    launch_mask_png(a, st);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return c->mp.end(c, st);
 }
 
 // Object points: a stand-alone pass over device arrays (no scene state, no work buffers); validates the

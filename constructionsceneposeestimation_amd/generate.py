@@ -33,6 +33,13 @@ same files:
   obj_coords/obj_coords_%06d.npy   (object coordinates / NOCS, H x W x 3 uint16, optional; no
                                     reference counterpart) + obj_coords/objects.json (each
                                     object's prim_path, class_name, inst_idx and box lo / hi)
+  train_pbr/%06d/{rgb,depth,mask,mask_visib}/ + bop/frag_%06d.json
+                                   (optional "bop": the BOP dataset layout, bop.py -- scene = frame // 1000;
+                                    RGB and 16-bit depth PNGs, one mask_visib and one amodal mask PNG per
+                                    listed object made on the GPU from the spans, and per-frame fragments
+                                    that ``python -m constructionsceneposeestimation_amd.bop merge RUN_DIR``
+                                    joins into scene_camera / scene_gt / scene_gt_info.json; no reference
+                                    counterpart)
   logs/generation_summary.json     (:2090; statistics, frame_logs, counters)
   logs/generation_detail.log       (:254-263, per-frame entries + report)
 
@@ -59,6 +66,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
+from . import bop
 from . import camera_math as cm
 from . import masks
 from . import prep_pool
@@ -95,6 +103,10 @@ OUTPUTS = ("rgb", "mask", "depth_csv", "depth_png", "depth_npy", "pointcloud", "
 # JET depth PNG, point-cloud TXT, instance mask .npy; the label JSON is always written (it is the
 # resume marker).
 REFERENCE_OUTPUTS = ("rgb", "mask", "depth_csv", "depth_png", "pointcloud")
+# The BOP dataset layout (bop.py): an output kind of its own, not part of "all" -- it brings its own
+# image, depth and mask files and does not go with the other per-object mask outputs.
+BOP_OUTPUT = "bop"
+BOP_EXCLUDES = ("mask", "mask_rle", "amodal_rle")
 
 
 # outputs encoded on the GPU in thread mode -> their csg_outputs.file_kinds kind (_lib.FILE_KINDS)
@@ -119,12 +131,19 @@ def parse_outputs(spec: str) -> tuple:
     if spec == "all":
         return OUTPUTS
     out = tuple(x.strip() for x in spec.split(",") if x.strip())
-    bad = [x for x in out if x not in OUTPUTS]
+    bad = [x for x in out if x not in OUTPUTS + (BOP_OUTPUT,)]
     if bad:
-        raise ValueError(f"unknown outputs {bad}; choose from {OUTPUTS}")
+        raise ValueError(f"unknown outputs {bad}; choose from {OUTPUTS + (BOP_OUTPUT,)}")
+    check_bop(out)
     if "amodal_rle" in out and "mask_rle" not in out:
         raise ValueError("output amodal_rle adds to the annotations of mask_rle: ask for both")
     return out
+
+
+def check_bop(outs) -> None:
+    clash = [x for x in BOP_EXCLUDES if x in outs] if BOP_OUTPUT in outs else []
+    if clash:
+        raise ValueError(f"output bop writes its own per-object masks: it does not go with {clash}")
 
 
 def render_outputs(outs: set, gpu_files: bool, host_depth: bool, occlusion: bool) -> list:
@@ -190,6 +209,13 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
     ``amodal_segmentation``, the object's full silhouette as if nothing stood in
     front of it, from one more pass over the scene behind each batch
     (Renderer.amodal_spans_host).
+    ``outputs`` with "bop": the BOP dataset layout (bop.py) under
+    ``train_pbr/``: RGB and 16-bit depth PNGs from the GPU encoders, one
+    ``mask_visib`` and one ``mask`` PNG per listed object made on the GPU from
+    the visible and the amodal spans (Renderer.mask_pngs_host), and a fragment
+    ``bop/frag_%06d.json`` per frame for ``python -m ...bop merge``.  Listed
+    are the objects of ``amodal_kinds`` with amodal pixels.  Thread writers
+    only; not with "mask", "mask_rle" or "amodal_rle".
     ``prep_workers``: processes that prepare batches ahead (epoch layouts,
     object poses, cameras; prep_pool.py), so that numpy work does not hold
     this process's GIL; -1 = two for runs of at least 20 batches, else none."""
@@ -204,7 +230,17 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
         outs.add("pointcloud")
     if normals:
         outs.add("normals")
+    check_bop(outs)
+    want_bop = BOP_OUTPUT in outs
+    if want_bop:
+        if writer_mode != "thread":
+            raise ValueError("output bop needs the GPU file encoders: writer_mode 'thread'")
+        s16 = float(depth16_counts_per_metre)
+        if not (np.isfinite(s16) and s16 > 0):
+            raise ValueError(f"depth16_counts_per_metre {depth16_counts_per_metre!r}: a finite number > 0")
     wl = Workload(workload, seed=seed, width=width, height=height)
+    if want_bop:
+        bop.check_depth_scale(wl.intr.near, depth16_counts_per_metre)
     for d in ("rgb", "labels", "depth", "pointcloud", "normals", "logs"):
         os.makedirs(os.path.join(out_dir, d), exist_ok=True)
     if "obj_coords" in outs:   # the boxes that turn the maps back into metres (labels.decode_obj_coords)
@@ -241,7 +277,10 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
     # cloud are encoded on the GPU (Renderer.render_files, csg_encode.hip) and
     # the host only writes bytes; writer processes encode on the host (libcsgio).
     gpu_files = writer_mode == "thread"
-    kinds = tuple(k for o, k in FILE_OF_OUTPUT if o in outs) if gpu_files else ()
+    # (bop: its rgb and depth files are the GPU's rgb_png and depth16_png, whether or not those outputs
+    # are asked for under their own names as well)
+    enc_outs = outs | {"rgb", "depth16_png"} if want_bop else outs
+    kinds = tuple(k for o, k in FILE_OF_OUTPUT if o in enc_outs) if gpu_files else ()
     # host depth for its own files; the quality log's depth counts come from
     # the GPU (depth_stats) in thread mode, from the host depth otherwise
     host_depth = "depth_npy" in outs or (not gpu_files and bool(outs & {"depth_csv", "pointcloud", "depth16_png"}))
@@ -274,9 +313,17 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
         amodal_el = eligible_labels(wl.scene, DYNAMIC_KINDS if amodal_kinds is None else tuple(amodal_kinds))
     fw = None       # thread mode: the native fragment writer (writers.FragmentWriter), made with the first poses
     kp_by_obj = masks.keypoints_by_object(wl.kp_table) if want_rle and not gpu_files else None
-    if want_rle:    # host-output batches keep their ids on the device for the span pass
+    if want_rle or want_bop:    # host-output batches keep their ids on the device for the span pass
         for x in rends:
             x.keep_instance(True)
+    bop_masks, bop_em, bop_scenes = {}, {}, set()   # per renderer; per epoch (bop.epoch_models); scene folders made
+    if want_bop:
+        bop_el = None if amodal_kinds is not None and "all" in amodal_kinds else eligible_labels(
+            wl.scene, DYNAMIC_KINDS if amodal_kinds is None else tuple(amodal_kinds))
+        bop_masks = {id(x): bop.BatchMasks(x, wl.scene, bop_el) for x in rends}
+        if frames and sink == "disk":
+            bop.write_run_tables(out_dir, wl.scene, bop.epoch_models(wl.epoch(frames[0] // 10).object_frames),
+                                 wl.intr.pixel_projection(), wl.width, wl.height, depth16_counts_per_metre)
     if gpu_files:   # page-locked slots, and buffers for the encoded files (an estimate, grown on demand)
         npx = wl.width * wl.height
         est = {"rgb_png": 2 * npx, "depth_csv": 10 * npx, "depth_png": npx, "pointcloud_txt": 48 * npx,
@@ -371,6 +418,15 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                 nb += st_a.nbytes + sum(o.nbytes + sp.nbytes for o, sp in per)
             return nb
 
+        bopr = [None]  # the batch's per-frame (listed objects, mask_visib files, mask files, amodal stats), with "bop"
+
+        def bop_of_batch() -> int:
+            ids, nf = r.last_instance()
+            if not ids or nf != len(fb):
+                raise RuntimeError(f"bop: the batch kept {nf} id images, {len(fb)} frames rendered")
+            bopr[0], nb = bop_masks[id(r)](make_frames(*cur[0], sets, fb), ids)
+            return nb
+
         cur = [None]   # the cameras of the attempt being rendered
 
         def run(views, projs):
@@ -384,7 +440,8 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                     offsets = r.copy_files(pool.grow_files(slot, need + need // 4, alloc=r.host_buffer,
                                                            free=r.free_host_buffer), len(fb) * nk)
                 arrays["file_offsets"] = offsets
-                d2h.append(int(offsets[-1]) + wire_bytes(out) + (spans_of_batch() if want_rle else 0))
+                d2h.append(int(offsets[-1]) + wire_bytes(out) + (spans_of_batch() if want_rle else 0)
+                           + (bop_of_batch() if want_bop else 0))
             else:
                 out = r.render(fr, want=want, out={k: v[:len(fb)] for k, v in arrays.items()})
                 d2h.append(wire_bytes(out) + (spans_of_batch() if want_rle else 0))
@@ -413,7 +470,7 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                 out = run(*wl.frame_params(fb, attempts))
                 check = again
         te = time.time()
-        return fb, slot, out, (te - tr, tp - tw, tr - tp), attempts, checks, failed, (rle[0], arle[0])
+        return fb, slot, out, (te - tr, tp - tw, tr - tp), attempts, checks, failed, (rle[0], arle[0], bopr[0])
 
     ahead = ThreadPoolExecutor(max_workers=n_rend)
     prep = ThreadPoolExecutor(max_workers=max(1, n_prep))
@@ -429,7 +486,7 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
         queued = [ahead.submit(render_batch, b) for b in range(min(n_rend, len(starts)))]
         for b in range(len(starts)):
             tq = time.time()
-            fb, slot, out, (dt, dwait, dprep), attempts, checks, failed, (rle, arle) = queued.pop(0).result()
+            fb, slot, out, (dt, dwait, dprep), attempts, checks, failed, (rle, arle, bopr) = queued.pop(0).result()
             t_main_wait += time.time() - tq
             t_render += dt
             t_slot_wait += dwait
@@ -476,6 +533,28 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                                           (k * nk + kinds.index(kd),)))
                 elif "rgb" in outs:
                     files.append((file_path(out_dir, "rgb", f), "png", ("rgb",)))
+                if want_bop:   # the two images from the GPU encoders, the mask files, then the fragment
+                    if f // bop.FRAMES_PER_SCENE not in bop_scenes and sink == "disk":
+                        bop.make_dirs(out_dir, f // bop.FRAMES_PER_SCENE)
+                        bop_scenes.add(f // bop.FRAMES_PER_SCENE)
+                    files.append((bop.image_path(out_dir, "rgb", f), "encoded", (k * nk + kinds.index("rgb_png"),)))
+                    files.append((bop.image_path(out_dir, "depth", f), "encoded",
+                                  (k * nk + kinds.index("depth16_png"),)))
+                    listed, vis_png, amo_png, a_stats = bopr[k]
+                    for g in range(len(listed)):
+                        files.append((bop.mask_path(out_dir, "mask_visib", f, g), "call",
+                                      (partial(bop.write_bytes, data=vis_png[g]),)))
+                        files.append((bop.mask_path(out_dir, "mask", f, g), "call",
+                                      (partial(bop.write_bytes, data=amo_png[g]),)))
+                    if f // 10 not in bop_em:
+                        if len(bop_em) >= 256:
+                            bop_em.pop(next(iter(bop_em)))
+                        bop_em[f // 10] = bop.epoch_models(wl.epoch(f // 10).object_frames)
+                    files.append((bop.fragment_path(out_dir, f), "call",
+                                  (partial(bop.write_fragment, frame_id=f, view=V, proj=P,
+                                           counts_per_metre=depth16_counts_per_metre, scene=wl.scene,
+                                           em=bop_em[f // 10], inst_stats=out["inst_stats"][k].copy(),
+                                           amodal_stats=a_stats, listed=listed),)))
                 if "mask" in outs:
                     files.append((os.path.join(out_dir, "labels", f"instance_mask_{f:06d}.npy"), "npy", ("instance",)))
                 if want_rle:   # written by the job itself, before the label file
@@ -565,7 +644,7 @@ def main(argv=None):
     ap.add_argument("--width", type=int)
     ap.add_argument("--height", type=int)
     ap.add_argument("--outputs", default="reference",
-                    help=f"'reference' ({','.join(REFERENCE_OUTPUTS)}), 'all', or a comma list of {OUTPUTS}")
+                    help=f"'reference' ({','.join(REFERENCE_OUTPUTS)}), 'all', or a comma list of {OUTPUTS + (BOP_OUTPUT,)}")
     ap.add_argument("--depth", action="store_true", help="add depth .npy")
     ap.add_argument("--depth-csv", action="store_true", help="add depth .npy and CSV")
     ap.add_argument("--pointcloud", action="store_true")

@@ -788,6 +788,81 @@ class Renderer:
             sp = h_sp.numpy().view(np.uint32).copy()
         return [(off[f], sp[int(ends[f] - totals[f]):int(ends[f])]) for f in range(n)], stats, cap
 
+    def span_stream(self):
+        """The wrapper's own stream, on which the ``*_host`` span and mask methods run (made on first use)."""
+        import torch
+        if getattr(self, "_span_stream", None) is None:
+            self._span_stream, self._span_pin = torch.cuda.Stream(torch.device("cuda", self.device)), {}
+        return self._span_stream
+
+    # -- per-object mask PNGs from spans ------------------------------------------------
+    def encode_span_masks(self, items, *, spans: int, span_offsets: int, capacity: int, out: int, out_capacity: int,
+                          file_offsets: int, n_frames: int, n_labels: Optional[int] = None,
+                          height: Optional[int] = None, width: Optional[int] = None, stream: int = 0) -> None:
+        """Enqueue the mask PNG files of ``items`` (csg_encode_span_masks; raw
+        device pointers, like :meth:`mask_spans`): item i = ``(frame, label)``
+        ((n_items, 2) uint32 on the HOST, copied before the call returns) is the
+        union of that label's records of that frame in ``spans`` (n_frames,
+        capacity, 2) / ``span_offsets`` (n_frames, L + 1) -- what
+        :meth:`mask_spans` or :meth:`amodal_spans` wrote -- as a finished 8-bit
+        grey PNG (0 / 255; :func:`writers.mask_png_bytes` states the bytes) at
+        ``out + file_offsets[i]``.  ``file_offsets`` (n_items + 1) uint64 gets
+        exact offsets whether or not the total ``file_offsets[n_items]`` fits
+        ``out_capacity``; where it does not, ``out`` is unspecified and the
+        caller repeats the pass with an output of that size.  ``n_labels``
+        defaults to the scene's, ``height`` / ``width`` to the renderer's."""
+        it = np.ascontiguousarray(np.asarray(items).reshape(-1, 2)).astype(np.uint32)
+        job = _lib.MaskPngJob(self.width if width is None else int(width), self.height if height is None else int(height),
+                              int(n_frames), self.n_labels if n_labels is None else int(n_labels), int(capacity),
+                              int(it.shape[0]), spans or None, span_offsets or None,
+                              it.ctypes.data if it.shape[0] else None, out or None, int(out_capacity),
+                              file_offsets or None)
+        self._check(self.lib.csg_encode_span_masks(self.ctx, C.byref(job), stream or None), "encode_span_masks")
+
+    def mask_pngs_host(self, items, *, spans: int, span_offsets: int, capacity: int, n_frames: int,
+                       n_labels: Optional[int] = None, height: Optional[int] = None, width: Optional[int] = None,
+                       out_capacity: int = 0, stream: int = 0) -> List[bytes]:
+        """:meth:`encode_span_masks` delivered to the host: the files of
+        ``items`` as a list of ``bytes``.  The pass runs on a stream of the
+        wrapper's own into an output of ``out_capacity`` bytes (0: a guess from
+        the frame size), ``file_offsets`` follow it to the host, and where the
+        total overflowed the pass is repeated once with an output of the exact
+        total.  The packed files cross PCIe in one copy.  ``stream`` (a raw
+        handle, 0: none) is the stream still writing the spans, if any: it is
+        waited for first.  Synchronous."""
+        import torch
+        it = np.ascontiguousarray(np.asarray(items).reshape(-1, 2)).astype(np.uint32)
+        n = int(it.shape[0])
+        if n == 0:
+            return []
+        H = self.height if height is None else int(height)
+        W = self.width if width is None else int(width)
+        dev = torch.device("cuda", self.device)
+        if stream:
+            torch.cuda.ExternalStream(stream, device=dev).synchronize()
+        else:
+            self.synchronize()
+        st = self.span_stream()
+        cap = int(out_capacity) or n * (H * (24 + W // 64) + 256)   # an empty row takes some 8 + W / 150 bytes
+        with torch.cuda.stream(st):
+            d_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            while True:
+                d_out = torch.empty(cap, dtype=torch.uint8, device=dev)
+                self.encode_span_masks(it, spans=spans, span_offsets=span_offsets, capacity=capacity,
+                                       out=d_out.data_ptr(), out_capacity=cap, file_offsets=d_off.data_ptr(),
+                                       n_frames=n_frames, n_labels=n_labels, height=H, width=W,
+                                       stream=st.cuda_stream)
+                off = d_off.cpu().numpy()   # waits for the stream
+                total = int(off[n])
+                if total <= cap:
+                    break
+                cap = total
+            h_out = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+            h_out.copy_(d_out[:total], non_blocking=True)
+            st.synchronize()
+            buf = h_out.numpy()
+        return [buf[int(off[i]):int(off[i + 1])].tobytes() for i in range(n)]
+
     def keep_instance(self, keep: bool = True) -> None:
         """Host-output batches (:meth:`render`, :meth:`render_files`) keep their
         instance ids on the device even when "instance" is not among the host

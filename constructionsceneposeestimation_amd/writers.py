@@ -197,6 +197,85 @@ def write_depth16_png(path: str, depth: np.ndarray, counts_per_metre: float = 25
         fh.write(depth16_png_bytes(depth_to_u16(depth, counts_per_metre)))
 
 
+MASK_PNG_IDAT_BYTES = 2048   # dfl::kIdatBytes: zlib bytes per IDAT chunk of a mask PNG
+
+
+def _fixed_code(sym: int):
+    """(code, bits) of literal / length symbol ``sym`` in deflate's fixed
+    Huffman code (RFC 1951 3.2.6), the code bit-reversed for LSB-first output."""
+    if sym < 144:
+        v, n = 0x30 + sym, 8
+    elif sym < 256:
+        v, n = 0x190 + sym - 144, 9
+    elif sym < 280:
+        v, n = sym - 256, 7
+    else:
+        v, n = 0xC0 + sym - 280, 8
+    return int(format(v, f"0{n}b")[::-1], 2), n
+
+
+def _length_token(length: int):
+    """(value, bits) of a distance-1 match of ``length`` 3..258: the fixed code
+    of its length symbol, the extra bits, and the 5-bit distance code 0."""
+    if length <= 10:
+        sym, ne, ex = 254 + length, 0, 0
+    elif length == 258:
+        sym, ne, ex = 285, 0, 0
+    else:
+        l = length - 3
+        ne = l.bit_length() - 3
+        sym, ex = 257 + 4 * ne + 4 + (l >> ne) - 4, l & ((1 << ne) - 1)
+    code, n = _fixed_code(sym)
+    return code | (ex << n), n + ne + 5
+
+
+def mask_png_bytes(mask: np.ndarray) -> bytes:
+    """The mask PNG of csg_encode_span_masks (``Renderer.mask_pngs_host``), byte
+    for byte, of an (H, W) mask (non-zero = 255): an 8-bit grey PNG, filter 0
+    on every row, whose zlib stream is ``78 01``, ONE fixed-Huffman deflate
+    block and the Adler-32, cut into IDAT chunks of 2048 bytes.  Each row's
+    1 + W bytes are tokenised on their own: every maximal run of equal bytes
+    (the filter byte joins a leading run of zeros) is one literal, distance-1
+    matches of at most 258 bytes and a remainder below 3 bytes as literals;
+    one end-of-block code follows the last row.  Plain Python, for tests and
+    readers of the format (csrc/csg_mask_png.h is the native statement)."""
+    import struct
+    import zlib
+    m = np.asarray(mask)
+    assert m.ndim == 2 and m.shape[0] >= 1 and m.shape[1] >= 1, m.shape
+    H, W = m.shape
+    raw = np.zeros((H, W + 1), np.uint8)
+    raw[:, 1:] = np.where(m != 0, 255, 0)
+    lit = {0: _fixed_code(0), 255: _fixed_code(255)}
+    acc, nbits = 0x0178 | (0b011 << 16), 19          # 78 01, BFINAL = 1, BTYPE = 01
+    z = bytearray()
+
+    def put(value_bits):
+        nonlocal acc, nbits
+        acc |= value_bits[0] << nbits
+        nbits += value_bits[1]
+
+    for row in raw:
+        z += (acc & ((1 << (nbits & ~7)) - 1)).to_bytes(nbits >> 3, "little")   # the whole bytes so far
+        acc, nbits = acc >> (nbits & ~7), nbits & 7
+        cuts = np.flatnonzero(row[1:] != row[:-1]) + 1
+        starts = np.concatenate([[0], cuts])
+        for s, e in zip(starts.tolist(), np.concatenate([cuts, [W + 1]]).tolist()):
+            b, rem = int(row[s]), e - s - 1
+            put(lit[b])
+            while rem >= 3:
+                n = min(rem, 258)
+                put(_length_token(n))
+                rem -= n
+            for _ in range(rem):
+                put(lit[b])
+    put(_fixed_code(256))
+    z = bytes(z) + acc.to_bytes((nbits + 7) // 8, "little") + struct.pack(">I", zlib.adler32(raw.tobytes()) & 0xFFFFFFFF)
+    idat = b"".join(_png_chunk(b"IDAT", z[k:k + MASK_PNG_IDAT_BYTES]) for k in range(0, len(z), MASK_PNG_IDAT_BYTES))
+    return (b"\x89PNG\r\n\x1a\n" + _png_chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 0, 0, 0, 0)) + idat
+            + _png_chunk(b"IEND", b""))
+
+
 def spans_to_rle(spans: np.ndarray, offsets: np.ndarray, height: int, width: int):
     """One frame's mask spans (``Renderer.mask_spans``: ``spans`` (total, 2)
     uint32 start / len, ``offsets`` (L + 1,) uint32) as COCO run-length masks,

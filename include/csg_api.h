@@ -64,6 +64,8 @@
  *                               the visible ids
  *   csg_amodal_spans .......... (new) the same spans of every object's amodal mask over
  *                               the whole frame, with its amodal box and pixel count
+ *   csg_encode_span_masks ..... (new) those spans as finished per-object mask PNG files
+ *                               (BOP's `mask_visib` / `mask` folders), packed in device memory
  *   csg_sample_object_points .. (new) N pixels of each object's visible mask with their
  *                               image indices, camera-frame points, colours and object
  *                               coordinates: the input of the point-based pose networks
@@ -793,6 +795,79 @@ typedef struct {
   uint32_t* amodal_stats;     /* DEVICE [n][L][5] = pixels, minx, miny, maxx, maxy, 4-B aligned, or NULL */
 } csg_amodal_span_job;
 int csg_amodal_spans(csg_ctx* ctx, const csg_amodal_span_job* job, uint32_t n_frames, void* stream);
+
+/* Per-object mask PNGs from spans: each (frame, label) item's mask, the union of
+ * that label's span records of that frame, as a finished 8-bit grey PNG file
+ * (0 / 255), all files packed into `out` -- what BOP's `mask_visib` and `mask`
+ * folders hold, one file per object per frame, without the dense ids crossing
+ * PCIe and without a zlib call per object on the host.  A stand-alone pass on
+ * device memory only, like csg_mask_spans: it needs no scene and no earlier
+ * render, and the frame size is the job's own.  Integers only.
+ *
+ *   spans, span_offsets  exactly what csg_mask_spans or csg_amodal_spans wrote for
+ *                 `n_frames` frames of `width` x `height` with L = n_labels and
+ *                 C = capacity; read only.
+ *   items         HOST [n_items] csg_mask_item {frame, label}, copied before the
+ *                 call returns.  The same label may appear in several items; a
+ *                 label without spans gives an all-zero mask, a valid file.
+ *   out           file i starts at out + file_offsets[i].
+ *   file_offsets  [n_items + 1] uint64; file_offsets[0] = 0 and
+ *                 file_offsets[n_items] is the exact total WHETHER OR NOT IT FITS.
+ *
+ * Records.  A record is used whole or not at all: it is ignored if len == 0,
+ * start >= W * H, or (start mod H) + len > H.  A frame whose off[f][L] > C
+ * (csg_mask_spans' overflow) may hold anything in its records and offsets: no
+ * value makes a kernel read or write outside the arrays described, and the files
+ * of that frame's items are then unspecified but well inside their ranges.
+ *
+ * Overflow.  When the total exceeds out_capacity, `out` is unspecified inside
+ * out_capacity, nothing is written beyond it and the offsets are still exact:
+ * the caller reads file_offsets[n_items] after its stream completes and repeats
+ * the pass with an output of that size.
+ *
+ * The file, byte for byte (one deterministic encoding; csrc/csg_mask_png.h, and
+ * writers.mask_png_bytes in Python): PNG signature; IHDR with W, H, bit depth 8,
+ * colour type 0, compression, filter and interlace 0; IDAT chunks of 2048 zlib
+ * bytes, the last one shorter; IEND.  The zlib stream is 78 01, ONE deflate block
+ * with BFINAL = 1 and BTYPE = 01 (fixed Huffman), byte padding, and the Adler-32
+ * big-endian.  The raw stream is per row the filter byte 0 and W bytes 0 / 255.
+ * Each row is tokenised on its own: its 1 + W bytes split into maximal runs of
+ * equal bytes (the filter byte joins a leading run of zeros) and each run is one
+ * literal, distance-1 matches of at most 258 bytes and a remainder below 3 bytes
+ * as literals; one end-of-block code follows the last row.
+ *
+ * Asynchronous on `stream` (NULL = the context's stream); behind the span pass
+ * on the same stream it needs no synchronisation.  The result is a pure function
+ * of the input.  Scratch is the pass's own, under an order of its own: one bit
+ * per pixel and item (bounded at 64 MiB: a job that needs more runs as ranges of
+ * items on the stream; CSG_MASK_PNG_PLANE_CAP, bytes, overrides the bound), 12
+ * bytes per row and item, and a staging area for the zlib streams of at most
+ * out_capacity + 4 bytes per item.
+ *
+ * CSG_ERR_INVALID, nothing enqueued or written: job, spans, span_offsets, items,
+ * out or file_offsets NULL; n_frames, n_items or capacity 0; width or height 0
+ * or above 8192; n_labels 0; an item with frame >= n_frames or label >=
+ * n_labels; spans or file_offsets not 8-byte or span_offsets not 4-byte aligned.
+ * CSG_ERR_LIMIT: n_labels above CSG_SPAN_MAX_LABELS. */
+typedef struct {            /* 8 bytes */
+  uint32_t frame;           /* < n_frames */
+  uint32_t label;           /* < n_labels */
+} csg_mask_item;
+
+typedef struct {
+  uint32_t width, height;      /* of the frames the spans describe: 1..8192 each */
+  uint32_t n_frames;
+  uint32_t n_labels;           /* L: 1..CSG_SPAN_MAX_LABELS */
+  uint32_t capacity;           /* C: span records per frame, >= 1 */
+  uint32_t n_items;            /* >= 1 */
+  const csg_span* spans;       /* DEVICE [n_frames][C], 8-B aligned */
+  const uint32_t* span_offsets;/* DEVICE [n_frames][L + 1], 4-B aligned */
+  const csg_mask_item* items;  /* HOST [n_items], copied before the call returns */
+  uint8_t* out;                /* DEVICE [out_capacity] */
+  uint64_t out_capacity;
+  uint64_t* file_offsets;      /* DEVICE [n_items + 1], 8-B aligned */
+} csg_mask_png_job;
+int csg_encode_span_masks(csg_ctx* ctx, const csg_mask_png_job* job, void* stream);
 
 /* Fixed-size per-object point samples: for each slot of `info`, N pixels drawn
  * from the visible mask of the slot's label, as their indices in the image
