@@ -145,8 +145,14 @@ typedef struct {
   uint8_t sky[4];            /* background RGB */
 } csg_light;
 
+/* The rotation of `view` must have a positive determinant (a proper look-at).
+ * The normals output is flipped by the sign of the screen-space determinant
+ * of the triangle, which faces the camera only then: under an improper view
+ * (determinant < 0) every normal faces away from the camera, while ids, depth,
+ * RGB, points, obj_coords and keypoints are what the geometry says
+ * (DESIGN.md section 3, item 8). */
 typedef struct {
-  float view[16];            /* row-major world->camera (USD camera: -Z forward) */
+  float view[16];            /* row-major world->camera (USD camera: -Z forward), rotation of det > 0 */
   float proj[16];            /* row-major; rows 0,1,3 give (u*w, v*w, w) in pixels */
   uint32_t xform_set;        /* instance-transform set (randomisation epoch) */
   uint32_t frame_id;

@@ -5,7 +5,8 @@ is shared with the oracle or the kernels (of the package only the scene model an
 ``packing.light_constants``, whose float32 constants are the light's inputs, are used).
 
 * Camera: V = M = identity, P = ``raster_exact.projection`` (fx = fy = 256, integer
-  cx, cy), near = 1/2, far = 256: both range bounds are powers of two.
+  cx, cy), near = 1/2, far = 256: both range bounds are powers of two.  (tests/pose_exact.py carries
+  these frames into posed worlds: other V, M and P under which the same arithmetic stays exact.)
 * A triangle is three 24.8 fixed-point screen vertices (U_k, V_k) on multiples of 16
   units, each with its own W_k = 2^j (1/4 .. 1024), and optionally uvs on multiples of
   1/256.  One edge is axis-aligned with length 2^p and the third vertex lies 2^q across
@@ -674,10 +675,11 @@ def render(insts, scene, light, Wd, Hd, cx, cy, first_instance, table=None):
     return out
 
 
-def keypoints(kps, depth, Wd, Hd, cx, cy):
-    """Item 10 on float32 points [(x, y, z)] (V = identity) -> uv (n, 2) float32, vis (n,) int32: every
-    operation of ``((P0 x + P1 y) + P2 z) + P3`` and the division rounded with ``rn32`` on rationals."""
-    P = projection(cx, cy)
+def keypoints(kps, depth, Wd, Hd, cx, cy, PV=None):
+    """Item 10 on float32 points [(x, y, z)] -> uv (n, 2) float32, vis (n,) int32: every operation of
+    ``((P0 x + P1 y) + P2 z) + P3`` and the division rounded with ``rn32`` on rationals.  ``PV`` is the
+    float32 product P V (tests/pose_exact.py); without it V = identity and P = ``projection(cx, cy)``."""
+    P = projection(cx, cy) if PV is None else np.asarray(PV, np.float32).astype(np.float64)
     uv = np.zeros((len(kps), 2), np.float32)
     vis = np.zeros(len(kps), np.int32)
     for k, pt in enumerate(kps):
