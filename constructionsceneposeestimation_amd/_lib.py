@@ -21,6 +21,7 @@ SPAN_MAX_LABELS = 256  # CSG_SPAN_MAX_LABELS: the most labels csg_mask_spans tak
 # csg_outputs.file_kinds (CSG_FILE_*): files encoded on the GPU, one per kind per frame, in bit order
 FILE_KINDS = {"rgb_png": 1, "depth_csv": 2, "depth_png": 4, "pointcloud_txt": 8, "pointcloud_ply": 16,
               "depth16_png": 32}
+JPEG_SUBSAMPLING = {"444": 0, "420": 1}  # CSG_JPEG_444, CSG_JPEG_420 (csg_jpeg_job.subsampling)
 DEPTH16_COUNTS_PER_METRE = 250.0  # csg_outputs.depth16_counts_per_metre = 0: 4 mm steps, 262.1 m range
 
 EXPORTED = (
@@ -32,7 +33,7 @@ EXPORTED = (
     "csg_get_work_info", "csg_host_id_bytes", "csg_set_object_frames", "csg_crop_objects", "csg_encode_files",
     "csg_crop_objects_filtered", "csg_crop_amodal", "csg_crop_amodal_geometry", "csg_mask_spans",
     "csg_keep_instance", "csg_last_instance", "csg_amodal_spans", "csg_sample_object_points",
-    "csg_encode_span_masks",
+    "csg_encode_span_masks", "csg_encode_jpeg", "csg_keep_rgb", "csg_last_rgb",
 )
 
 
@@ -151,6 +152,13 @@ class MaskPngJob(C.Structure):
                 ("items", C.c_void_p), ("out", C.c_void_p), ("out_capacity", C.c_uint64), ("file_offsets", C.c_void_p)]
 
 
+class JpegJob(C.Structure):
+    """csg_jpeg_job (csg_encode_jpeg)."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n_frames", C.c_uint32), ("quality", C.c_uint32),
+                ("subsampling", C.c_uint32), ("pad", C.c_uint32), ("rgb", C.c_void_p), ("out", C.c_void_p),
+                ("out_capacity", C.c_uint64), ("file_offsets", C.c_void_p)]
+
+
 class PointJob(C.Structure):
     """csg_point_job (csg_sample_object_points)."""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n_labels", C.c_uint32), ("per_frame", C.c_uint32),
@@ -243,6 +251,9 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     lib.csg_amodal_spans.argtypes = [vp, C.POINTER(AmodalSpanJob), u32, vp]
     lib.csg_sample_object_points.argtypes = [vp, C.POINTER(PointJob), u32, vp]
     lib.csg_encode_span_masks.argtypes = [vp, C.POINTER(MaskPngJob), vp]
+    lib.csg_encode_jpeg.argtypes = [vp, C.POINTER(JpegJob), vp]
+    lib.csg_keep_rgb.argtypes = [vp, i32]
+    lib.csg_last_rgb.argtypes = [vp, C.POINTER(vp), C.POINTER(u32)]
     lib.csg_keep_instance.argtypes = [vp, i32]
     lib.csg_last_instance.argtypes = [vp, C.POINTER(vp), C.POINTER(u32)]
     if lib.csg_abi_version() != ABI_VERSION:

@@ -5,6 +5,7 @@
     DIR/camera.json
     DIR/models/models_info.json, DIR/models/objects.json
     DIR/train_pbr/%06d/rgb/%06d.png           scene = frame_id // 1000, image = frame_id % 1000
+                                              (%06d.jpg with the generator's --bop-rgb jpg)
     DIR/train_pbr/%06d/depth/%06d.png         16-bit, millimetres = sample * depth_scale
     DIR/train_pbr/%06d/mask/%06d_%06d.png     amodal mask of object gt_id of the image
     DIR/train_pbr/%06d/mask_visib/%06d_%06d.png
@@ -56,10 +57,10 @@ def scene_dir(out_dir: str, scene_id: int) -> str:
     return os.path.join(out_dir, SPLIT, f"{int(scene_id):06d}")
 
 
-def image_path(out_dir: str, kind: str, frame_id: int) -> str:
-    """``kind`` "rgb" or "depth"."""
+def image_path(out_dir: str, kind: str, frame_id: int, ext: str = "png") -> str:
+    """``kind`` "rgb" or "depth"; ``ext`` "jpg" for the RGB of ``--bop-rgb jpg``."""
     s, i = scene_image(frame_id)
-    return os.path.join(scene_dir(out_dir, s), kind, f"{i:06d}.png")
+    return os.path.join(scene_dir(out_dir, s), kind, f"{i:06d}.{ext}")
 
 
 def mask_path(out_dir: str, kind: str, frame_id: int, gt_id: int) -> str:

@@ -159,6 +159,8 @@ void csg_destroy(csg_ctx* c) {
   (void)c->am.wait_host(c);   // passes on streams of the caller's
   (void)c->ms.wait_host(c);
   (void)c->op.wait_host(c);
+  (void)c->mp.wait_host(c);
+  (void)c->jp.wait_host(c);
   if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   for (auto& e : c->ring)
@@ -887,7 +889,7 @@ static int enqueue_batch(csg_ctx* c, const csg_frame* frames, uint32_t F, int fr
     b.kp_uv = out->keypoints_uv;
     b.kp_vis = out->keypoints_vis;
   } else {
-    if (out->rgb) { HIP_TRY(c, c->o_rgb.alloc(F * npx * 3)); b.rgb = c->o_rgb.p; }
+    if (out->rgb || c->keep_rgb) { HIP_TRY(c, c->o_rgb.alloc(F * npx * 3)); b.rgb = c->o_rgb.p; }
     if (out->instance || c->keep_ids) { HIP_TRY(c, c->o_inst.alloc(F * npx)); b.inst = c->o_inst.p; }
     if (out->depth) { HIP_TRY(c, c->o_depth.alloc(F * npx)); b.depth = c->o_depth.p; }
     if (out->normals) { HIP_TRY(c, c->o_normals.alloc(F * npx * 3)); b.normals = c->o_normals.p; }
@@ -1111,6 +1113,8 @@ static int enqueue_batch(csg_ctx* c, const csg_frame* frames, uint32_t F, int fr
   c->last_dvis = dvis;
   c->last_inst = dev ? nullptr : b.inst;
   c->last_inst_frames = c->last_inst ? F : 0;
+  c->kept_rgb = dev ? nullptr : b.rgb;
+  c->kept_rgb_frames = c->kept_rgb ? F : 0;
   if (!dev) {   // the batch's stream orders everything after it (and csg_synchronize) behind the copies
     if (narrow) {   // ... and behind the widening of every chain's ids
       auto* l = new std::shared_ptr<WidenLatch>(latch);
@@ -1746,6 +1750,20 @@ int csg_last_instance(csg_ctx* c, const int32_t** instance, uint32_t* n_frames) 
   if (!instance || !n_frames) return c->fail(CSG_ERR_INVALID, "last_instance: null argument");
   *instance = c->last_inst;
   *n_frames = c->last_inst_frames;
+  return CSG_OK;
+}
+
+int csg_keep_rgb(csg_ctx* c, int32_t keep) {
+  if (!c) return CSG_ERR_INVALID;
+  c->keep_rgb = keep != 0;
+  return CSG_OK;
+}
+
+int csg_last_rgb(csg_ctx* c, const uint8_t** rgb, uint32_t* n_frames) {
+  if (!c) return CSG_ERR_INVALID;
+  if (!rgb || !n_frames) return c->fail(CSG_ERR_INVALID, "last_rgb: null argument");
+  *rgb = c->kept_rgb;
+  *n_frames = c->kept_rgb_frames;
   return CSG_OK;
 }
 

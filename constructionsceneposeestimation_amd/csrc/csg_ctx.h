@@ -12,6 +12,7 @@
 
 #include "../../include/csg_api.h"
 #include "csg_encode.h"
+#include "csg_jpeg.h"
 #include "csg_kernels.h"
 #include "csg_mask_png.h"
 
@@ -313,6 +314,20 @@ struct csg_ctx {
   DevBuf<csg::MaskFile> mp_files;
   DevBuf<uint8_t> mp_z;
   csg::PassOrder mp;
+  // JPEG files (csg_encode_jpeg): the pass's own scratch -- the format's tables behind their staging slot, and
+  // of one range of frames the coefficients, the blocks' AC bits, the intervals' staging slots, sizes and
+  // positions and the files' sizes -- grown to the job, under an order of its own.
+  DevBuf<csg::jpg::Tables> jp_tables;
+  csg::StageSlot<csg::jpg::Tables> jp_stage;
+  DevBuf<int16_t> jp_coef;
+  DevBuf<uint32_t> jp_abits, jp_isize, jp_ipos;
+  DevBuf<uint8_t> jp_z;
+  DevBuf<uint64_t> jp_fsize;
+  csg::PassOrder jp;
+  // csg_keep_rgb / csg_last_rgb: host-output batches render their RGB into o_rgb whether or not anything copies it
+  bool keep_rgb = false;
+  const uint8_t* kept_rgb = nullptr;
+  uint32_t kept_rgb_frames = 0;
   // csg_keep_instance / csg_last_instance: host-output batches keep their ids on the device
   bool keep_ids = false;
   const int32_t* last_inst = nullptr;

@@ -253,6 +253,74 @@ int csg_encode_span_masks(csg_ctx* c, const csg_mask_png_job* job, void* stream)
   return c->mp.end(c, st);
 }
 
+// JPEG files: a stand-alone pass over an RGB image in device memory (no scene state, no work buffers);
+// validates the job, uploads the format's tables, grows the pass's own scratch and enqueues the kernels.
+// The scratch (coefficients, bit counts, staging slots) is bounded at kJpegScratchCap bytes: a job that
+// needs more runs as ranges of frames on the stream, each filling and reading the same scratch and
+// continuing file_offsets where the last one ended.
+int csg_encode_jpeg(csg_ctx* c, const csg_jpeg_job* job, void* stream) {
+  constexpr size_t kJpegScratchCap = 256u << 20;
+  static_assert(jpg::k444 == CSG_JPEG_444 && jpg::k420 == CSG_JPEG_420, "subsampling values");
+  if (!c) return CSG_ERR_INVALID;
+  if (!job) return c->fail(CSG_ERR_INVALID, "encode_jpeg: null job");
+  if (!job->rgb || !job->out || !job->file_offsets)
+    return c->fail(CSG_ERR_INVALID, "encode_jpeg: rgb, out and file_offsets must not be NULL");
+  if (job->n_frames == 0) return c->fail(CSG_ERR_INVALID, "encode_jpeg: no frames");
+  CSG_TRY(check_frame_dims(c, "encode_jpeg", job->width, job->height));
+  if (job->quality < 1 || job->quality > 100)
+    return c->fail(CSG_ERR_INVALID, "encode_jpeg: quality %u outside 1..100", job->quality);
+  if (job->subsampling != CSG_JPEG_444 && job->subsampling != CSG_JPEG_420)
+    return c->fail(CSG_ERR_INVALID, "encode_jpeg: subsampling %u is neither CSG_JPEG_444 nor CSG_JPEG_420",
+                   job->subsampling);
+  if ((uintptr_t)job->file_offsets & 7u) return c->fail(CSG_ERR_INVALID, "encode_jpeg: file_offsets must be 8-byte aligned");
+  hipStream_t st;
+  CSG_TRY(pass_stream(c, stream, &st));
+  JpegArgs a{};
+  a.W = job->width;
+  a.H = job->height;
+  a.sub = job->subsampling;
+  a.g = jpg::geometry(a.W, a.H, a.sub);
+  a.slot = jpg::slot_bytes(a.g);
+  const size_t blocks = (size_t)a.g.my * a.g.mx * a.g.bpm;   // of one frame
+  const size_t per_frame = blocks * (64u * sizeof(int16_t) + sizeof(uint32_t)) + (size_t)a.g.my * (a.slot + 8u) + 8u;
+  size_t cap = kJpegScratchCap;
+  if (const char* e = getenv("CSG_JPEG_SCRATCH_CAP")) cap = (size_t)strtoull(e, nullptr, 10);   // (tests: bytes)
+  const uint32_t range = (uint32_t)std::min<size_t>(std::min<uint32_t>(job->n_frames, 65535u),   // grid limit
+                                                    std::max<size_t>(1, cap / per_frame));
+  const size_t n_int = (size_t)range * a.g.my;
+  CSG_TRY(c->jp.begin(c, st, c->jp_tables.n < 1 || c->jp_coef.n < range * blocks * 64u || c->jp_abits.n < range * blocks ||
+                              c->jp_z.n < n_int * a.slot || c->jp_isize.n < n_int || c->jp_ipos.n < n_int ||
+                              c->jp_fsize.n < range));
+  HIP_TRY(c, c->jp_tables.alloc(1));
+  HIP_TRY(c, c->jp_coef.alloc(range * blocks * 64u));
+  HIP_TRY(c, c->jp_abits.alloc(range * blocks));
+  HIP_TRY(c, c->jp_z.alloc(n_int * a.slot));
+  HIP_TRY(c, c->jp_isize.alloc(n_int));
+  HIP_TRY(c, c->jp_ipos.alloc(n_int));
+  HIP_TRY(c, c->jp_fsize.alloc(range));
+  HIP_TRY(c, c->jp_stage.upload(c->jp_tables.p, 1, st, [&](jpg::Tables* h) {
+    jpg::build_tables(*h, job->width, job->height, job->quality, job->subsampling);
+  }));
+  a.tables = c->jp_tables.p;
+  a.rgb = job->rgb;
+  a.coef = c->jp_coef.p;
+  a.abits = c->jp_abits.p;
+  a.zbuf = c->jp_z.p;
+  a.isize = c->jp_isize.p;
+  a.ipos = c->jp_ipos.p;
+  a.fsize = c->jp_fsize.p;
+  a.out = job->out;
+  a.out_capacity = job->out_capacity;
+  a.file_offsets = job->file_offsets;
+  for (uint32_t f0 = 0; f0 < job->n_frames; f0 += range) {
+    a.first = f0;
+    a.n = std::min(range, job->n_frames - f0);
+    launch_jpeg(a, st);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return c->jp.end(c, st);
+}
+
 // Object points: a stand-alone pass over device arrays (no scene state, no work buffers); validates the
 // job, grows the pass's own count scratch and enqueues count, scan and emit.
 int csg_sample_object_points(csg_ctx* c, const csg_point_job* job, uint32_t n_frames, void* stream) {

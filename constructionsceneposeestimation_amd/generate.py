@@ -20,6 +20,9 @@ same files:
                                     merge RUN_DIR`` joins them into coco/instances.json; with "amodal_rle"
                                     as well, objects of --amodal-kinds also carry amodal_bbox, amodal_area
                                     and amodal_segmentation: the full silhouette as if nothing stood in front)
+  rgb/rgb_%06d.jpg                 (optional "rgb_jpg": a baseline JPEG, --jpeg-quality, --jpeg-subsampling,
+                                    encoded on the GPU from the RGB the batch keeps there; no reference
+                                    counterpart)
   depth/depth_%06d.csv             (:1687-1688)
   depth/depth_%06d.png             (:1690-1709, JET colour map made on the GPU)
   depth/depth_%06d.npy             (optional)
@@ -35,8 +38,9 @@ same files:
                                     object's prim_path, class_name, inst_idx and box lo / hi)
   train_pbr/%06d/{rgb,depth,mask,mask_visib}/ + bop/frag_%06d.json
                                    (optional "bop": the BOP dataset layout, bop.py -- scene = frame // 1000;
-                                    RGB and 16-bit depth PNGs, one mask_visib and one amodal mask PNG per
-                                    listed object made on the GPU from the spans, and per-frame fragments
+                                    RGB (PNG, or JPEG with --bop-rgb jpg) and 16-bit depth PNGs, one
+                                    mask_visib and one amodal mask PNG per listed object made on the GPU
+                                    from the spans, and per-frame fragments
                                     that ``python -m constructionsceneposeestimation_amd.bop merge RUN_DIR``
                                     joins into scene_camera / scene_gt / scene_gt_info.json; no reference
                                     counterpart)
@@ -77,7 +81,7 @@ from .renderer import Renderer, make_frames, output_spec, scene_labels
 from .shard import shard_of_range
 from .workload import Workload
 from .writer_pool import WriterPool
-from .writers import FragmentWriter, LabelWriter
+from .writers import JPEG_SUBSAMPLING, FragmentWriter, LabelWriter, write_jpeg
 from .writer_pool import _write_png  # noqa: F401  (the generator's PNG settings; tools/gen_bench.py)
 
 
@@ -98,7 +102,7 @@ def _log_done(log: QualityLog, fut, log_args: dict, points: bool) -> None:
 
 
 OUTPUTS = ("rgb", "mask", "depth_csv", "depth_png", "depth_npy", "pointcloud", "normals", "obj_coords",
-           "pointcloud_ply", "depth16_png", "mask_rle", "amodal_rle")
+           "pointcloud_ply", "depth16_png", "mask_rle", "amodal_rle", "rgb_jpg")
 # What the reference writes for every frame (GDP:1668-1771, 2055-2072): RGB PNG, depth CSV and
 # JET depth PNG, point-cloud TXT, instance mask .npy; the label JSON is always written (it is the
 # resume marker).
@@ -115,7 +119,8 @@ FILE_OF_OUTPUT = (("rgb", "rgb_png"), ("depth_csv", "depth_csv"), ("depth_png", 
                   ("depth16_png", "depth16_png"))
 _PATHS = {"rgb": ("rgb", "rgb_{:06d}.png"), "depth_csv": ("depth", "depth_{:06d}.csv"),
           "depth_png": ("depth", "depth_{:06d}.png"), "pointcloud": ("pointcloud", "pointcloud_{:06d}.txt"),
-          "pointcloud_ply": ("pointcloud", "pointcloud_{:06d}.ply"), "depth16_png": ("depth", "depth16_{:06d}.png")}
+          "pointcloud_ply": ("pointcloud", "pointcloud_{:06d}.ply"), "depth16_png": ("depth", "depth16_{:06d}.png"),
+          "rgb_jpg": ("rgb", "rgb_{:06d}.jpg")}
 _ENCODED_KIND = {"pointcloud": "encoded_pointcloud", "pointcloud_ply": "encoded_ply"}   # writer_pool.write_frame
 
 
@@ -170,7 +175,8 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
              writer_mode: str = "thread", renderers: int = 0, object_list: str = "visible",
              occlusion: bool = False, sink: str = "disk", validate_pointcloud: bool = False,
              min_points: int = 100, max_retries: int = 5, prep_workers: int = -1,
-             depth16_counts_per_metre: float = 250.0, amodal_kinds: Optional[Sequence[str]] = None) -> dict:
+             depth16_counts_per_metre: float = 250.0, amodal_kinds: Optional[Sequence[str]] = None,
+             jpeg_quality: int = 95, jpeg_subsampling: str = "420", bop_rgb: str = "png") -> dict:
     """Render ``frames`` on one GPU and write them (``outputs``, default the
     reference's set; ``depth`` / ``depth_csv`` / ``pointcloud`` / ``normals``
     add the depth .npy, the depth .npy + CSV, the point cloud, the normals).
@@ -216,6 +222,15 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
     ``bop/frag_%06d.json`` per frame for ``python -m ...bop merge``.  Listed
     are the objects of ``amodal_kinds`` with amodal pixels.  Thread writers
     only; not with "mask", "mask_rle" or "amodal_rle".
+    ``outputs`` with "rgb_jpg": ``rgb/rgb_%06d.jpg``, a baseline JPEG at
+    ``jpeg_quality`` (1..100) and ``jpeg_subsampling`` ("444" or "420").  With
+    thread writers the batch keeps its RGB on the device (csg_keep_rgb), the
+    files are encoded there behind the render (Renderer.jpegs_host,
+    csg_encode_jpeg) and cross PCIe packed, in one copy; next to "rgb" both
+    files are written, without it the PNG is neither encoded nor copied.
+    Writer processes encode the host RGB with writers.jpeg_bytes (the same
+    bytes).  ``bop_rgb`` "jpg": output "bop" writes ``rgb/%06d.jpg`` from the
+    same pass instead of the RGB PNG.
     ``prep_workers``: processes that prepare batches ahead (epoch layouts,
     object poses, cameras; prep_pool.py), so that numpy work does not hold
     this process's GIL; -1 = two for runs of at least 20 batches, else none."""
@@ -232,6 +247,15 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
         outs.add("normals")
     check_bop(outs)
     want_bop = BOP_OUTPUT in outs
+    if bop_rgb not in ("png", "jpg"):
+        raise ValueError(f"bop_rgb {bop_rgb!r}: 'png' or 'jpg'")
+    bop_jpg = want_bop and bop_rgb == "jpg"
+    want_jpg = "rgb_jpg" in outs or bop_jpg
+    if want_jpg:
+        if not 1 <= int(jpeg_quality) <= 100:
+            raise ValueError(f"jpeg_quality {jpeg_quality!r} outside 1..100")
+        if str(jpeg_subsampling) not in JPEG_SUBSAMPLING:
+            raise ValueError(f"jpeg_subsampling {jpeg_subsampling!r}: '444' or '420'")
     if want_bop:
         if writer_mode != "thread":
             raise ValueError("output bop needs the GPU file encoders: writer_mode 'thread'")
@@ -279,7 +303,7 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
     gpu_files = writer_mode == "thread"
     # (bop: its rgb and depth files are the GPU's rgb_png and depth16_png, whether or not those outputs
     # are asked for under their own names as well)
-    enc_outs = outs | {"rgb", "depth16_png"} if want_bop else outs
+    enc_outs = outs | {"depth16_png"} | (set() if bop_jpg else {"rgb"}) if want_bop else outs
     kinds = tuple(k for o, k in FILE_OF_OUTPUT if o in enc_outs) if gpu_files else ()
     # host depth for its own files; the quality log's depth counts come from
     # the GPU (depth_stats) in thread mode, from the host depth otherwise
@@ -316,6 +340,10 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
     if want_rle or want_bop:    # host-output batches keep their ids on the device for the span pass
         for x in rends:
             x.keep_instance(True)
+    if want_jpg and gpu_files:   # ... and their RGB for the JPEG pass, whether or not anything else needs it
+        for x in rends:
+            x.keep_rgb(True)
+    jpg_cap = {}    # renderer -> the bytes its last batch's JPEG files took (jpegs_host repeats a pass that overflows)
     bop_masks, bop_em, bop_scenes = {}, {}, set()   # per renderer; per epoch (bop.epoch_models); scene folders made
     if want_bop:
         bop_el = None if amodal_kinds is not None and "all" in amodal_kinds else eligible_labels(
@@ -427,6 +455,18 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
             bopr[0], nb = bop_masks[id(r)](make_frames(*cur[0], sets, fb), ids)
             return nb
 
+        jpgr = [None]  # the batch's .jpg files, with "rgb_jpg" or bop's jpg RGB in thread mode
+
+        def jpgs_of_batch() -> int:
+            rgb, nf = r.last_rgb()
+            if not rgb or nf != len(fb):
+                raise RuntimeError(f"rgb_jpg: the batch kept {nf} RGB images, {len(fb)} frames rendered")
+            jpgr[0] = r.jpegs_host(len(fb), rgb=rgb, quality=jpeg_quality, subsampling=jpeg_subsampling,
+                                   out_capacity=jpg_cap.get(id(r), 0), views=True)
+            nb = sum(len(j) for j in jpgr[0])
+            jpg_cap[id(r)] = nb + nb // 4
+            return nb
+
         cur = [None]   # the cameras of the attempt being rendered
 
         def run(views, projs):
@@ -441,10 +481,11 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                                                            free=r.free_host_buffer), len(fb) * nk)
                 arrays["file_offsets"] = offsets
                 d2h.append(int(offsets[-1]) + wire_bytes(out) + (spans_of_batch() if want_rle else 0)
-                           + (bop_of_batch() if want_bop else 0))
+                           + (bop_of_batch() if want_bop else 0) + (jpgs_of_batch() if want_jpg else 0))
             else:
                 out = r.render(fr, want=want, out={k: v[:len(fb)] for k, v in arrays.items()})
-                d2h.append(wire_bytes(out) + (spans_of_batch() if want_rle else 0))
+                d2h.append(wire_bytes(out) + (spans_of_batch() if want_rle else 0)
+                           + (jpgs_of_batch() if want_jpg and gpu_files else 0))
             return out
 
         out = run(views, projs)
@@ -470,7 +511,7 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                 out = run(*wl.frame_params(fb, attempts))
                 check = again
         te = time.time()
-        return fb, slot, out, (te - tr, tp - tw, tr - tp), attempts, checks, failed, (rle[0], arle[0], bopr[0])
+        return fb, slot, out, (te - tr, tp - tw, tr - tp), attempts, checks, failed, (rle[0], arle[0], bopr[0], jpgr[0])
 
     ahead = ThreadPoolExecutor(max_workers=n_rend)
     prep = ThreadPoolExecutor(max_workers=max(1, n_prep))
@@ -486,7 +527,7 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
         queued = [ahead.submit(render_batch, b) for b in range(min(n_rend, len(starts)))]
         for b in range(len(starts)):
             tq = time.time()
-            fb, slot, out, (dt, dwait, dprep), attempts, checks, failed, (rle, arle, bopr) = queued.pop(0).result()
+            fb, slot, out, (dt, dwait, dprep), attempts, checks, failed, (rle, arle, bopr, jpgr) = queued.pop(0).result()
             t_main_wait += time.time() - tq
             t_render += dt
             t_slot_wait += dwait
@@ -533,11 +574,21 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                                           (k * nk + kinds.index(kd),)))
                 elif "rgb" in outs:
                     files.append((file_path(out_dir, "rgb", f), "png", ("rgb",)))
+                if "rgb_jpg" in outs:   # made on the GPU behind the batch, or by the writer from the host RGB
+                    files.append((file_path(out_dir, "rgb_jpg", f), "call",
+                                  (partial(bop.write_bytes, data=jpgr[k]) if gpu_files else
+                                   partial(write_jpeg, rgb=out["rgb"][k].copy(), quality=jpeg_quality,
+                                           subsampling=jpeg_subsampling),)))
                 if want_bop:   # the two images from the GPU encoders, the mask files, then the fragment
                     if f // bop.FRAMES_PER_SCENE not in bop_scenes and sink == "disk":
                         bop.make_dirs(out_dir, f // bop.FRAMES_PER_SCENE)
                         bop_scenes.add(f // bop.FRAMES_PER_SCENE)
-                    files.append((bop.image_path(out_dir, "rgb", f), "encoded", (k * nk + kinds.index("rgb_png"),)))
+                    if bop_jpg:
+                        files.append((bop.image_path(out_dir, "rgb", f, "jpg"), "call",
+                                      (partial(bop.write_bytes, data=jpgr[k]),)))
+                    else:
+                        files.append((bop.image_path(out_dir, "rgb", f), "encoded",
+                                      (k * nk + kinds.index("rgb_png"),)))
                     files.append((bop.image_path(out_dir, "depth", f), "encoded",
                                   (k * nk + kinds.index("depth16_png"),)))
                     listed, vis_png, amo_png, a_stats = bopr[k]
@@ -671,6 +722,10 @@ def main(argv=None):
     ap.add_argument("--amodal-kinds", default=",".join(DYNAMIC_KINDS),
                     help="object kinds whose annotations get amodal masks with the amodal_rle output "
                          "(a comma list, or 'all' for every label)")
+    ap.add_argument("--jpeg-quality", type=int, default=95, help="quality of the rgb_jpg output and of bop's jpg RGB")
+    ap.add_argument("--jpeg-subsampling", default="420", choices=("444", "420"))
+    ap.add_argument("--bop-rgb", default="png", choices=("png", "jpg"),
+                    help="output bop: train_pbr/%%06d/rgb/%%06d.png, or .jpg (BOP's train_pbr convention)")
     ap.add_argument("--prep-workers", type=int, default=-1,
                     help="processes preparing batches ahead (-1: two for runs of >= 20 batches)")
     a = ap.parse_args(argv)
@@ -686,7 +741,8 @@ def main(argv=None):
                        object_list=a.object_list, occlusion=a.occlusion, sink=a.sink,
                        validate_pointcloud=a.validate_pointcloud, min_points=a.min_points, max_retries=a.max_retries,
                        prep_workers=a.prep_workers, depth16_counts_per_metre=a.depth16_counts_per_metre,
-                       amodal_kinds=tuple(x.strip() for x in a.amodal_kinds.split(",") if x.strip()))
+                       amodal_kinds=tuple(x.strip() for x in a.amodal_kinds.split(",") if x.strip()),
+                       jpeg_quality=a.jpeg_quality, jpeg_subsampling=a.jpeg_subsampling, bop_rgb=a.bop_rgb)
     print(json.dumps(summary))
 
 

@@ -863,6 +863,84 @@ class Renderer:
             buf = h_out.numpy()
         return [buf[int(off[i]):int(off[i + 1])].tobytes() for i in range(n)]
 
+    # -- baseline JPEG files of RGB frames ------------------------------------------------
+    def encode_jpeg(self, n: int, *, rgb: int, out: int, out_capacity: int, file_offsets: int, quality: int = 95,
+                    subsampling: str = "420", height: Optional[int] = None, width: Optional[int] = None,
+                    stream: int = 0) -> None:
+        """Enqueue the JPEG files of ``n`` RGB frames (csg_encode_jpeg; raw
+        device pointers, like :meth:`encode_span_masks`): frame f of ``rgb``
+        (n, H, W, 3) uint8 at any alignment becomes a finished baseline JPEG
+        (:func:`writers.jpeg_bytes` states the bytes) at ``out +
+        file_offsets[f]``.  ``file_offsets`` (n + 1) uint64 gets exact offsets
+        whether or not the total ``file_offsets[n]`` fits ``out_capacity``; a
+        file that does not fit is not written, and the caller repeats the pass
+        with an output of that size.  ``subsampling`` is "444" or "420",
+        ``height`` / ``width`` default to the renderer's."""
+        if str(subsampling) not in _lib.JPEG_SUBSAMPLING:
+            raise ValueError(f"encode_jpeg: subsampling {subsampling!r} is neither '444' nor '420'")
+        job = _lib.JpegJob(self.width if width is None else int(width), self.height if height is None else int(height),
+                           int(n), int(quality), _lib.JPEG_SUBSAMPLING[str(subsampling)], 0, rgb or None, out or None,
+                           int(out_capacity), file_offsets or None)
+        self._check(self.lib.csg_encode_jpeg(self.ctx, C.byref(job), stream or None), "encode_jpeg")
+
+    def jpegs_host(self, n: int, *, rgb: int, quality: int = 95, subsampling: str = "420",
+                   height: Optional[int] = None, width: Optional[int] = None, out_capacity: int = 0,
+                   stream: int = 0, views: bool = False) -> List[bytes]:
+        """:meth:`encode_jpeg` delivered to the host: the files of ``n`` frames
+        as a list of ``bytes`` (with ``views`` as memoryviews of the page-locked
+        buffer they arrived in, which lives as long as one of them: no copy).  The pass runs on a stream of the wrapper's own
+        into an output of ``out_capacity`` bytes (0: a guess from the frame
+        size), ``file_offsets`` follow it to the host, and where the total
+        overflowed the pass is repeated once with an output of the exact total.
+        The packed files cross PCIe in one copy.  ``stream`` (a raw handle, 0:
+        none) is the stream still writing ``rgb``, if any: it is waited for
+        first.  Synchronous."""
+        import torch
+        n = int(n)
+        if n == 0:
+            return []
+        H = self.height if height is None else int(height)
+        W = self.width if width is None else int(width)
+        dev = torch.device("cuda", self.device)
+        if stream:
+            torch.cuda.ExternalStream(stream, device=dev).synchronize()
+        else:
+            self.synchronize()
+        st = self.span_stream()
+        cap = int(out_capacity) or n * (H * W // 2 + 4096)   # a rendered frame at quality 95 takes a tenth of that
+        with torch.cuda.stream(st):
+            d_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            while True:
+                d_out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+                self.encode_jpeg(n, rgb=rgb, out=d_out.data_ptr(), out_capacity=cap, file_offsets=d_off.data_ptr(),
+                                 quality=quality, subsampling=subsampling, height=H, width=W, stream=st.cuda_stream)
+                off = d_off.cpu().numpy()   # waits for the stream
+                total = int(off[n])
+                if total <= cap:
+                    break
+                cap = total
+            h_out = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+            h_out.copy_(d_out[:total], non_blocking=True)
+            st.synchronize()
+            buf = h_out.numpy()
+        if views:
+            return [memoryview(buf[int(off[i]):int(off[i + 1])]) for i in range(n)]
+        return [buf[int(off[i]):int(off[i + 1])].tobytes() for i in range(n)]
+
+    def keep_rgb(self, keep: bool = True) -> None:
+        """Host-output batches (:meth:`render`, :meth:`render_files`) render
+        their RGB into the context's device image even when "rgb" is not among
+        the host outputs and no file kind needs it (csg_keep_rgb):
+        :meth:`last_rgb` then finds it."""
+        self._check(self.lib.csg_keep_rgb(self.ctx, int(bool(keep))), "keep_rgb")
+
+    def last_rgb(self):
+        """``(device pointer, frames)`` of the last host-output batch's RGB image
+        (csg_last_rgb), valid until the next batch; (0, 0) when it made none."""
+        p, nf = C.c_void_p(), C.c_uint32()
+        self._check(self.lib.csg_last_rgb(self.ctx, C.byref(p), C.byref(nf)), "last_rgb")
+        return int(p.value or 0), int(nf.value)
+
     def keep_instance(self, keep: bool = True) -> None:
         """Host-output batches (:meth:`render`, :meth:`render_files`) keep their
         instance ids on the device even when "instance" is not among the host

@@ -438,3 +438,225 @@ class FragmentWriter:
         _check(load().csgio_write_coco_fragment_amodal(path.encode(), C.byref(F), ast.ctypes.data,
                                                        asp.ctypes.data if asp.size else None, aoff.ctypes.data),
                "write_coco_fragment_amodal", path)
+
+
+# ---- baseline JPEG (csrc/csg_jpeg.h) ----------------------------------------------------
+
+JPEG_SUBSAMPLING = {"444": 0, "420": 1}
+JPEG_HEAD_BYTES = 629       # jpg::kHeadBytes: SOI .. SOS header
+JPEG_DCT_SHIFT = 20         # jpg::kDctShift: jpeg_fdct's results are coefficients * 2^20
+JPEG_ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20,
+                        13, 6, 7, 14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52,
+                        45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63])
+_JPEG_BASE_Q = np.array([
+    [16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51,
+     87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101,
+     72, 92, 95, 98, 112, 100, 103, 99],
+    [17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99]
+    + [99] * 36])
+_JPEG_DC_BITS = ([0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0], [0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0])
+_JPEG_AC_BITS = ([0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125], [0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119])
+_JPEG_AC_VALS = (bytes.fromhex(
+    "01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738"
+    "393a434445464748494a535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5"
+    "a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa"),
+    bytes.fromhex(
+    "0001020311040521310612415107617113223281081442 91a1b1c109233352f0156272d10a162434e125f11718191a262728292a353637"
+    "38393a434445464748494a535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3"
+    "a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa"))
+_JPEG_K = (None, 8035, 7568, 6811, 5793, 4551, 3135, 1598)   # round(2^14 * cos(j pi / 16) / 2)
+
+
+def jpeg_quant_tables(quality: int) -> np.ndarray:
+    """(2, 64) luminance and chrominance quantisers in zig-zag order: Annex K
+    scaled by libjpeg's quality rule."""
+    if not 1 <= int(quality) <= 100:
+        raise ValueError(f"jpeg quality {quality} outside 1..100")
+    s = 5000 // int(quality) if quality < 50 else 200 - 2 * int(quality)
+    return np.clip((_JPEG_BASE_Q * s + 50) // 100, 1, 255)[:, JPEG_ZIGZAG]
+
+
+def _jpeg_canonical(bits, vals):
+    codes, code, k = {}, 0, 0
+    for n in range(1, 17):
+        for _ in range(bits[n - 1]):
+            codes[vals[k]] = (code, n)
+            code += 1
+            k += 1
+        code <<= 1
+    return codes
+
+
+def jpeg_huffman_codes():
+    """[(dc, ac)] for the luminance and the chrominance tables of Annex K.3:
+    dicts symbol -> (code, bits)."""
+    return [(_jpeg_canonical(_JPEG_DC_BITS[c], bytes(range(12))), _jpeg_canonical(_JPEG_AC_BITS[c], _JPEG_AC_VALS[c]))
+            for c in range(2)]
+
+
+def _jpeg_dct8(a: np.ndarray, rnd: int, shift: int) -> np.ndarray:
+    """jpg::dct8 along the last axis of an int64 array."""
+    _, k1, k2, k3, k4, k5, k6, k7 = _JPEG_K
+    s = a[..., :4] + a[..., :3:-1]
+    d = a[..., :4] - a[..., :3:-1]
+    s0, s1, s2, s3 = (s[..., i] for i in range(4))
+    d0, d1, d2, d3 = (d[..., i] for i in range(4))
+    out = np.stack([k4 * (s0 + s1 + s2 + s3),
+                    k1 * d0 + k3 * d1 + k5 * d2 + k7 * d3,
+                    k2 * (s0 - s3) + k6 * (s1 - s2),
+                    k3 * d0 - k7 * d1 - k1 * d2 - k5 * d3,
+                    k4 * (s0 - s1 - s2 + s3),
+                    k5 * d0 - k1 * d1 + k7 * d2 + k3 * d3,
+                    k6 * (s0 - s3) - k2 * (s1 - s2),
+                    k7 * d0 - k5 * d1 + k3 * d2 - k1 * d3], axis=-1)
+    return (out + rnd) >> shift
+
+
+def jpeg_fdct(blocks: np.ndarray) -> np.ndarray:
+    """jpg::fdct8x8 of (..., 8, 8) level-shifted integer samples: int64
+    coefficients * 2^JPEG_DCT_SHIFT, [..., v, u]."""
+    t = _jpeg_dct8(np.asarray(blocks).astype(np.int64), 128, 8)                        # rows
+    return np.swapaxes(_jpeg_dct8(np.swapaxes(t, -1, -2), 0, 0), -1, -2)              # columns
+
+
+def jpeg_ycc(rgb: np.ndarray):
+    """jpg::ycc of an (..., 3) uint8 array: int64 Y, Cb, Cr in 0..255."""
+    r, g, b = (np.asarray(rgb)[..., i].astype(np.int64) for i in range(3))
+    return ((19595 * r + 38470 * g + 7471 * b + 32768) >> 16,
+            (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16,
+            (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16)
+
+
+def jpeg_samples(rgb: np.ndarray, subsampling: str = "420"):
+    """The level-shifted sample blocks of an (H, W, 3) uint8 image in the
+    scan's order: int64 (MCU rows, blocks per row, 8, 8), and the component
+    (0 Y, 1 Cb, 2 Cr) of each block of a row."""
+    sub = JPEG_SUBSAMPLING[str(subsampling)]
+    H, W = rgb.shape[:2]
+    m = 16 if sub else 8
+    my, mx = -(-H // m), -(-W // m)
+    ext = np.pad(rgb, ((0, my * m - H), (0, mx * m - W), (0, 0)), mode="edge")
+    planes = [p - 128 for p in jpeg_ycc(ext)]
+
+    def cut(p):   # (rows of blocks, blocks, 8, 8)
+        return p.reshape(p.shape[0] // 8, 8, p.shape[1] // 8, 8).swapaxes(1, 2)
+
+    if sub:
+        y = cut(planes[0]).reshape(my, 2, mx, 2, 8, 8).transpose(0, 2, 1, 3, 4, 5).reshape(my, mx, 4, 8, 8)
+        c = [cut(((p + 128).reshape(my * 8, 2, mx * 8, 2).sum(axis=(1, 3)) + 2 >> 2) - 128) for p in planes[1:]]
+        blocks = np.concatenate([y, c[0][:, :, None], c[1][:, :, None]], axis=2)
+        comp = [0, 0, 0, 0, 1, 2]
+    else:
+        blocks = np.stack([cut(p) for p in planes], axis=2)
+        comp = [0, 1, 2]
+    return blocks.reshape(my, mx * len(comp), 8, 8), np.array(comp * mx)
+
+
+def jpeg_coefficients(rgb: np.ndarray, quality: int = 95, subsampling: str = "420"):
+    """The quantised coefficients of jpeg_bytes in the scan's order: int64
+    (MCU rows, blocks per row, 64) in zig-zag order with the DC absolute, and
+    each block's component."""
+    blocks, comp = jpeg_samples(rgb, subsampling)
+    F = jpeg_fdct(blocks).reshape(*blocks.shape[:2], 64)[..., JPEG_ZIGZAG]
+    d = jpeg_quant_tables(quality)[np.minimum(comp, 1)].astype(np.int64) << JPEG_DCT_SHIFT   # (blocks, 64)
+    q = np.sign(F) * ((np.abs(F) + (d >> 1)) // d)
+    q[..., 1:] = np.clip(q[..., 1:], -1023, 1023)
+    if JPEG_SUBSAMPLING[str(subsampling)]:
+        # a luminance block with no pixel of the image repeats the DC of the block before it in its MCU
+        # and has no AC (jpg::luma_source)
+        H, W = rgb.shape[:2]
+        mcu = q.reshape(q.shape[0], -1, 6, 64)
+        col = (np.arange(mcu.shape[1]) * 16 + 8 < W)[None, :]
+        row = (np.arange(mcu.shape[0]) * 16 + 8 < H)[:, None]
+        s1 = np.where(col, 1, 0) + np.zeros_like(row, int)
+        source = {1: s1, 2: np.where(row, 2, s1), 3: np.where(row, np.where(col, 3, 2), s1)}
+        dc = mcu[..., 0].copy()
+        for k, src in source.items():
+            empty = src != k
+            mcu[:, :, k][empty] = 0
+            mcu[:, :, k, 0][empty] = np.take_along_axis(dc, src[..., None], 2)[..., 0][empty]
+    return q, comp
+
+
+def jpeg_header(width: int, height: int, quality: int = 95, subsampling: str = "420") -> bytes:
+    """SOI, APP0, DQT x 2, SOF0, DHT x 4, DRI, SOS header of jpeg_bytes."""
+    import struct
+    sub = JPEG_SUBSAMPLING[str(subsampling)]
+    q = jpeg_quant_tables(quality)
+    mx = -(-width // (16 if sub else 8))
+    h = b"\xff\xd8\xff\xe0" + struct.pack(">H5sHBHHBB", 16, b"JFIF\0", 0x0101, 0, 1, 1, 0, 0)
+    for c in range(2):
+        h += b"\xff\xdb" + struct.pack(">HB", 67, c) + bytes(q[c].tolist())
+    h += b"\xff\xc0" + struct.pack(">HBHHB", 17, 8, height, width, 3)
+    h += bytes([1, 0x22 if sub else 0x11, 0, 2, 0x11, 1, 3, 0x11, 1])
+    for c in range(2):
+        h += b"\xff\xc4" + struct.pack(">HB", 31, c) + bytes(_JPEG_DC_BITS[c]) + bytes(range(12))
+        h += b"\xff\xc4" + struct.pack(">HB", 181, 0x10 | c) + bytes(_JPEG_AC_BITS[c]) + _JPEG_AC_VALS[c]
+    h += b"\xff\xdd" + struct.pack(">HH", 4, mx)
+    h += b"\xff\xda" + struct.pack(">HB", 12, 3) + bytes([1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0])
+    assert len(h) == JPEG_HEAD_BYTES
+    return h
+
+
+def jpeg_bytes(rgb: np.ndarray, quality: int = 95, subsampling: str = "420") -> bytes:
+    """The JPEG of csg_encode_jpeg (``Renderer.jpegs_host``), byte for byte, of
+    an (H, W, 3) uint8 image: a baseline JFIF file laid out as libjpeg writes
+    one with a restart interval per MCU row, Y Cb Cr in one scan at 4:4:4 or
+    4:2:0, Annex K's tables at libjpeg's quality scaling, and the integer
+    colour conversion, chroma mean, DCT and quantiser of csrc/csg_jpeg.h (the
+    native statement).  NumPy and plain Python, for tests, the CPU writer path
+    and readers of the format."""
+    a = np.asarray(rgb)
+    if a.dtype != np.uint8:
+        raise TypeError(f"jpeg_bytes: image of {a.dtype}, not uint8")
+    if a.ndim != 3 or a.shape[2] != 3 or not (1 <= a.shape[0] <= 8192 and 1 <= a.shape[1] <= 8192):
+        raise ValueError(f"jpeg_bytes: image of shape {a.shape}, not (H, W, 3) with H, W in 1..8192")
+    if str(subsampling) not in JPEG_SUBSAMPLING:
+        raise ValueError(f"jpeg_bytes: subsampling {subsampling!r} is neither '444' nor '420'")
+    H, W = a.shape[:2]
+    out = bytearray(jpeg_header(W, H, quality, subsampling))
+    coef, comp = jpeg_coefficients(a, quality, subsampling)
+    codes = jpeg_huffman_codes()
+    n_comp = 3
+    for r in range(coef.shape[0]):
+        acc, nbits = 0, 0
+        pred = [0] * n_comp
+        for zz, c in zip(coef[r].tolist(), comp.tolist()):
+            dc, ac = codes[min(c, 1)]
+            diff = max(-2047, min(2047, zz[0] - pred[c]))
+            pred[c] = zz[0]
+            s = abs(diff).bit_length()
+            code, n = dc[s]
+            acc = (((acc << n) | code) << s) | ((diff - 1 if diff < 0 else diff) & ((1 << s) - 1))
+            nbits += n + s
+            run = 0
+            for v in zz[1:]:
+                if v == 0:
+                    run += 1
+                    continue
+                while run >= 16:
+                    code, n = ac[0xF0]
+                    acc = (acc << n) | code
+                    nbits += n
+                    run -= 16
+                s = abs(v).bit_length()
+                code, n = ac[(run << 4) | s]
+                acc = (((acc << n) | code) << s) | ((v - 1 if v < 0 else v) & ((1 << s) - 1))
+                nbits += n + s
+                run = 0
+            if run:
+                code, n = ac[0]
+                acc = (acc << n) | code
+                nbits += n
+        pad = -nbits % 8
+        data = ((acc << pad) | ((1 << pad) - 1)).to_bytes((nbits + pad) // 8, "big")
+        out += data.replace(b"\xff", b"\xff\x00")
+        if r + 1 < coef.shape[0]:
+            out += bytes([0xFF, 0xD0 + (r & 7)])
+    return bytes(out + b"\xff\xd9")
+
+
+def write_jpeg(path: str, rgb: np.ndarray, quality: int = 95, subsampling: str = "420") -> None:
+    """``jpeg_bytes`` of an (H, W, 3) uint8 image to ``path`` (the generator's writer processes)."""
+    with open(path, "wb") as fh:
+        fh.write(jpeg_bytes(rgb, quality, subsampling))

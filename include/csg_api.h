@@ -66,6 +66,8 @@
  *                               the whole frame, with its amodal box and pixel count
  *   csg_encode_span_masks ..... (new) those spans as finished per-object mask PNG files
  *                               (BOP's `mask_visib` / `mask` folders), packed in device memory
+ *   csg_encode_jpeg ........... (new) RGB frames in device memory as finished baseline JPEG
+ *                               files (BOP's `rgb/%06d.jpg`), packed in device memory
  *   csg_sample_object_points .. (new) N pixels of each object's visible mask with their
  *                               image indices, camera-frame points, colours and object
  *                               coordinates: the input of the point-based pose networks
@@ -874,6 +876,70 @@ typedef struct {
   uint64_t* file_offsets;      /* DEVICE [n_items + 1], 8-B aligned */
 } csg_mask_png_job;
 int csg_encode_span_masks(csg_ctx* ctx, const csg_mask_png_job* job, void* stream);
+
+/* Baseline JPEG files of RGB frames, made on the GPU.  A stand-alone pass on
+ * device memory only, like csg_encode_span_masks: it needs no scene and no
+ * earlier render, and the frame size is the job's own.  Frame f becomes one
+ * .jpg file; the files are packed back to back in `out`: file f occupies
+ * out[file_offsets[f] .. file_offsets[f + 1]), file_offsets[0] = 0, and
+ * file_offsets[n_frames] is the exact total whether or not it fits.  Nothing is
+ * written beyond out_capacity, and a file that does not fit whole is not written
+ * at all: the caller reads file_offsets[n_frames] after its stream completes and
+ * repeats the pass with an output of that size.
+ *
+ * The file, byte for byte (one deterministic encoding; csrc/csg_jpeg.h, and
+ * writers.jpeg_bytes in Python): SOI; APP0 (JFIF 1.01, density 1:1, no
+ * thumbnail); two DQT (Annex K's tables at libjpeg's quality scaling, zig-zag
+ * order); SOF0 with the true W and H and components Y, Cb, Cr (ids 1, 2, 3) at
+ * 4:4:4 or 4:2:0; four DHT (Annex K.3's typical tables: DC0, AC0, DC1, AC1); DRI
+ * with the MCUs of one MCU row; SOS; one interleaved scan in which every MCU row
+ * is a restart interval, padded with 1-bits and followed by RSTm (m counting mod
+ * 8) except the last; EOI.  A zero byte follows every 0xFF byte of entropy data.
+ * Colour is JFIF's full-range BT.601 in 16-bit fixed point, the image extends to
+ * whole MCUs by repeating its last column and row, 4:2:0 chroma is the rounded
+ * mean of 2 x 2 samples, the DCT is an integer one within 0.2 of the exact
+ * transform, and the quantiser rounds half away from zero.  A 4:2:0 luminance
+ * block that holds no pixel of the image repeats the DC of the block before it
+ * in its MCU and has no AC.
+ *
+ * Asynchronous on `stream` (NULL = the context's stream); behind the kernel that
+ * wrote `rgb` on the same stream it needs no synchronisation.  The result is a
+ * pure function of the input.  Scratch is the pass's own, under an order of its
+ * own: per 8 x 8 block 128 bytes of coefficients, 4 bytes of bit counts and a
+ * 208-byte staging slot, bounded at 256 MiB: a job that needs more runs as
+ * ranges of frames on the stream; CSG_JPEG_SCRATCH_CAP, bytes, overrides the
+ * bound.
+ *
+ * CSG_ERR_INVALID, nothing enqueued or written: job, rgb, out or file_offsets
+ * NULL; n_frames 0; width or height 0 or above 8192; quality outside 1..100;
+ * a subsampling other than CSG_JPEG_444 and CSG_JPEG_420; file_offsets not
+ * 8-byte aligned. */
+#define CSG_JPEG_444 0u
+#define CSG_JPEG_420 1u
+typedef struct {
+  uint32_t width, height;     /* 1..8192 each */
+  uint32_t n_frames;          /* >= 1 */
+  uint32_t quality;           /* 1..100 */
+  uint32_t subsampling;       /* CSG_JPEG_444 = 0, CSG_JPEG_420 = 1 */
+  uint32_t pad;
+  const uint8_t* rgb;         /* DEVICE [n_frames][H][W][3], any alignment */
+  uint8_t* out;               /* DEVICE [out_capacity] */
+  uint64_t out_capacity;
+  uint64_t* file_offsets;     /* DEVICE [n_frames + 1], 8-B aligned */
+} csg_jpeg_job;
+int csg_encode_jpeg(csg_ctx* ctx, const csg_jpeg_job* job, void* stream);
+
+/* The RGB of a host-output batch for csg_encode_jpeg, without its trip to the
+ * host: the exact counterparts of csg_keep_instance and csg_last_instance.
+ * After csg_keep_rgb(ctx, 1) every later host-output batch renders its RGB into
+ * the context's own device image even when csg_outputs.rgb is NULL and no file
+ * kind asks for it, and copies nothing more than it did; 0 turns that off again.
+ * csg_last_rgb returns the device image [n_frames][height][width][3] uint8 of the
+ * context's last batch and its frame count (NULL and 0 when that batch rendered
+ * no RGB, or wrote it to the caller's device memory); it stays valid until the
+ * context's next batch.  Neither call touches the GPU. */
+int csg_keep_rgb(csg_ctx* ctx, int32_t keep);
+int csg_last_rgb(csg_ctx* ctx, const uint8_t** rgb, uint32_t* n_frames);
 
 /* Fixed-size per-object point samples: for each slot of `info`, N pixels drawn
  * from the visible mask of the slot's label, as their indices in the image
