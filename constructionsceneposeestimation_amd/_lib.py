@@ -34,6 +34,7 @@ EXPORTED = (
     "csg_crop_objects_filtered", "csg_crop_amodal", "csg_crop_amodal_geometry", "csg_mask_spans",
     "csg_keep_instance", "csg_last_instance", "csg_amodal_spans", "csg_sample_object_points",
     "csg_encode_span_masks", "csg_encode_jpeg", "csg_keep_rgb", "csg_last_rgb",
+    "csg_voxel_cloud", "csg_keep_points", "csg_last_points",
 )
 
 
@@ -168,6 +169,14 @@ class PointJob(C.Structure):
                 ("pt_xyz", C.c_void_p), ("pt_rgb", C.c_void_p), ("pt_coords", C.c_void_p)]
 
 
+class VoxelJob(C.Structure):
+    """csg_voxel_job (csg_voxel_cloud)."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n_labels", C.c_uint32), ("capacity", C.c_uint32),
+                ("voxel_size", C.c_float), ("pad", C.c_uint32), ("points", C.c_void_p), ("rgb", C.c_void_p),
+                ("instance", C.c_void_p), ("vx_xyz", C.c_void_p), ("vx_rgb", C.c_void_p), ("vx_label", C.c_void_p),
+                ("vx_count", C.c_void_p), ("vx_total", C.c_void_p), ("vx_dropped", C.c_void_p)]
+
+
 class EncodeJob(C.Structure):
     """csg_encode_job (csg_encode_files)."""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n_frames", C.c_uint32), ("file_kinds", C.c_uint32),
@@ -252,6 +261,9 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     lib.csg_sample_object_points.argtypes = [vp, C.POINTER(PointJob), u32, vp]
     lib.csg_encode_span_masks.argtypes = [vp, C.POINTER(MaskPngJob), vp]
     lib.csg_encode_jpeg.argtypes = [vp, C.POINTER(JpegJob), vp]
+    lib.csg_voxel_cloud.argtypes = [vp, C.POINTER(VoxelJob), u32, vp]
+    lib.csg_keep_points.argtypes = [vp, i32]
+    lib.csg_last_points.argtypes = [vp, C.POINTER(vp), C.POINTER(u32)]
     lib.csg_keep_rgb.argtypes = [vp, i32]
     lib.csg_last_rgb.argtypes = [vp, C.POINTER(vp), C.POINTER(u32)]
     lib.csg_keep_instance.argtypes = [vp, i32]

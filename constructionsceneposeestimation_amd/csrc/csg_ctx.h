@@ -15,6 +15,7 @@
 #include "csg_jpeg.h"
 #include "csg_kernels.h"
 #include "csg_mask_png.h"
+#include "csg_voxels.h"
 
 namespace csg {
 
@@ -324,6 +325,17 @@ struct csg_ctx {
   DevBuf<uint8_t> jp_z;
   DevBuf<uint64_t> jp_fsize;
   csg::PassOrder jp;
+  // Voxel clouds (csg_voxel_cloud): the pass's own scratch -- of one range of frames the tables, the
+  // bitmaps of the voxels' lowest pixels with their word prefixes, and the frames' counters -- grown to the
+  // job, under an order of its own.
+  DevBuf<csg::VxSlot> vx_slots;
+  DevBuf<uint32_t> vx_words;
+  DevBuf<csg::VxFrame> vx_frames;
+  csg::PassOrder vx;
+  // csg_keep_points / csg_last_points: host-output batches render their points into o_points whether or not anything copies them
+  bool keep_points = false;
+  const float* kept_points = nullptr;
+  uint32_t kept_points_frames = 0;
   // csg_keep_rgb / csg_last_rgb: host-output batches render their RGB into o_rgb whether or not anything copies it
   bool keep_rgb = false;
   const uint8_t* kept_rgb = nullptr;

@@ -1,7 +1,7 @@
 // The stand-alone passes of libcsg.so (see include/csg_api.h): object crops, mask spans, mask PNGs, object
-// points and the three amodal passes.  Each validates its job on the host, orders itself behind the last pass
-// that used its scratch (PassOrder, csg_ctx.h), grows that scratch and enqueues its kernels on the
-// caller's stream.  None of them touches a render's work buffers.
+// points, voxel clouds and the three amodal passes.  Each validates its job on the host, orders itself
+// behind the last pass that used its scratch (PassOrder, csg_ctx.h), grows that scratch and enqueues its
+// kernels on the caller's stream.  None of them touches a render's work buffers.
 #include <stdlib.h>
 #include <string.h>
 
@@ -381,6 +381,73 @@ int csg_sample_object_points(csg_ctx* c, const csg_point_job* job, uint32_t n_fr
   launch_pts_emit(a, n_frames, st);
   HIP_TRY(c, hipGetLastError());
   return c->op.end(c, st);
+}
+
+// Voxel clouds: a stand-alone pass over device arrays (no scene state, no work buffers); validates the
+// job, grows the pass's own scratch and enqueues the kernels.  The scratch (a table of T slots of 64 bytes
+// and two bitmap-sized arrays per frame) is bounded at kVoxelScratchCap bytes: a job that needs more runs
+// as ranges of frames on the stream, each initialising, filling and reading the same scratch.
+int csg_voxel_cloud(csg_ctx* c, const csg_voxel_job* job, uint32_t n_frames, void* stream) {
+  constexpr size_t kVoxelScratchCap = 256u << 20;
+  if (!c) return CSG_ERR_INVALID;
+  if (!job) return c->fail(CSG_ERR_INVALID, "voxel_cloud: null job");
+  if (n_frames == 0) return c->fail(CSG_ERR_INVALID, "voxel_cloud: no frames");
+  CSG_TRY(check_frame_dims(c, "voxel_cloud", job->width, job->height));
+  if (!std::isfinite(job->voxel_size) || !(job->voxel_size > 0.0f))
+    return c->fail(CSG_ERR_INVALID, "voxel_cloud: voxel_size %g is not a finite value > 0", (double)job->voxel_size);
+  if (job->capacity == 0) return c->fail(CSG_ERR_INVALID, "voxel_cloud: capacity must be at least 1");
+  if (job->instance && (job->n_labels == 0 || job->n_labels > CSG_SPAN_MAX_LABELS))
+    return c->fail(CSG_ERR_INVALID, "voxel_cloud: n_labels %u outside 1..%u", job->n_labels, CSG_SPAN_MAX_LABELS);
+  if (!job->points || !job->vx_total) return c->fail(CSG_ERR_INVALID, "voxel_cloud: points and vx_total must not be NULL");
+  if (((uintptr_t)job->points | (uintptr_t)job->instance | (uintptr_t)job->vx_xyz | (uintptr_t)job->vx_label |
+       (uintptr_t)job->vx_count | (uintptr_t)job->vx_total | (uintptr_t)job->vx_dropped) & 3u)
+    return c->fail(CSG_ERR_INVALID, "voxel_cloud: every pointer but rgb and vx_rgb must be 4-byte aligned");
+  hipStream_t st;
+  CSG_TRY(pass_stream(c, stream, &st));
+  VoxelArgs a{};
+  a.W = job->width;
+  a.H = job->height;
+  a.P = job->width * job->height;
+  a.L = job->instance ? job->n_labels : 0u;
+  a.C = job->capacity;
+  a.Ceff = std::min(a.C, a.P);
+  a.T = 2;
+  while (a.T < 2u * a.Ceff) a.T <<= 1;   // Ceff <= 2^26
+  a.BW = (a.P + 31u) / 32u;
+  a.s = job->voxel_size;
+  a.r = 1.0f / job->voxel_size;
+  a.combine = 1;
+  if (const char* e = getenv("CSG_VOXEL_COMBINE")) a.combine = atoi(e) != 0;   // (A/B: 0 = an atomic per point)
+  a.points = job->points;
+  a.rgb = job->rgb;
+  a.instance = job->instance;
+  a.vx_xyz = job->vx_xyz;
+  a.vx_rgb = job->vx_rgb;
+  a.vx_label = job->vx_label;
+  a.vx_count = job->vx_count;
+  a.vx_total = job->vx_total;
+  a.vx_dropped = job->vx_dropped;
+  const size_t per_frame = (size_t)a.T * sizeof(VxSlot) + (size_t)a.BW * 8u + sizeof(VxFrame);
+  size_t cap = kVoxelScratchCap;
+  if (const char* e = getenv("CSG_VOXEL_SCRATCH_CAP")) cap = (size_t)strtoull(e, nullptr, 10);   // (tests: bytes)
+  const uint32_t range = (uint32_t)std::min<size_t>(std::min<uint32_t>(n_frames, 65535u),   // grid y limit
+                                                    std::max<size_t>(1, cap / per_frame));
+  const size_t n_slots = (size_t)range * a.T, n_words = (size_t)range * a.BW * 2u;
+  CSG_TRY(c->vx.begin(c, st, c->vx_slots.n < n_slots || c->vx_words.n < n_words || c->vx_frames.n < range));
+  HIP_TRY(c, c->vx_slots.alloc(n_slots));
+  HIP_TRY(c, c->vx_words.alloc(n_words));
+  HIP_TRY(c, c->vx_frames.alloc(range));
+  a.slots = c->vx_slots.p;
+  a.bitmap = c->vx_words.p;
+  a.wprefix = c->vx_words.p + (size_t)range * a.BW;
+  a.frames = c->vx_frames.p;
+  for (uint32_t f0 = 0; f0 < n_frames; f0 += range) {
+    a.first = f0;
+    a.n = std::min(range, n_frames - f0);
+    launch_voxels(a, st);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return c->vx.end(c, st);
 }
 
 // Amodal crop masks: reads the scene tables (synced here as a render syncs them) and the caller's

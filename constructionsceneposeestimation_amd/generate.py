@@ -29,6 +29,12 @@ same files:
   pointcloud/pointcloud_%06d.txt   (:1716-1757; points from the GPU resolve, text encoded on the GPU)
   pointcloud/pointcloud_%06d.ply   (optional "pointcloud_ply": the same points as a binary PLY, xyz
                                     float32 + rgb uchar, 15 B per point; no reference counterpart)
+  pointcloud/voxels_%06d.ply       (optional "pointcloud_voxel_ply": the frame's points voxel-downsampled on
+                                    the GPU on a world-fixed grid of --voxel-size metres, one record per
+                                    (cell, object): centroid, mean colour, ``label`` = the mask's inst_idx
+                                    (-1 background) and point count, 23 B per record, voxel_cloud.read_ply;
+                                    + pointcloud/objects.json as obj_coords' and the grid; no reference
+                                    counterpart)
   depth/depth16_%06d.png           (optional "depth16_png": 16-bit grey PNG at a fixed number of counts
                                     per metre, writers.depth_to_u16) + depth/depth16.json (the scale;
                                     0 = no hit)
@@ -74,6 +80,7 @@ from . import bop
 from . import camera_math as cm
 from . import masks
 from . import prep_pool
+from . import voxel_cloud
 from .crops import DYNAMIC_KINDS, eligible_labels
 from .labels import OBJECT_LISTS, in_frustum, label_record, object_box, object_poses
 from .quality_log import QualityLog
@@ -102,7 +109,7 @@ def _log_done(log: QualityLog, fut, log_args: dict, points: bool) -> None:
 
 
 OUTPUTS = ("rgb", "mask", "depth_csv", "depth_png", "depth_npy", "pointcloud", "normals", "obj_coords",
-           "pointcloud_ply", "depth16_png", "mask_rle", "amodal_rle", "rgb_jpg")
+           "pointcloud_ply", "depth16_png", "mask_rle", "amodal_rle", "rgb_jpg", "pointcloud_voxel_ply")
 # What the reference writes for every frame (GDP:1668-1771, 2055-2072): RGB PNG, depth CSV and
 # JET depth PNG, point-cloud TXT, instance mask .npy; the label JSON is always written (it is the
 # resume marker).
@@ -120,7 +127,7 @@ FILE_OF_OUTPUT = (("rgb", "rgb_png"), ("depth_csv", "depth_csv"), ("depth_png", 
 _PATHS = {"rgb": ("rgb", "rgb_{:06d}.png"), "depth_csv": ("depth", "depth_{:06d}.csv"),
           "depth_png": ("depth", "depth_{:06d}.png"), "pointcloud": ("pointcloud", "pointcloud_{:06d}.txt"),
           "pointcloud_ply": ("pointcloud", "pointcloud_{:06d}.ply"), "depth16_png": ("depth", "depth16_{:06d}.png"),
-          "rgb_jpg": ("rgb", "rgb_{:06d}.jpg")}
+          "rgb_jpg": ("rgb", "rgb_{:06d}.jpg"), "pointcloud_voxel_ply": ("pointcloud", "voxels_{:06d}.ply")}
 _ENCODED_KIND = {"pointcloud": "encoded_pointcloud", "pointcloud_ply": "encoded_ply"}   # writer_pool.write_frame
 
 
@@ -149,6 +156,8 @@ def check_bop(outs) -> None:
     clash = [x for x in BOP_EXCLUDES if x in outs] if BOP_OUTPUT in outs else []
     if clash:
         raise ValueError(f"output bop writes its own per-object masks: it does not go with {clash}")
+    if BOP_OUTPUT in outs and "pointcloud_voxel_ply" in outs:
+        raise ValueError("output bop has no place for voxel clouds: it does not go with pointcloud_voxel_ply")
 
 
 def render_outputs(outs: set, gpu_files: bool, host_depth: bool, occlusion: bool) -> list:
@@ -176,7 +185,8 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
              occlusion: bool = False, sink: str = "disk", validate_pointcloud: bool = False,
              min_points: int = 100, max_retries: int = 5, prep_workers: int = -1,
              depth16_counts_per_metre: float = 250.0, amodal_kinds: Optional[Sequence[str]] = None,
-             jpeg_quality: int = 95, jpeg_subsampling: str = "420", bop_rgb: str = "png") -> dict:
+             jpeg_quality: int = 95, jpeg_subsampling: str = "420", bop_rgb: str = "png",
+             voxel_size: float = voxel_cloud.DEFAULT_VOXEL_SIZE, voxel_capacity: int = 0) -> dict:
     """Render ``frames`` on one GPU and write them (``outputs``, default the
     reference's set; ``depth`` / ``depth_csv`` / ``pointcloud`` / ``normals``
     add the depth .npy, the depth .npy + CSV, the point cloud, the normals).
@@ -231,6 +241,15 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
     Writer processes encode the host RGB with writers.jpeg_bytes (the same
     bytes).  ``bop_rgb`` "jpg": output "bop" writes ``rgb/%06d.jpg`` from the
     same pass instead of the RGB PNG.
+    ``outputs`` with "pointcloud_voxel_ply": ``pointcloud/voxels_%06d.ply``, the
+    frame's world-space points voxel-downsampled on a grid of ``voxel_size``
+    metres that is fixed in the world, one labelled record per (cell, object)
+    (voxel_cloud.py).  The batch keeps its points, ids and RGB on the device
+    (csg_keep_points, csg_keep_instance, csg_keep_rgb), the records are made
+    there behind the render (Renderer.voxel_cloud_host, csg_voxel_cloud) and only
+    they cross PCIe.  ``voxel_capacity``: records per frame the pass starts with
+    (0: voxel_cloud.DEFAULT_VOXEL_CAPACITY); a renderer keeps what its retries
+    settled on.  Not with "bop".
     ``prep_workers``: processes that prepare batches ahead (epoch layouts,
     object poses, cameras; prep_pool.py), so that numpy work does not hold
     this process's GIL; -1 = two for runs of at least 20 batches, else none."""
@@ -267,15 +286,22 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
         bop.check_depth_scale(wl.intr.near, depth16_counts_per_metre)
     for d in ("rgb", "labels", "depth", "pointcloud", "normals", "logs"):
         os.makedirs(os.path.join(out_dir, d), exist_ok=True)
-    if "obj_coords" in outs:   # the boxes that turn the maps back into metres (labels.decode_obj_coords)
-        os.makedirs(os.path.join(out_dir, "obj_coords"), exist_ok=True)
+    want_vox = "pointcloud_voxel_ply" in outs
+    if want_vox and not (np.isfinite(float(voxel_size)) and float(voxel_size) > 0 and int(voxel_capacity) >= 0):
+        raise ValueError(f"voxel_size {voxel_size!r}: a finite number > 0; voxel_capacity {voxel_capacity!r}: >= 0")
+    if "obj_coords" in outs or want_vox:
         objs = []
         for o in wl.scene.objects:
             box = object_box(o)
             objs.append({"prim_path": o.prim_path, "class_name": o.class_name, "inst_idx": int(o.inst_idx),
                          "lo": box[0].tolist() if box else None, "hi": box[1].tolist() if box else None})
+    if "obj_coords" in outs:   # the boxes that turn the maps back into metres (labels.decode_obj_coords)
+        os.makedirs(os.path.join(out_dir, "obj_coords"), exist_ok=True)
         with open(os.path.join(out_dir, "obj_coords", "objects.json"), "w") as fh:
             json.dump({"objects": objs}, fh, indent=2)
+    if want_vox:   # what a record's label names, and the grid
+        with open(os.path.join(out_dir, "pointcloud", "objects.json"), "w") as fh:
+            json.dump({"objects": objs, "voxel_size": float(np.float32(voxel_size))}, fh, indent=2)
     if "amodal_rle" in outs and "mask_rle" not in outs:
         raise ValueError("output amodal_rle adds to the annotations of mask_rle: ask for both")
     if "mask_rle" in outs:
@@ -343,6 +369,13 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
     if want_jpg and gpu_files:   # ... and their RGB for the JPEG pass, whether or not anything else needs it
         for x in rends:
             x.keep_rgb(True)
+    if want_vox:    # ... and their points, ids and RGB for the voxel pass
+        for x in rends:
+            x.keep_points(True)
+            x.keep_instance(True)
+            x.keep_rgb(True)
+    vox_cap = {}    # renderer -> the voxel capacity its last batch needed (voxel_cloud_host grows it)
+    vox_stats = {"frames": 0, "voxels": 0, "voxels_max": 0}
     jpg_cap = {}    # renderer -> the bytes its last batch's JPEG files took (jpegs_host repeats a pass that overflows)
     bop_masks, bop_em, bop_scenes = {}, {}, set()   # per renderer; per epoch (bop.epoch_models); scene folders made
     if want_bop:
@@ -467,6 +500,18 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
             jpg_cap[id(r)] = nb + nb // 4
             return nb
 
+        voxr = [None]  # the batch's (voxels_%06d.ply file, records) per frame, with "pointcloud_voxel_ply"
+
+        def voxels_of_batch() -> int:
+            (pts, n0), (ids, n1), (rgb, n2) = r.last_points(), r.last_instance(), r.last_rgb()
+            if not pts or not ids or not rgb or {n0, n1, n2} != {len(fb)}:
+                raise RuntimeError(f"pointcloud_voxel_ply: the batch kept {n0} point, {n1} id and {n2} RGB images, "
+                                   f"{len(fb)} frames rendered")
+            recs, vox_cap[id(r)], _ = r.voxel_cloud_host(len(fb), voxel_size, points=pts, rgb=rgb, instance=ids,
+                                                         capacity=vox_cap.get(id(r), int(voxel_capacity)))
+            voxr[0] = [(voxel_cloud.ply_bytes(x), len(x)) for x in recs]
+            return sum(x.nbytes for x in recs)
+
         cur = [None]   # the cameras of the attempt being rendered
 
         def run(views, projs):
@@ -481,11 +526,13 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                                                            free=r.free_host_buffer), len(fb) * nk)
                 arrays["file_offsets"] = offsets
                 d2h.append(int(offsets[-1]) + wire_bytes(out) + (spans_of_batch() if want_rle else 0)
-                           + (bop_of_batch() if want_bop else 0) + (jpgs_of_batch() if want_jpg else 0))
+                           + (bop_of_batch() if want_bop else 0) + (jpgs_of_batch() if want_jpg else 0)
+                           + (voxels_of_batch() if want_vox else 0))
             else:
                 out = r.render(fr, want=want, out={k: v[:len(fb)] for k, v in arrays.items()})
                 d2h.append(wire_bytes(out) + (spans_of_batch() if want_rle else 0)
-                           + (jpgs_of_batch() if want_jpg and gpu_files else 0))
+                           + (jpgs_of_batch() if want_jpg and gpu_files else 0)
+                           + (voxels_of_batch() if want_vox else 0))
             return out
 
         out = run(views, projs)
@@ -511,7 +558,7 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                 out = run(*wl.frame_params(fb, attempts))
                 check = again
         te = time.time()
-        return fb, slot, out, (te - tr, tp - tw, tr - tp), attempts, checks, failed, (rle[0], arle[0], bopr[0], jpgr[0])
+        return fb, slot, out, (te - tr, tp - tw, tr - tp), attempts, checks, failed, (rle[0], arle[0], bopr[0], jpgr[0], voxr[0])
 
     ahead = ThreadPoolExecutor(max_workers=n_rend)
     prep = ThreadPoolExecutor(max_workers=max(1, n_prep))
@@ -527,7 +574,7 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
         queued = [ahead.submit(render_batch, b) for b in range(min(n_rend, len(starts)))]
         for b in range(len(starts)):
             tq = time.time()
-            fb, slot, out, (dt, dwait, dprep), attempts, checks, failed, (rle, arle, bopr, jpgr) = queued.pop(0).result()
+            fb, slot, out, (dt, dwait, dprep), attempts, checks, failed, (rle, arle, bopr, jpgr, voxr) = queued.pop(0).result()
             t_main_wait += time.time() - tq
             t_render += dt
             t_slot_wait += dwait
@@ -579,6 +626,12 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                                   (partial(bop.write_bytes, data=jpgr[k]) if gpu_files else
                                    partial(write_jpeg, rgb=out["rgb"][k].copy(), quality=jpeg_quality,
                                            subsampling=jpeg_subsampling),)))
+                if want_vox:   # made on the GPU behind the batch
+                    files.append((file_path(out_dir, "pointcloud_voxel_ply", f), "call",
+                                  (partial(bop.write_bytes, data=voxr[k][0]),)))
+                    vox_stats["frames"] += 1
+                    vox_stats["voxels"] += voxr[k][1]
+                    vox_stats["voxels_max"] = max(vox_stats["voxels_max"], voxr[k][1])
                 if want_bop:   # the two images from the GPU encoders, the mask files, then the fragment
                     if f // bop.FRAMES_PER_SCENE not in bop_scenes and sink == "disk":
                         bop.make_dirs(out_dir, f // bop.FRAMES_PER_SCENE)
@@ -679,6 +732,11 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                              "sink": sink, "prep_workers": n_prep,
                              "writer_busy": round(pool.task_s / (wall * n_writers), 3) if wall > 0 else None,
                              "outputs": sorted(outs)}
+    if want_vox:
+        summary["voxel_cloud"] = {"voxel_size": float(np.float32(voxel_size)),
+                                  "capacity": max(vox_cap.values()) if vox_cap else int(voxel_capacity),
+                                  "voxels_per_frame": round(vox_stats["voxels"] / max(vox_stats["frames"], 1), 1),
+                                  "voxels_max": vox_stats["voxels_max"]}
     return summary
 
 
@@ -726,6 +784,11 @@ def main(argv=None):
     ap.add_argument("--jpeg-subsampling", default="420", choices=("444", "420"))
     ap.add_argument("--bop-rgb", default="png", choices=("png", "jpg"),
                     help="output bop: train_pbr/%%06d/rgb/%%06d.png, or .jpg (BOP's train_pbr convention)")
+    ap.add_argument("--voxel-size", type=float, default=voxel_cloud.DEFAULT_VOXEL_SIZE,
+                    help="side in metres of the world-fixed grid of the pointcloud_voxel_ply output")
+    ap.add_argument("--voxel-capacity", type=int, default=0,
+                    help=f"voxel records per frame the pass starts with (0: {voxel_cloud.DEFAULT_VOXEL_CAPACITY}; "
+                         "doubled while a frame overflows, and kept)")
     ap.add_argument("--prep-workers", type=int, default=-1,
                     help="processes preparing batches ahead (-1: two for runs of >= 20 batches)")
     a = ap.parse_args(argv)
@@ -742,7 +805,8 @@ def main(argv=None):
                        validate_pointcloud=a.validate_pointcloud, min_points=a.min_points, max_retries=a.max_retries,
                        prep_workers=a.prep_workers, depth16_counts_per_metre=a.depth16_counts_per_metre,
                        amodal_kinds=tuple(x.strip() for x in a.amodal_kinds.split(",") if x.strip()),
-                       jpeg_quality=a.jpeg_quality, jpeg_subsampling=a.jpeg_subsampling, bop_rgb=a.bop_rgb)
+                       jpeg_quality=a.jpeg_quality, jpeg_subsampling=a.jpeg_subsampling, bop_rgb=a.bop_rgb,
+                       voxel_size=a.voxel_size, voxel_capacity=a.voxel_capacity)
     print(json.dumps(summary))
 
 

@@ -23,6 +23,8 @@ from .labels import object_unit_transforms
 from .object_points import intrinsics_rows
 from .packing import PackedScene, light_constants, pack_scene
 from .scene.model import Scene
+from .voxel_cloud import DEFAULT_VOXEL_CAPACITY, DEFAULT_VOXEL_SIZE, RECORD_DTYPE
+from .voxel_cloud import OVERFLOW as VOXEL_OVERFLOW
 
 FRAME_DTYPE = np.dtype([("view", "<f4", 16), ("proj", "<f4", 16), ("xform_set", "<u4"), ("frame_id", "<u4"),
                         ("records_hint", "<u4"), ("bins_hint", "<u4")])
@@ -926,6 +928,110 @@ class Renderer:
         if views:
             return [memoryview(buf[int(off[i]):int(off[i + 1])]) for i in range(n)]
         return [buf[int(off[i]):int(off[i + 1])].tobytes() for i in range(n)]
+
+    # -- voxel-downsampled labelled point clouds ------------------------------------------
+    def voxel_cloud(self, n: int, *, voxel_size: float, capacity: int, points: int, rgb: int = 0, instance: int = 0,
+                    vx_xyz: int = 0, vx_rgb: int = 0, vx_label: int = 0, vx_count: int = 0, vx_total: int = 0,
+                    vx_dropped: int = 0, height: Optional[int] = None, width: Optional[int] = None,
+                    n_labels: Optional[int] = None, stream: int = 0) -> None:
+        """Enqueue the voxel clouds of ``n`` frames (csg_voxel_cloud; raw device
+        pointers, like :meth:`sample_points`): the finite points of ``points``
+        (n, H, W, 3) float32 (world space, as the "points" output) whose id in
+        ``instance`` (n, H, W) int32 lies in ``[-1, n_labels)`` (0: every id is
+        -1), binned on the world-fixed grid of ``voxel_size`` metres per (cell,
+        id), one record per voxel in the order of the voxels' first pixels:
+        ``vx_xyz`` (n, C, 3) float32 centroids, ``vx_rgb`` (n, C, 3) uint8 mean
+        colours of ``rgb`` (n, H, W, 3) uint8 (0: zeros), ``vx_label`` (n, C)
+        int32, ``vx_count`` (n, C) uint32, with C = ``capacity``; rows past a
+        frame's voxels hold NaN, 0, -1 and 0.  ``vx_total`` (n,) uint32 gets the
+        voxels of each frame, or 0xFFFFFFFF where they exceed ``capacity`` (that
+        frame's rows are then unspecified: repeat with a larger one);
+        ``vx_dropped`` (n,) uint32 the points beyond +-2^17 cells of the origin.
+        Sums are integers: the result is the same bytes on every run.
+        ``n_labels`` defaults to the scene's, ``height`` / ``width`` to the
+        renderer's.  On the stream of the render that wrote the sources no
+        synchronisation is needed in between."""
+        job = _lib.VoxelJob(self.width if width is None else int(width), self.height if height is None else int(height),
+                            self.n_labels if n_labels is None else int(n_labels), int(capacity), float(voxel_size), 0,
+                            points or None, rgb or None, instance or None, vx_xyz or None, vx_rgb or None,
+                            vx_label or None, vx_count or None, vx_total or None, vx_dropped or None)
+        self._check(self.lib.csg_voxel_cloud(self.ctx, C.byref(job), int(n), stream or None), "voxel_cloud")
+
+    def voxel_cloud_host(self, n: int, voxel_size: float = DEFAULT_VOXEL_SIZE, *, points: int, rgb: int = 0,
+                         instance: int = 0, capacity: int = 0, height: Optional[int] = None,
+                         width: Optional[int] = None, n_labels: Optional[int] = None, stream: int = 0):
+        """:meth:`voxel_cloud` of device images (pointers ``points``, ``rgb``,
+        ``instance``), delivered to the host: returns ``(frames, capacity,
+        dropped)`` where ``frames`` is a list of ``n`` structured arrays of
+        ``voxel_cloud.RECORD_DTYPE`` (fields ``xyz``, ``rgb``, ``label``,
+        ``count``), ``capacity`` the per-frame capacity that was enough and
+        ``dropped`` (n,) uint32 the dropped points.  The pass starts at
+        ``capacity`` (0: ``voxel_cloud.DEFAULT_VOXEL_CAPACITY``), never above
+        H * W, and is repeated with the capacity doubled, up to H * W, while
+        any frame reports 0xFFFFFFFF.  Only the totals and the records in use
+        cross PCIe: the pass runs on a stream of the wrapper's own, and the
+        frames' records are packed on the device and copied once.  ``stream``
+        (a raw handle, 0: none) is the stream still writing the sources, if
+        any: it is waited for first.  Synchronous."""
+        import torch
+        n = int(n)
+        H = self.height if height is None else int(height)
+        W = self.width if width is None else int(width)
+        cap = min(int(capacity) or DEFAULT_VOXEL_CAPACITY, H * W)
+        dev = torch.device("cuda", self.device)
+        if stream:
+            torch.cuda.ExternalStream(stream, device=dev).synchronize()
+        else:
+            self.synchronize()
+        st = self.span_stream()
+        with torch.cuda.stream(st):
+            d_tot = torch.empty((2, n), dtype=torch.int32, device=dev)
+            while True:
+                d_xyz = torch.empty((n, cap, 3), dtype=torch.float32, device=dev)
+                d_rgb = torch.empty((n, cap, 3), dtype=torch.uint8, device=dev)
+                d_lab = torch.empty((n, cap), dtype=torch.int32, device=dev)
+                d_cnt = torch.empty((n, cap), dtype=torch.int32, device=dev)
+                self.voxel_cloud(n, voxel_size=voxel_size, capacity=cap, points=points, rgb=rgb, instance=instance,
+                                 vx_xyz=d_xyz.data_ptr(), vx_rgb=d_rgb.data_ptr(), vx_label=d_lab.data_ptr(),
+                                 vx_count=d_cnt.data_ptr(), vx_total=d_tot[0].data_ptr(),
+                                 vx_dropped=d_tot[1].data_ptr(), height=H, width=W, n_labels=n_labels,
+                                 stream=st.cuda_stream)
+                tot = d_tot.cpu().numpy().view(np.uint32)   # waits for the stream
+                if not (tot[0] == VOXEL_OVERFLOW).any():
+                    break
+                if cap >= H * W:
+                    raise CsgError("voxel_cloud_host: a frame overflows a capacity of H * W")
+                cap = min(2 * cap, H * W)
+            totals = tot[0].astype(np.int64)
+            parts = []
+            for t in (d_xyz, d_rgb, d_lab, d_cnt):   # the records in use, and no more
+                parts.append(torch.cat([t[f, :int(totals[f])] for f in range(n)]).cpu().numpy() if n else None)
+            st.synchronize()
+        ends = np.cumsum(totals)
+        frames = []
+        for f in range(n):
+            lo, hi = int(ends[f] - totals[f]), int(ends[f])
+            rec = np.empty(hi - lo, RECORD_DTYPE)
+            rec["xyz"].view(np.uint32)[...] = parts[0][lo:hi].view(np.uint32)   # bit copies
+            rec["rgb"] = parts[1][lo:hi]
+            rec["label"] = parts[2][lo:hi]
+            rec["count"] = parts[3][lo:hi].view(np.uint32)
+            frames.append(rec)
+        return frames, cap, tot[1].copy()
+
+    def keep_points(self, keep: bool = True) -> None:
+        """Host-output batches (:meth:`render`, :meth:`render_files`) render
+        their world-space points into the context's device image even when
+        "points" is not among the host outputs and no file kind needs them
+        (csg_keep_points): :meth:`last_points` then finds them."""
+        self._check(self.lib.csg_keep_points(self.ctx, int(bool(keep))), "keep_points")
+
+    def last_points(self):
+        """``(device pointer, frames)`` of the last host-output batch's points image
+        (csg_last_points), valid until the next batch; (0, 0) when it made none."""
+        p, nf = C.c_void_p(), C.c_uint32()
+        self._check(self.lib.csg_last_points(self.ctx, C.byref(p), C.byref(nf)), "last_points")
+        return int(p.value or 0), int(nf.value)
 
     def keep_rgb(self, keep: bool = True) -> None:
         """Host-output batches (:meth:`render`, :meth:`render_files`) render

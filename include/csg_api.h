@@ -71,6 +71,8 @@
  *   csg_sample_object_points .. (new) N pixels of each object's visible mask with their
  *                               image indices, camera-frame points, colours and object
  *                               coordinates: the input of the point-based pose networks
+ *   csg_voxel_cloud ........... (new) the frame's world-space points voxel-downsampled on a
+ *                               world-fixed grid, one labelled record per (cell, object)
  *   csg_last_error / csg_destroy
  *
  * Threading: several contexts may share a device (each has its own stream
@@ -1035,6 +1037,101 @@ typedef struct {
   uint16_t* pt_coords;         /* [n][K][N][3] */
 } csg_point_job;
 int csg_sample_object_points(csg_ctx* ctx, const csg_point_job* job, uint32_t n_frames, void* stream);
+
+/* The world-space points of a host-output batch for csg_voxel_cloud, without
+ * their trip to the host: the exact counterparts of csg_keep_rgb and
+ * csg_last_rgb.  After csg_keep_points(ctx, 1) every later host-output batch
+ * renders its points into the context's own device image even when
+ * csg_outputs.points is NULL and no file kind asks for them, and copies nothing
+ * more than it did; 0 turns that off again.  csg_last_points returns the device
+ * image [n_frames][height][width][3] float32 of the context's last batch and its
+ * frame count (NULL and 0 when that batch rendered no points, or wrote them to
+ * the caller's device memory); it stays valid until the context's next batch.
+ * Neither call touches the GPU. */
+int csg_keep_points(csg_ctx* ctx, int32_t keep);
+int csg_last_points(csg_ctx* ctx, const float** points, uint32_t* n_frames);
+
+/* Voxel-downsampled labelled point clouds: the points of a frame binned on a
+ * grid of cubes of side s that is fixed in the world (clouds of different frames
+ * line up), one record per occupied (cell, id) pair -- the centroid, the mean
+ * colour, the id and the point count -- some 10^4..10^5 records of 23 bytes
+ * instead of one point per pixel.  Points of two ids are never merged.  A
+ * stand-alone pass on device memory only, like csg_sample_object_points: it
+ * needs no scene and no earlier render, and the frame size is the job's own.
+ * L = n_labels, C = capacity, s = voxel_size.
+ *
+ * Points and cells.
+ *   A pixel is a point iff its three coordinates are finite and -1 <= id < L
+ *   (id = -1 everywhere when `instance` is NULL; n_labels is then ignored).
+ *   r = fl32(1.0f / s), computed once on the host.
+ *   t_a = fl32(p_a * r) and c_a = floorf(t_a), per axis a.
+ *   A point whose t_a is not finite, or whose c_a lies outside [-2^17, 2^17) on
+ *   any axis, is dropped.  vx_dropped[f] counts these points.
+ *   This range lets 3 x 18 cell bits and the 9 bits of id + 1 fit one 63-bit
+ *   key.  All-ones is then free as the empty mark.
+ *
+ * Accumulation.
+ *   frac_a = fl32(t_a - c_a).  This subtraction is exact in float32, and frac_a
+ *   lies in [0, 1), except for t_a in (-0.5, 0): there c_a = -1 and t_a + 1 is
+ *   rounded (by at most 2^-25), to 1.0 for t_a above -2^-25.
+ *   q_a = min((uint32)(frac_a * 65536.0f), 65535), which lies in [0, 65535].
+ *   A voxel is the set of kept points of one frame that share (c_x, c_y, c_z, id).
+ *   Per voxel: n, the point count; S_a = sum of q_a, which needs 64 bits;
+ *   R_k = sum of colour_k (0 when `rgb` is NULL).
+ *
+ * Record of a voxel.
+ *   vx_count = n.  vx_label = id.
+ *   vx_rgb_k = (2 * R_k + n) / (2n), in integer arithmetic.
+ *   m_a = (2 * S_a + n) / (2n), in integer arithmetic.
+ *   vx_xyz_a = fl32(fl32((float)c_a + fl32(((float)m_a + 0.5f) * (1.0f / 65536.0f))) * s).
+ *   Every operation rounds once.
+ *
+ * Order.  Voxels are ordered ascending by the lowest row-major pixel index
+ * p = y * W + x among their points.  V is their count.
+ *
+ * Capacity.
+ *   V <= C: vx_total[f] = V.  Rows [0, V) are the records.  Rows [V, C) are
+ *   filled with 0x7FC00000 for xyz, 0 for rgb and count, and -1 for label.
+ *   V > C: vx_total[f] = 0xFFFFFFFF.  The frame's rows are unspecified, but
+ *   nothing is written outside them.  vx_dropped[f] is still exact.
+ *   Other frames of the call are unaffected.
+ *
+ * The result is a pure function of the inputs.  There are no float atomics, and
+ * nothing depends on scheduling or on the hash.  No coordinate, id or colour
+ * yields an address outside the arrays described.
+ *
+ * Enqueues on `stream` (NULL = the context's stream) and returns; behind the
+ * render that wrote the sources on the same stream it needs no synchronisation.
+ * csg_synchronize waits for it under the rule for the crops.  The pass has
+ * scratch of its own (per frame a table of T slots of 64 bytes, T the smallest
+ * power of two >= 2 * min(C, H * W), and H * W / 4 bytes), grown to the job and
+ * bounded at 256 MiB: a job that needs more runs as ranges of frames.  An event
+ * orders passes on different streams; it never touches the render's work buffers.
+ *
+ * CSG_ERR_INVALID, nothing enqueued or written: job NULL; n_frames == 0; width
+ * or height outside 1..8192; voxel_size not finite or not > 0; capacity == 0;
+ * with `instance`, n_labels == 0 or above CSG_SPAN_MAX_LABELS; points or
+ * vx_total NULL; a pointer that is not aligned to its element (4 bytes for
+ * points, instance, vx_xyz, vx_label, vx_count, vx_total and vx_dropped). */
+typedef struct {
+  uint32_t width, height;      /* of the frames: 1..8192 each */
+  uint32_t n_labels;           /* L: 1..CSG_SPAN_MAX_LABELS (ignored without `instance`) */
+  uint32_t capacity;           /* C >= 1: records per frame */
+  float    voxel_size;         /* s: finite, > 0 */
+  uint32_t pad;
+  /* sources, device memory */
+  const float*   points;       /* [n][H][W][3] as csg_outputs.points: world space, NaN where nothing is hit */
+  const uint8_t* rgb;          /* [n][H][W][3], or NULL: colours are 0 */
+  const int32_t* instance;     /* [n][H][W], or NULL: every id is -1 */
+  /* outputs, device memory; any may be NULL except vx_total */
+  float*    vx_xyz;            /* [n][C][3] */
+  uint8_t*  vx_rgb;            /* [n][C][3] */
+  int32_t*  vx_label;          /* [n][C] */
+  uint32_t* vx_count;          /* [n][C] */
+  uint32_t* vx_total;          /* [n] */
+  uint32_t* vx_dropped;        /* [n] */
+} csg_voxel_job;
+int csg_voxel_cloud(csg_ctx* ctx, const csg_voxel_job* job, uint32_t n_frames, void* stream);
 
 /* Stand-alone 3D->2D projection (host buffers): uv [n][2], vis [n] without a
  * depth test (1 = in front and inside the image, 0 otherwise). */
