@@ -35,6 +35,7 @@ EXPORTED = (
     "csg_keep_instance", "csg_last_instance", "csg_amodal_spans", "csg_sample_object_points",
     "csg_encode_span_masks", "csg_encode_jpeg", "csg_keep_rgb", "csg_last_rgb",
     "csg_voxel_cloud", "csg_keep_points", "csg_last_points",
+    "csg_sensor_depth", "csg_keep_depth", "csg_last_depth",
 )
 
 
@@ -177,6 +178,18 @@ class VoxelJob(C.Structure):
                 ("vx_count", C.c_void_p), ("vx_total", C.c_void_p), ("vx_dropped", C.c_void_p)]
 
 
+class SensorJob(C.Structure):
+    """csg_sensor_job (csg_sensor_depth)."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("radius", C.c_uint32), ("min_support", C.c_uint32),
+                ("tol", C.c_uint32), ("subpixel_bits", C.c_uint32), ("noise_k", C.c_uint32), ("seed", C.c_uint32),
+                ("flags", C.c_uint32), ("baseline", C.c_float), ("z_min", C.c_float), ("z_max", C.c_float),
+                ("depth", C.c_void_p), ("intrinsics", C.c_void_p), ("frame_keys", C.c_void_p),
+                ("sensor_depth", C.c_void_p), ("sensor_cause", C.c_void_p), ("sensor_count", C.c_void_p)]
+
+
+SENSOR_CLIP_BAND = 1   # CSG_SENSOR_CLIP_BAND
+
+
 class EncodeJob(C.Structure):
     """csg_encode_job (csg_encode_files)."""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n_frames", C.c_uint32), ("file_kinds", C.c_uint32),
@@ -264,6 +277,9 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     lib.csg_voxel_cloud.argtypes = [vp, C.POINTER(VoxelJob), u32, vp]
     lib.csg_keep_points.argtypes = [vp, i32]
     lib.csg_last_points.argtypes = [vp, C.POINTER(vp), C.POINTER(u32)]
+    lib.csg_sensor_depth.argtypes = [vp, C.POINTER(SensorJob), u32, vp]
+    lib.csg_keep_depth.argtypes = [vp, i32]
+    lib.csg_last_depth.argtypes = [vp, C.POINTER(vp), C.POINTER(u32)]
     lib.csg_keep_rgb.argtypes = [vp, i32]
     lib.csg_last_rgb.argtypes = [vp, C.POINTER(vp), C.POINTER(u32)]
     lib.csg_keep_instance.argtypes = [vp, i32]

@@ -162,6 +162,7 @@ void csg_destroy(csg_ctx* c) {
   (void)c->mp.wait_host(c);
   (void)c->jp.wait_host(c);
   (void)c->vx.wait_host(c);
+  (void)c->sn.wait_host(c);
   if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   for (auto& e : c->ring)
@@ -892,7 +893,7 @@ static int enqueue_batch(csg_ctx* c, const csg_frame* frames, uint32_t F, int fr
   } else {
     if (out->rgb || c->keep_rgb) { HIP_TRY(c, c->o_rgb.alloc(F * npx * 3)); b.rgb = c->o_rgb.p; }
     if (out->instance || c->keep_ids) { HIP_TRY(c, c->o_inst.alloc(F * npx)); b.inst = c->o_inst.p; }
-    if (out->depth) { HIP_TRY(c, c->o_depth.alloc(F * npx)); b.depth = c->o_depth.p; }
+    if (out->depth || c->keep_depth) { HIP_TRY(c, c->o_depth.alloc(F * npx)); b.depth = c->o_depth.p; }
     if (out->normals) { HIP_TRY(c, c->o_normals.alloc(F * npx * 3)); b.normals = c->o_normals.p; }
     if (out->points || c->keep_points) { HIP_TRY(c, c->o_points.alloc(F * npx * 3)); b.points = c->o_points.p; }
     if (out->inst_stats && out->n_labels) {
@@ -1118,6 +1119,8 @@ static int enqueue_batch(csg_ctx* c, const csg_frame* frames, uint32_t F, int fr
   c->kept_rgb_frames = c->kept_rgb ? F : 0;
   c->kept_points = dev ? nullptr : b.points;
   c->kept_points_frames = c->kept_points ? F : 0;
+  c->kept_depth = dev ? nullptr : b.depth;
+  c->kept_depth_frames = c->kept_depth ? F : 0;
   if (!dev) {   // the batch's stream orders everything after it (and csg_synchronize) behind the copies
     if (narrow) {   // ... and behind the widening of every chain's ids
       auto* l = new std::shared_ptr<WidenLatch>(latch);
@@ -1781,6 +1784,20 @@ int csg_last_points(csg_ctx* c, const float** points, uint32_t* n_frames) {
   if (!points || !n_frames) return c->fail(CSG_ERR_INVALID, "last_points: null argument");
   *points = c->kept_points;
   *n_frames = c->kept_points_frames;
+  return CSG_OK;
+}
+
+int csg_keep_depth(csg_ctx* c, int32_t keep) {
+  if (!c) return CSG_ERR_INVALID;
+  c->keep_depth = keep != 0;
+  return CSG_OK;
+}
+
+int csg_last_depth(csg_ctx* c, const float** depth, uint32_t* n_frames) {
+  if (!c) return CSG_ERR_INVALID;
+  if (!depth || !n_frames) return c->fail(CSG_ERR_INVALID, "last_depth: null argument");
+  *depth = c->kept_depth;
+  *n_frames = c->kept_depth_frames;
   return CSG_OK;
 }
 

@@ -15,6 +15,7 @@
 #include "csg_jpeg.h"
 #include "csg_kernels.h"
 #include "csg_mask_png.h"
+#include "csg_sensor.h"
 #include "csg_voxels.h"
 
 namespace csg {
@@ -332,6 +333,15 @@ struct csg_ctx {
   DevBuf<uint32_t> vx_words;
   DevBuf<csg::VxFrame> vx_frames;
   csg::PassOrder vx;
+  // Stereo-camera depth (csg_sensor_depth): the pass's own scratch -- of one range of frames the state
+  // image (an int32 per pixel) and the causes' counters -- grown to the job, under an order of its own.
+  DevBuf<int32_t> sn_state;
+  DevBuf<uint32_t> sn_counts;
+  csg::PassOrder sn;
+  // csg_keep_depth / csg_last_depth: host-output batches render their depth into o_depth whether or not anything copies it
+  bool keep_depth = false;
+  const float* kept_depth = nullptr;
+  uint32_t kept_depth_frames = 0;
   // csg_keep_points / csg_last_points: host-output batches render their points into o_points whether or not anything copies them
   bool keep_points = false;
   const float* kept_points = nullptr;

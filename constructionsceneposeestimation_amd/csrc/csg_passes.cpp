@@ -1,7 +1,7 @@
 // The stand-alone passes of libcsg.so (see include/csg_api.h): object crops, mask spans, mask PNGs, object
-// points, voxel clouds and the three amodal passes.  Each validates its job on the host, orders itself
-// behind the last pass that used its scratch (PassOrder, csg_ctx.h), grows that scratch and enqueues its
-// kernels on the caller's stream.  None of them touches a render's work buffers.
+// points, voxel clouds, stereo-camera depth and the three amodal passes.  Each validates its job on the
+// host, orders itself behind the last pass that used its scratch (PassOrder, csg_ctx.h), grows that scratch
+// and enqueues its kernels on the caller's stream.  None of them touches a render's work buffers.
 #include <stdlib.h>
 #include <string.h>
 
@@ -448,6 +448,91 @@ int csg_voxel_cloud(csg_ctx* c, const csg_voxel_job* job, uint32_t n_frames, voi
   }
   HIP_TRY(c, hipGetLastError());
   return c->vx.end(c, st);
+}
+
+// Stereo-camera depth: a stand-alone pass over device arrays (no scene state, no work buffers); validates
+// the job, grows the pass's own scratch and enqueues the kernels.  The scratch (an int32 of state per pixel
+// and eight counters per frame) is bounded at kSensorScratchCap bytes: a job that needs more runs as ranges
+// of frames on the stream, each writing and reading the same scratch.
+int csg_sensor_depth(csg_ctx* c, const csg_sensor_job* job, uint32_t n_frames, void* stream) {
+  constexpr size_t kSensorScratchCap = 256u << 20;
+  if (!c) return CSG_ERR_INVALID;
+  if (!job) return c->fail(CSG_ERR_INVALID, "sensor_depth: null job");
+  if (n_frames == 0) return c->fail(CSG_ERR_INVALID, "sensor_depth: no frames");
+  CSG_TRY(check_frame_dims(c, "sensor_depth", job->width, job->height));
+  if (job->radius > 4) return c->fail(CSG_ERR_INVALID, "sensor_depth: radius %u outside 0..4", job->radius);
+  const uint32_t window = (2u * job->radius + 1u) * (2u * job->radius + 1u);
+  if (job->min_support < 1 || job->min_support > window)
+    return c->fail(CSG_ERR_INVALID, "sensor_depth: min_support %u outside 1..%u", job->min_support, window);
+  if (job->subpixel_bits > 8)
+    return c->fail(CSG_ERR_INVALID, "sensor_depth: subpixel_bits %u outside 0..8", job->subpixel_bits);
+  if (job->noise_k > (1u << 20)) return c->fail(CSG_ERR_INVALID, "sensor_depth: noise_k %u above 2^20", job->noise_k);
+  if (job->flags & ~CSG_SENSOR_CLIP_BAND) return c->fail(CSG_ERR_INVALID, "sensor_depth: unknown flags 0x%x", job->flags);
+  if (!std::isfinite(job->baseline) || job->baseline == 0.0f)
+    return c->fail(CSG_ERR_INVALID, "sensor_depth: baseline %g is not a finite value other than 0", (double)job->baseline);
+  if (!std::isfinite(job->z_min) || !std::isfinite(job->z_max) || !(job->z_min > 0.0f) || !(job->z_min <= job->z_max))
+    return c->fail(CSG_ERR_INVALID, "sensor_depth: z_min %g, z_max %g: not finite with 0 < z_min <= z_max",
+                   (double)job->z_min, (double)job->z_max);
+  if (!job->depth || !job->intrinsics) return c->fail(CSG_ERR_INVALID, "sensor_depth: depth and intrinsics must not be NULL");
+  if (!job->sensor_depth && !job->sensor_cause && !job->sensor_count)
+    return c->fail(CSG_ERR_INVALID, "sensor_depth: no output");
+  if (((uintptr_t)job->depth | (uintptr_t)job->intrinsics | (uintptr_t)job->frame_keys | (uintptr_t)job->sensor_depth |
+       (uintptr_t)job->sensor_count) & 3u)
+    return c->fail(CSG_ERR_INVALID, "sensor_depth: every pointer but sensor_cause must be 4-byte aligned");
+  const size_t P = (size_t)job->width * job->height;
+  {   // no output may overlap a source: k_sn_match writes a tile while other tiles' rows are still read
+    const struct { const void* p; size_t bytes; } src[] = {{job->depth, (size_t)n_frames * P * 4u},
+                                                           {job->intrinsics, (size_t)n_frames * 16u},
+                                                           {job->frame_keys, (size_t)n_frames * 4u}},
+        dst[] = {{job->sensor_depth, (size_t)n_frames * P * 4u}, {job->sensor_cause, (size_t)n_frames * P},
+                 {job->sensor_count, (size_t)n_frames * kSnCauses * 4u}};
+    for (const auto& s : src)
+      for (const auto& d : dst) {
+        const uintptr_t s0 = (uintptr_t)s.p, d0 = (uintptr_t)d.p;
+        if (s.p && d.p && s0 < d0 + d.bytes && d0 < s0 + s.bytes)
+          return c->fail(CSG_ERR_INVALID, "sensor_depth: an output overlaps a source");
+      }
+  }
+  hipStream_t st;
+  CSG_TRY(pass_stream(c, stream, &st));
+  SensorArgs a{};
+  a.W = job->width;
+  a.H = job->height;
+  a.r = job->radius;
+  a.min_support = job->min_support;
+  a.tol = job->tol;
+  a.sh = 8u - job->subpixel_bits;
+  a.noise_k = job->noise_k;
+  a.seed = job->seed;
+  a.clip_band = job->flags & CSG_SENSOR_CLIP_BAND;
+  a.abs_b = std::fabs(job->baseline);
+  a.right = job->baseline > 0.0f;
+  a.z_min = job->z_min;
+  a.z_max = job->z_max;
+  a.depth = job->depth;
+  a.intrinsics = job->intrinsics;
+  a.frame_keys = job->frame_keys;
+  a.sensor_depth = job->sensor_depth;
+  a.sensor_cause = job->sensor_cause;
+  a.sensor_count = job->sensor_count;
+  const size_t per_frame = P * sizeof(int32_t) + kSnCountStride * sizeof(uint32_t);
+  size_t cap = kSensorScratchCap;
+  if (const char* e = getenv("CSG_SENSOR_SCRATCH_CAP")) cap = (size_t)strtoull(e, nullptr, 10);   // (tests: bytes)
+  const uint32_t range = (uint32_t)std::min<size_t>(std::min<uint32_t>(n_frames, 65535u),   // grid y / z limit
+                                                    std::max<size_t>(1, cap / per_frame));
+  const size_t n_state = (size_t)range * P, n_counts = (size_t)range * kSnCountStride;
+  CSG_TRY(c->sn.begin(c, st, c->sn_state.n < n_state || c->sn_counts.n < n_counts));
+  HIP_TRY(c, c->sn_state.alloc(n_state));
+  HIP_TRY(c, c->sn_counts.alloc(n_counts));
+  a.state = c->sn_state.p;
+  a.counts = c->sn_counts.p;
+  for (uint32_t f0 = 0; f0 < n_frames; f0 += range) {
+    a.first = f0;
+    a.n = std::min(range, n_frames - f0);
+    launch_sensor(a, st);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return c->sn.end(c, st);
 }
 
 // Amodal crop masks: reads the scene tables (synced here as a render syncs them) and the caller's

@@ -35,6 +35,12 @@ same files:
                                     (-1 background) and point count, 23 B per record, voxel_cloud.read_ply;
                                     + pointcloud/objects.json as obj_coords' and the grid; no reference
                                     counterpart)
+  depth/sensor16_%06d.png          (optional "depth_sensor16_png": the depth a stereo depth camera registered to
+                                    the colour camera would return -- half-occlusion holes, window erosion,
+                                    quantised and noisy disparity (depth_sensor.StereoModel, made on the GPU
+                                    behind the render) -- as depth16_png's 16-bit PNG at the same scale, 0 = no
+                                    return; + depth/sensor.json: the model, the job's integers, the seed and the
+                                    run's pixels per cause; no reference counterpart)
   depth/depth16_%06d.png           (optional "depth16_png": 16-bit grey PNG at a fixed number of counts
                                     per metre, writers.depth_to_u16) + depth/depth16.json (the scale;
                                     0 = no hit)
@@ -65,6 +71,7 @@ Resume: frames whose label file already exists are skipped.
 from __future__ import annotations
 
 import argparse
+import dataclasses
 import json
 import os
 import sys
@@ -78,10 +85,12 @@ import numpy as np
 
 from . import bop
 from . import camera_math as cm
+from . import depth_sensor
 from . import masks
 from . import prep_pool
 from . import voxel_cloud
 from .crops import DYNAMIC_KINDS, eligible_labels
+from .object_points import intrinsics_rows
 from .labels import OBJECT_LISTS, in_frustum, label_record, object_box, object_poses
 from .quality_log import QualityLog
 from .renderer import Renderer, make_frames, output_spec, scene_labels
@@ -109,7 +118,8 @@ def _log_done(log: QualityLog, fut, log_args: dict, points: bool) -> None:
 
 
 OUTPUTS = ("rgb", "mask", "depth_csv", "depth_png", "depth_npy", "pointcloud", "normals", "obj_coords",
-           "pointcloud_ply", "depth16_png", "mask_rle", "amodal_rle", "rgb_jpg", "pointcloud_voxel_ply")
+           "pointcloud_ply", "depth16_png", "mask_rle", "amodal_rle", "rgb_jpg", "pointcloud_voxel_ply",
+           "depth_sensor16_png")
 # What the reference writes for every frame (GDP:1668-1771, 2055-2072): RGB PNG, depth CSV and
 # JET depth PNG, point-cloud TXT, instance mask .npy; the label JSON is always written (it is the
 # resume marker).
@@ -127,7 +137,8 @@ FILE_OF_OUTPUT = (("rgb", "rgb_png"), ("depth_csv", "depth_csv"), ("depth_png", 
 _PATHS = {"rgb": ("rgb", "rgb_{:06d}.png"), "depth_csv": ("depth", "depth_{:06d}.csv"),
           "depth_png": ("depth", "depth_{:06d}.png"), "pointcloud": ("pointcloud", "pointcloud_{:06d}.txt"),
           "pointcloud_ply": ("pointcloud", "pointcloud_{:06d}.ply"), "depth16_png": ("depth", "depth16_{:06d}.png"),
-          "rgb_jpg": ("rgb", "rgb_{:06d}.jpg"), "pointcloud_voxel_ply": ("pointcloud", "voxels_{:06d}.ply")}
+          "rgb_jpg": ("rgb", "rgb_{:06d}.jpg"), "pointcloud_voxel_ply": ("pointcloud", "voxels_{:06d}.ply"),
+          "depth_sensor16_png": ("depth", "sensor16_{:06d}.png")}
 _ENCODED_KIND = {"pointcloud": "encoded_pointcloud", "pointcloud_ply": "encoded_ply"}   # writer_pool.write_frame
 
 
@@ -158,6 +169,24 @@ def check_bop(outs) -> None:
         raise ValueError(f"output bop writes its own per-object masks: it does not go with {clash}")
     if BOP_OUTPUT in outs and "pointcloud_voxel_ply" in outs:
         raise ValueError("output bop has no place for voxel clouds: it does not go with pointcloud_voxel_ply")
+    if BOP_OUTPUT in outs and "depth_sensor16_png" in outs:
+        raise ValueError("output bop has no place for sensor depth: it does not go with depth_sensor16_png")
+
+
+def sensor_model(preset: Optional[str] = None, baseline: Optional[float] = None,
+                 noise_px: Optional[float] = None) -> "depth_sensor.StereoModel":
+    """The stereo model of the depth_sensor16_png output: a preset of
+    depth_sensor.PRESETS (default "site") with its baseline and disparity noise
+    replaced where given."""
+    name = preset or "site"
+    if name not in depth_sensor.PRESETS:
+        raise ValueError(f"depth sensor preset {name!r}: one of {sorted(depth_sensor.PRESETS)}")
+    kw = {}
+    if baseline is not None:
+        kw["baseline"] = float(baseline)
+    if noise_px is not None:
+        kw["noise_sigma_px"] = float(noise_px)
+    return dataclasses.replace(depth_sensor.PRESETS[name], **kw)
 
 
 def render_outputs(outs: set, gpu_files: bool, host_depth: bool, occlusion: bool) -> list:
@@ -186,7 +215,9 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
              min_points: int = 100, max_retries: int = 5, prep_workers: int = -1,
              depth16_counts_per_metre: float = 250.0, amodal_kinds: Optional[Sequence[str]] = None,
              jpeg_quality: int = 95, jpeg_subsampling: str = "420", bop_rgb: str = "png",
-             voxel_size: float = voxel_cloud.DEFAULT_VOXEL_SIZE, voxel_capacity: int = 0) -> dict:
+             voxel_size: float = voxel_cloud.DEFAULT_VOXEL_SIZE, voxel_capacity: int = 0,
+             depth_sensor_preset: Optional[str] = None, sensor_baseline: Optional[float] = None,
+             sensor_noise_px: Optional[float] = None, sensor_seed: int = 0) -> dict:
     """Render ``frames`` on one GPU and write them (``outputs``, default the
     reference's set; ``depth`` / ``depth_csv`` / ``pointcloud`` / ``normals``
     add the depth .npy, the depth .npy + CSV, the point cloud, the normals).
@@ -250,6 +281,19 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
     they cross PCIe.  ``voxel_capacity``: records per frame the pass starts with
     (0: voxel_cloud.DEFAULT_VOXEL_CAPACITY); a renderer keeps what its retries
     settled on.  Not with "bop".
+    ``outputs`` with "depth_sensor16_png": ``depth/sensor16_%06d.png``, the depth
+    a stereo depth camera would return for the frame (depth_sensor.py): the
+    model is ``depth_sensor_preset`` of depth_sensor.PRESETS (default "site")
+    with ``sensor_baseline`` metres and ``sensor_noise_px`` pixels of disparity
+    noise where given.  The batch keeps its depth on the device
+    (csg_keep_depth), the pass runs there behind the render (csg_sensor_depth)
+    and its image goes through the 16-bit depth PNG encoder
+    (csg_encode_files) at ``depth16_counts_per_metre``.  A frame's noise is a
+    function of ``sensor_seed`` and its frame id, not of batching or sharding.
+    ``depth/sensor.json`` holds the model, the job's integers, the seed, the
+    scale (``counts_per_metre``), ``invalid`` (the sample that means "no
+    return", 0, as in depth/depth16.json) and the run's pixels per cause.
+    Not with "bop".
     ``prep_workers``: processes that prepare batches ahead (epoch layouts,
     object poses, cameras; prep_pool.py), so that numpy work does not hold
     this process's GIL; -1 = two for runs of at least 20 batches, else none."""
@@ -289,6 +333,13 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
     want_vox = "pointcloud_voxel_ply" in outs
     if want_vox and not (np.isfinite(float(voxel_size)) and float(voxel_size) > 0 and int(voxel_capacity) >= 0):
         raise ValueError(f"voxel_size {voxel_size!r}: a finite number > 0; voxel_capacity {voxel_capacity!r}: >= 0")
+    want_sens = "depth_sensor16_png" in outs
+    if want_sens:
+        s16 = float(depth16_counts_per_metre)
+        if not (np.isfinite(s16) and s16 > 0):
+            raise ValueError(f"depth16_counts_per_metre {depth16_counts_per_metre!r}: a finite number > 0")
+        sens_model = sensor_model(depth_sensor_preset, sensor_baseline, sensor_noise_px)
+        sens_job = dict(sens_model.to_job_fields(), seed=int(sensor_seed) & 0xFFFFFFFF)
     if "obj_coords" in outs or want_vox:
         objs = []
         for o in wl.scene.objects:
@@ -374,6 +425,12 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
             x.keep_points(True)
             x.keep_instance(True)
             x.keep_rgb(True)
+    if want_sens:   # ... and their depth for the sensor pass
+        for x in rends:
+            x.keep_depth(True)
+    sens_cap = {}   # renderer -> the bytes its last batch's sensor PNGs took
+    sens_buf = {}   # renderer -> its device arrays for the pass (intrinsics, keys, sensor depth, counts)
+    sens_counts = np.zeros(7, np.int64)   # the run's pixels per cause
     vox_cap = {}    # renderer -> the voxel capacity its last batch needed (voxel_cloud_host grows it)
     vox_stats = {"frames": 0, "voxels": 0, "voxels_max": 0}
     jpg_cap = {}    # renderer -> the bytes its last batch's JPEG files took (jpegs_host repeats a pass that overflows)
@@ -512,6 +569,37 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
             voxr[0] = [(voxel_cloud.ply_bytes(x), len(x)) for x in recs]
             return sum(x.nbytes for x in recs)
 
+        sensr = [None]  # the batch's (sensor16_%06d.png file, pixels per cause) per frame, with "depth_sensor16_png"
+
+        def sensor_of_batch() -> int:
+            import torch
+            dep, nf = r.last_depth()
+            if not dep or nf != len(fb):
+                raise RuntimeError(f"depth_sensor16_png: the batch kept {nf} depth images, {len(fb)} frames rendered")
+            n, dev = len(fb), torch.device("cuda", r.device)
+            if id(r) not in sens_buf:   # the renderer's device arrays, made once for a full batch
+                sens_buf[id(r)] = (torch.empty((batch, 4), dtype=torch.float32, device=dev),
+                                   torch.empty((batch,), dtype=torch.int32, device=dev),
+                                   torch.empty((batch, wl.height, wl.width), dtype=torch.float32, device=dev),
+                                   torch.empty((batch, 7), dtype=torch.int32, device=dev))
+            d_in, d_keys, d_out, d_cnt = sens_buf[id(r)]
+            d_in[:n].copy_(torch.from_numpy(intrinsics_rows(make_frames(*cur[0], sets, fb))))
+            d_keys[:n].copy_(torch.from_numpy(np.asarray(fb, np.uint32).view(np.int32).copy()))   # the frame ids
+            torch.cuda.current_stream(dev).synchronize()   # the uploads, before the context's stream reads them
+            # on the context's stream, behind the render and in front of the encoder, which waits for both
+            r.sensor_depth(n, depth=dep, intrinsics=d_in.data_ptr(), model=sens_job, frame_keys=d_keys.data_ptr(),
+                           sensor_depth=d_out.data_ptr(), sensor_count=d_cnt.data_ptr())
+            buf = np.empty(sens_cap.get(id(r), n * (2 * wl.width * wl.height + 4096)), np.uint8)
+            offsets, need = r.encode_files(n, wl.width, wl.height, ("depth16_png",), buf, depth=d_out.data_ptr(),
+                                           depth16_counts_per_metre=depth16_counts_per_metre)
+            if offsets is None:   # the files did not fit: a larger buffer, no second pass
+                buf = np.empty(need + need // 4, np.uint8)
+                offsets = r.copy_files(buf, n)
+            sens_cap[id(r)] = max(sens_cap.get(id(r), 0), need + need // 4)
+            cnt = d_cnt[:n].cpu().numpy().view(np.uint32)   # (the encoder has waited for the pass)
+            sensr[0] = [(buf[int(offsets[k]):int(offsets[k + 1])].tobytes(), cnt[k].astype(np.int64)) for k in range(n)]
+            return int(offsets[-1]) + cnt.nbytes
+
         cur = [None]   # the cameras of the attempt being rendered
 
         def run(views, projs):
@@ -527,12 +615,12 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                 arrays["file_offsets"] = offsets
                 d2h.append(int(offsets[-1]) + wire_bytes(out) + (spans_of_batch() if want_rle else 0)
                            + (bop_of_batch() if want_bop else 0) + (jpgs_of_batch() if want_jpg else 0)
-                           + (voxels_of_batch() if want_vox else 0))
+                           + (voxels_of_batch() if want_vox else 0) + (sensor_of_batch() if want_sens else 0))
             else:
                 out = r.render(fr, want=want, out={k: v[:len(fb)] for k, v in arrays.items()})
                 d2h.append(wire_bytes(out) + (spans_of_batch() if want_rle else 0)
                            + (jpgs_of_batch() if want_jpg and gpu_files else 0)
-                           + (voxels_of_batch() if want_vox else 0))
+                           + (voxels_of_batch() if want_vox else 0) + (sensor_of_batch() if want_sens else 0))
             return out
 
         out = run(views, projs)
@@ -558,7 +646,7 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                 out = run(*wl.frame_params(fb, attempts))
                 check = again
         te = time.time()
-        return fb, slot, out, (te - tr, tp - tw, tr - tp), attempts, checks, failed, (rle[0], arle[0], bopr[0], jpgr[0], voxr[0])
+        return fb, slot, out, (te - tr, tp - tw, tr - tp), attempts, checks, failed, (rle[0], arle[0], bopr[0], jpgr[0], voxr[0], sensr[0])
 
     ahead = ThreadPoolExecutor(max_workers=n_rend)
     prep = ThreadPoolExecutor(max_workers=max(1, n_prep))
@@ -574,7 +662,7 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
         queued = [ahead.submit(render_batch, b) for b in range(min(n_rend, len(starts)))]
         for b in range(len(starts)):
             tq = time.time()
-            fb, slot, out, (dt, dwait, dprep), attempts, checks, failed, (rle, arle, bopr, jpgr, voxr) = queued.pop(0).result()
+            fb, slot, out, (dt, dwait, dprep), attempts, checks, failed, (rle, arle, bopr, jpgr, voxr, sensr) = queued.pop(0).result()
             t_main_wait += time.time() - tq
             t_render += dt
             t_slot_wait += dwait
@@ -632,6 +720,10 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                     vox_stats["frames"] += 1
                     vox_stats["voxels"] += voxr[k][1]
                     vox_stats["voxels_max"] = max(vox_stats["voxels_max"], voxr[k][1])
+                if want_sens:   # made on the GPU behind the batch
+                    files.append((file_path(out_dir, "depth_sensor16_png", f), "call",
+                                  (partial(bop.write_bytes, data=sensr[k][0]),)))
+                    sens_counts += sensr[k][1]
                 if want_bop:   # the two images from the GPU encoders, the mask files, then the fragment
                     if f // bop.FRAMES_PER_SCENE not in bop_scenes and sink == "disk":
                         bop.make_dirs(out_dir, f // bop.FRAMES_PER_SCENE)
@@ -732,6 +824,14 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                              "sink": sink, "prep_workers": n_prep,
                              "writer_busy": round(pool.task_s / (wall * n_writers), 3) if wall > 0 else None,
                              "outputs": sorted(outs)}
+    if want_sens:
+        meta = {"model": sens_model.as_dict(), "job": sens_job, "seed": sens_job["seed"], "frame_key": "frame id",
+                "counts_per_metre": float(depth16_counts_per_metre), "invalid": 0,
+                "cause_names": list(depth_sensor.cause_names),
+                "cause_totals": {name: int(sens_counts[c]) for c, name in enumerate(depth_sensor.cause_names)}}
+        with open(os.path.join(out_dir, "depth", "sensor.json"), "w") as fh:
+            json.dump(meta, fh, indent=2)
+        summary["depth_sensor"] = meta
     if want_vox:
         summary["voxel_cloud"] = {"voxel_size": float(np.float32(voxel_size)),
                                   "capacity": max(vox_cap.values()) if vox_cap else int(voxel_capacity),
@@ -789,6 +889,13 @@ def main(argv=None):
     ap.add_argument("--voxel-capacity", type=int, default=0,
                     help=f"voxel records per frame the pass starts with (0: {voxel_cloud.DEFAULT_VOXEL_CAPACITY}; "
                          "doubled while a frame overflows, and kept)")
+    ap.add_argument("--depth-sensor", default=None, metavar="PRESET", choices=sorted(depth_sensor.PRESETS),
+                    help="stereo model of the depth_sensor16_png output (depth_sensor.PRESETS; default site)")
+    ap.add_argument("--sensor-baseline", type=float, default=None,
+                    help="baseline in metres of the stereo model (signed: the second camera's x), instead of the preset's")
+    ap.add_argument("--sensor-noise-px", type=float, default=None,
+                    help="standard deviation of the disparity noise in pixels, instead of the preset's")
+    ap.add_argument("--sensor-seed", type=int, default=0, help="seed of the sensor noise (a frame's key is its frame id)")
     ap.add_argument("--prep-workers", type=int, default=-1,
                     help="processes preparing batches ahead (-1: two for runs of >= 20 batches)")
     a = ap.parse_args(argv)
@@ -806,7 +913,8 @@ def main(argv=None):
                        prep_workers=a.prep_workers, depth16_counts_per_metre=a.depth16_counts_per_metre,
                        amodal_kinds=tuple(x.strip() for x in a.amodal_kinds.split(",") if x.strip()),
                        jpeg_quality=a.jpeg_quality, jpeg_subsampling=a.jpeg_subsampling, bop_rgb=a.bop_rgb,
-                       voxel_size=a.voxel_size, voxel_capacity=a.voxel_capacity)
+                       voxel_size=a.voxel_size, voxel_capacity=a.voxel_capacity, depth_sensor_preset=a.depth_sensor,
+                       sensor_baseline=a.sensor_baseline, sensor_noise_px=a.sensor_noise_px, sensor_seed=a.sensor_seed)
     print(json.dumps(summary))
 
 

@@ -1033,6 +1033,88 @@ class Renderer:
         self._check(self.lib.csg_last_points(self.ctx, C.byref(p), C.byref(nf)), "last_points")
         return int(p.value or 0), int(nf.value)
 
+    # -- simulated stereo-camera depth ----------------------------------------------------
+    def sensor_depth(self, n: int, *, depth: int, intrinsics: int, model, seed: int = 0, frame_keys: int = 0,
+                     sensor_depth: int = 0, sensor_cause: int = 0, sensor_count: int = 0,
+                     height: Optional[int] = None, width: Optional[int] = None, stream: int = 0) -> None:
+        """Enqueue the stereo-camera depth of ``n`` frames (csg_sensor_depth; raw
+        device pointers, like :meth:`voxel_cloud`): ``depth`` (n, H, W) float32
+        as the "depth" output and ``intrinsics`` (n, 4) float32 ``fx, fy, cx,
+        cy`` (only fx is read) under ``model``, a :class:`depth_sensor.StereoModel`
+        or a dict of the job's integers as ``StereoModel.to_job_fields`` gives
+        them.  ``sensor_depth`` (n, H, W) float32 gets the depth the camera
+        returns, 0.0 where it returns none; ``sensor_cause`` (n, H, W) uint8
+        why (``depth_sensor.cause_names``); ``sensor_count`` (n, 7) uint32 the
+        pixels of each cause.  Any output may be 0, not all; ``sensor_depth``
+        must not overlap ``depth``.  The noise of a frame is a function of
+        ``seed`` and its key: ``frame_keys`` (n,) uint32, or 0 for the frame's
+        place in the batch.  ``height`` / ``width`` default to the renderer's.
+        On the stream of the render that wrote the depth no synchronisation is
+        needed in between."""
+        f = model if isinstance(model, dict) else model.to_job_fields()
+        job = _lib.SensorJob(self.width if width is None else int(width), self.height if height is None else int(height),
+                             int(f["radius"]), int(f["min_support"]), int(f["tol"]), int(f["subpixel_bits"]),
+                             int(f["noise_k"]), int(f.get("seed", seed)) & 0xFFFFFFFF, int(f["flags"]),
+                             float(f["baseline"]), float(f["z_min"]), float(f["z_max"]), depth or None,
+                             intrinsics or None, frame_keys or None, sensor_depth or None, sensor_cause or None,
+                             sensor_count or None)
+        self._check(self.lib.csg_sensor_depth(self.ctx, C.byref(job), int(n), stream or None), "sensor_depth")
+
+    def sensor_depth_host(self, n: int, model, *, depth: int, intrinsics, frame_keys=None, seed: int = 0,
+                          want=("depth", "cause", "count"), height: Optional[int] = None,
+                          width: Optional[int] = None, stream: int = 0) -> dict:
+        """:meth:`sensor_depth` of a device depth image (pointer ``depth``),
+        delivered to the host: a dict with ``"depth"`` (n, H, W) float32,
+        ``"cause"`` (n, H, W) uint8 and ``"count"`` (n, 7) uint32, as far as
+        ``want`` names them.  ``intrinsics`` (n, 4) and ``frame_keys`` (n,) are
+        host arrays.  The pass runs on a stream of the wrapper's own;
+        ``stream`` (a raw handle, 0: none) is the stream still writing the
+        depth, if any: it is waited for first.  Synchronous."""
+        import torch
+        n = int(n)
+        H = self.height if height is None else int(height)
+        W = self.width if width is None else int(width)
+        bad = [k for k in want if k not in ("depth", "cause", "count")]
+        if bad or not want:
+            raise CsgError(f"sensor_depth_host: want {tuple(want)!r}: some of depth, cause, count")
+        dev = torch.device("cuda", self.device)
+        if stream:
+            torch.cuda.ExternalStream(stream, device=dev).synchronize()
+        else:
+            self.synchronize()
+        st = self.span_stream()
+        with torch.cuda.stream(st):
+            d_in = torch.from_numpy(np.ascontiguousarray(intrinsics, np.float32).reshape(n, 4)).to(dev)
+            d_keys = None if frame_keys is None else \
+                torch.from_numpy(np.ascontiguousarray(frame_keys, np.uint32).reshape(n).view(np.int32)).to(dev)
+            d_out = {"depth": torch.empty((n, H, W), dtype=torch.float32, device=dev) if "depth" in want else None,
+                     "cause": torch.empty((n, H, W), dtype=torch.uint8, device=dev) if "cause" in want else None,
+                     "count": torch.empty((n, 7), dtype=torch.int32, device=dev) if "count" in want else None}
+            ptr = {k: (t.data_ptr() if t is not None else 0) for k, t in d_out.items()}
+            self.sensor_depth(n, depth=depth, intrinsics=d_in.data_ptr(), model=model, seed=seed,
+                              frame_keys=d_keys.data_ptr() if d_keys is not None else 0, sensor_depth=ptr["depth"],
+                              sensor_cause=ptr["cause"], sensor_count=ptr["count"], height=H, width=W,
+                              stream=st.cuda_stream)
+            out = {k: t.cpu().numpy() for k, t in d_out.items() if t is not None}
+            st.synchronize()
+        if "count" in out:
+            out["count"] = out["count"].view(np.uint32)
+        return out
+
+    def keep_depth(self, keep: bool = True) -> None:
+        """Host-output batches (:meth:`render`, :meth:`render_files`) render
+        their depth into the context's device image even when "depth" is not
+        among the host outputs and nothing else needs it (csg_keep_depth):
+        :meth:`last_depth` then finds it."""
+        self._check(self.lib.csg_keep_depth(self.ctx, int(bool(keep))), "keep_depth")
+
+    def last_depth(self):
+        """``(device pointer, frames)`` of the last host-output batch's depth image
+        (csg_last_depth), valid until the next batch; (0, 0) when it made none."""
+        p, nf = C.c_void_p(), C.c_uint32()
+        self._check(self.lib.csg_last_depth(self.ctx, C.byref(p), C.byref(nf)), "last_depth")
+        return int(p.value or 0), int(nf.value)
+
     def keep_rgb(self, keep: bool = True) -> None:
         """Host-output batches (:meth:`render`, :meth:`render_files`) render
         their RGB into the context's device image even when "rgb" is not among

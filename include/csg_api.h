@@ -73,6 +73,9 @@
  *                               coordinates: the input of the point-based pose networks
  *   csg_voxel_cloud ........... (new) the frame's world-space points voxel-downsampled on a
  *                               world-fixed grid, one labelled record per (cell, object)
+ *   csg_sensor_depth .......... (new) a depth image as a stereo depth camera would return
+ *                               it: half-occlusion holes, window erosion, quantised and noisy
+ *                               disparity, with the cause of every missing value
  *   csg_last_error / csg_destroy
  *
  * Threading: several contexts may share a device (each has its own stream
@@ -1132,6 +1135,122 @@ typedef struct {
   uint32_t* vx_dropped;        /* [n] */
 } csg_voxel_job;
 int csg_voxel_cloud(csg_ctx* ctx, const csg_voxel_job* job, uint32_t n_frames, void* stream);
+
+/* The depth image of a host-output batch for csg_sensor_depth, without its trip
+ * to the host: the exact counterparts of csg_keep_points and csg_last_points.
+ * After csg_keep_depth(ctx, 1) every later host-output batch renders its depth
+ * into the context's own device image even when csg_outputs.depth is NULL and
+ * nothing else asks for it, and copies nothing more than it did; 0 turns that
+ * off again.  csg_last_depth returns the device image [n_frames][height][width]
+ * float32 of the context's last batch and its frame count (NULL and 0 when that
+ * batch rendered no depth, or wrote it to the caller's device memory); it stays
+ * valid until the context's next batch.  Neither call touches the GPU. */
+int csg_keep_depth(csg_ctx* ctx, int32_t keep);
+int csg_last_depth(csg_ctx* ctx, const float** depth, uint32_t* n_frames);
+
+/* Simulated stereo-camera depth: the ideal depth of a frame as a stereo depth
+ * camera registered to the colour camera would return it -- half-occlusion holes
+ * beside foreground edges, a matching window that erodes edges and drops thin
+ * structure, disparity quantisation and disparity noise (both grow as z^2 in
+ * depth) -- with the cause of every missing value.  A stand-alone pass on
+ * device memory only, like csg_voxel_cloud: it needs no scene and no earlier
+ * render, and the frame size is the job's own.  Everything is local and an
+ * integer in the disparity domain, so the result is defined to the bit.  Every
+ * float operation below is float32 and rounds once (no contraction); '/' is the
+ * correctly rounded division.  W = width, H = height, b = baseline, r = radius.
+ *
+ * Geometry.  The depth image is registered to the colour camera, as in aligned
+ * RGB-D datasets.  The second camera sits at (b, 0, 0) in the OpenCV camera
+ * frame; b may be negative.  A point at depth z has the disparity
+ * D = fx * |b| / z; the second camera sees it in column x - D for b > 0 and
+ * x + D for b < 0.
+ *
+ * Per pixel (x, y) of frame f, p = y * W + x, d = depth[f][y][x]:
+ *   fb = fl32(fx_f * |b|) with fx_f = intrinsics[f][0] (the [n][4] table of
+ *     csg_point_job.intrinsics; only fx is read).
+ *   D = fl32(fb / d).
+ *   The pixel is a surface iff d is finite, d > 0 and D > 0 (a NaN D fails).
+ *   dq, the disparity in 1/256 px: 2^30 if D is infinite or D >= 4194304.0f,
+ *     otherwise (uint32) fl32(fl32(D * 256.0f) + 0.5f).
+ *   u, the second camera's column in 1/256 px: 256 * x + 128 - dq for b > 0,
+ *     256 * x + 128 + dq for b < 0.  It fits int32.
+ *
+ * Cause.  sensor_cause[f][y][x]; the first rule that applies wins:
+ *   1 none     the pixel is not a surface.
+ *   2 range    !(z_min <= d <= z_max).
+ *   3 half-occluded   the pixel is hidden from the second camera.  b > 0: some
+ *              surface pixel x' > x of the same row has u(x') <= u(x).  b < 0:
+ *              some surface pixel x' < x has u(x') >= u(x).  Every surface
+ *              pixel occludes, out-of-range ones included; others never do.
+ *   4 band     only with CSG_SENSOR_CLIP_BAND.  b > 0: u < 0.  b < 0:
+ *              u >= 256 * W.  The strip the second camera's image lacks.
+ *   5 support  a pixel is lit if none of the rules 1-4 applies to it.  n counts
+ *              the lit pixels (x', y') of the (2r+1)^2 window around (x, y) with
+ *              |dq(x', y') - dq(x, y)| <= tol; the centre counts, pixels outside
+ *              the image do not.  Cause 5 iff n < min_support.
+ *   6 noise    m <= 0, with m as below.
+ *   0 return   none of the rules 1-6 applies.
+ *
+ * Value of a return, with fmix32 as under csg_sample_object_points:
+ *   key_f = frame_keys[f], or f when frame_keys is NULL.
+ *   base = fmix32(seed ^ key_f), h1 = fmix32(base ^ p),
+ *   h2 = fmix32(h1 ^ 0x9E3779B9u).
+ *   g = (h1 & 0xFFFF) + (h1 >> 16) + (h2 & 0xFFFF) + (h2 >> 16) - 131070, in
+ *     int64: a sum of four uniforms, mean 0, standard deviation 65536 / sqrt(3).
+ *   e = (g * noise_k + 32768) >> 16, an arithmetic shift in int64.
+ *   sh = 8 - subpixel_bits.
+ *   m = (dq + e + ((1 << sh) >> 1)) >> sh, arithmetic.
+ *   dn = (uint32)(m << sh), below 2^31.
+ *   sensor_depth = fl32(fl32(fb * 256.0f) / (float)dn); the conversion rounds
+ *     to nearest even.
+ *
+ * What is written.  sensor_depth is 0.0f wherever the cause is not 0: the "no
+ * return" value of real depth files, and what CSG_FILE_DEPTH16_PNG maps to sample
+ * 0.  sensor_count[f][c], c = 0..6, holds the pixels of each cause.  Every
+ * element of every requested output is written.  The result is a pure function
+ * of the inputs: no float atomics, nothing depends on scheduling or on the
+ * frame's place in the batch except through its key.  No input value yields an
+ * address outside the arrays described.
+ *
+ * sensor_depth must not overlap depth (the kernels read neighbours); no output
+ * may overlap a source.  This is checked on the host.
+ *
+ * Enqueues on `stream` (NULL = the context's stream) and returns; behind the
+ * render that wrote the sources on the same stream it needs no synchronisation.
+ * csg_synchronize waits for it under the rule for the crops.  The pass has
+ * scratch of its own (4 bytes per pixel and 32 per frame), grown to the job and
+ * bounded at 256 MiB: a job that needs more runs as ranges of frames.  An event
+ * orders passes on different streams; it never touches the render's work buffers.
+ *
+ * Returns -1 for a NULL ctx.  CSG_ERR_INVALID, nothing enqueued or written: job
+ * NULL; n_frames == 0; width or height outside 1..8192; radius above 4;
+ * min_support outside 1..(2r+1)^2; subpixel_bits above 8; noise_k above 2^20;
+ * an unknown flag; baseline not finite or zero; z_min or z_max not finite, or
+ * not 0 < z_min <= z_max; depth or intrinsics NULL; no output at all; an
+ * output that overlaps a source; a pointer that is not aligned to its element
+ * (4 bytes for all but sensor_cause). */
+#define CSG_SENSOR_CLIP_BAND 1u   /* rule 4: no return outside the second camera's image */
+typedef struct {
+  uint32_t width, height;      /* of the frames: 1..8192 each */
+  uint32_t radius;             /* r: 0..4, the matching window is (2r+1)^2 */
+  uint32_t min_support;        /* 1..(2r+1)^2 */
+  uint32_t tol;                /* disparity tolerance of the window, 1/256 px */
+  uint32_t subpixel_bits;      /* 0..8: returned disparities are multiples of 2^-bits px */
+  uint32_t noise_k;            /* 0..2^20: disparity noise, standard deviation noise_k / sqrt(3) / 256 px */
+  uint32_t seed;
+  uint32_t flags;              /* CSG_SENSOR_* */
+  float    baseline;           /* b, metres: finite, not 0 */
+  float    z_min, z_max;       /* metres: finite, 0 < z_min <= z_max */
+  /* sources, device memory */
+  const float*    depth;       /* [n][H][W] as csg_outputs.depth */
+  const float*    intrinsics;  /* [n][4] fx fy cx cy as csg_point_job.intrinsics; only fx is read */
+  const uint32_t* frame_keys;  /* [n], or NULL: key_f = f */
+  /* outputs, device memory; any may be NULL, not all */
+  float*    sensor_depth;      /* [n][H][W], 0.0f where there is no return */
+  uint8_t*  sensor_cause;      /* [n][H][W] */
+  uint32_t* sensor_count;      /* [n][7] */
+} csg_sensor_job;
+int csg_sensor_depth(csg_ctx* ctx, const csg_sensor_job* job, uint32_t n_frames, void* stream);
 
 /* Stand-alone 3D->2D projection (host buffers): uv [n][2], vis [n] without a
  * depth test (1 = in front and inside the image, 0 otherwise). */
