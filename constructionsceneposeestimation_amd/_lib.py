@@ -36,6 +36,7 @@ EXPORTED = (
     "csg_encode_span_masks", "csg_encode_jpeg", "csg_keep_rgb", "csg_last_rgb",
     "csg_voxel_cloud", "csg_keep_points", "csg_last_points",
     "csg_sensor_depth", "csg_keep_depth", "csg_last_depth",
+    "csg_farthest_points",
 )
 
 
@@ -189,6 +190,22 @@ class SensorJob(C.Structure):
 
 SENSOR_CLIP_BAND = 1   # CSG_SENSOR_CLIP_BAND
 
+FPS_MAX_PAYLOADS = 4   # CSG_FPS_MAX_PAYLOADS
+
+
+class FpsPayload(C.Structure):
+    """csg_fps_payload."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_uint32), ("fill", C.c_uint32)]
+
+
+class FpsJob(C.Structure):
+    """csg_fps_job (csg_farthest_points)."""
+    _fields_ = [("rows", C.c_uint32), ("pool", C.c_uint32), ("samples", C.c_uint32), ("seed", C.c_uint32),
+                ("n_payloads", C.c_uint32), ("pad", C.c_uint32),
+                ("xyz", C.c_void_p), ("counts", C.c_void_p), ("set_keys", C.c_void_p),
+                ("fp_index", C.c_void_p), ("fp_xyz", C.c_void_p), ("fp_dist2", C.c_void_p), ("fp_count", C.c_void_p),
+                ("payloads", FpsPayload * FPS_MAX_PAYLOADS)]
+
 
 class EncodeJob(C.Structure):
     """csg_encode_job (csg_encode_files)."""
@@ -278,6 +295,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     lib.csg_keep_points.argtypes = [vp, i32]
     lib.csg_last_points.argtypes = [vp, C.POINTER(vp), C.POINTER(u32)]
     lib.csg_sensor_depth.argtypes = [vp, C.POINTER(SensorJob), u32, vp]
+    lib.csg_farthest_points.argtypes = [vp, C.POINTER(FpsJob), u32, vp]
     lib.csg_keep_depth.argtypes = [vp, i32]
     lib.csg_last_depth.argtypes = [vp, C.POINTER(vp), C.POINTER(u32)]
     lib.csg_keep_rgb.argtypes = [vp, i32]

@@ -1,7 +1,7 @@
 // The stand-alone passes of libcsg.so (see include/csg_api.h): object crops, mask spans, mask PNGs, object
-// points, voxel clouds, stereo-camera depth and the three amodal passes.  Each validates its job on the
-// host, orders itself behind the last pass that used its scratch (PassOrder, csg_ctx.h), grows that scratch
-// and enqueues its kernels on the caller's stream.  None of them touches a render's work buffers.
+// points, voxel clouds, stereo-camera depth, farthest points and the three amodal passes.  Each validates
+// its job on the host, orders itself behind the last pass that used its scratch (PassOrder, csg_ctx.h), grows
+// that scratch and enqueues its kernels on the caller's stream.  None of them touches a render's work buffers.
 #include <stdlib.h>
 #include <string.h>
 
@@ -12,6 +12,7 @@
 #include "csg_amodal_spans.h"
 #include "csg_crops.h"
 #include "csg_ctx.h"
+#include "csg_fps.h"
 #include "csg_points.h"
 #include "csg_spans.h"
 
@@ -533,6 +534,84 @@ int csg_sensor_depth(csg_ctx* c, const csg_sensor_job* job, uint32_t n_frames, v
   }
   HIP_TRY(c, hipGetLastError());
   return c->sn.end(c, st);
+}
+
+// Farthest-point sampling: a stand-alone pass over device arrays (no scene state, no work buffers, no
+// scratch: a set's candidates live in its workgroup's registers, the chosen ones in its LDS); validates the
+// job and enqueues one kernel, in ranges of 2^30 sets.
+int csg_farthest_points(csg_ctx* c, const csg_fps_job* job, uint32_t n_sets, void* stream) {
+  static_assert(CSG_FPS_MAX_PAYLOADS == kFpMaxPayloads, "payload slots");
+  if (!c) return CSG_ERR_INVALID;
+  if (!job) return c->fail(CSG_ERR_INVALID, "farthest_points: null job");
+  if (n_sets == 0) return c->fail(CSG_ERR_INVALID, "farthest_points: no sets");
+  if (job->rows < 1 || job->rows > (1u << 24)) return c->fail(CSG_ERR_INVALID, "farthest_points: rows %u outside 1..2^24", job->rows);
+  if (job->pool < 1 || job->pool > kFpMaxPool)
+    return c->fail(CSG_ERR_INVALID, "farthest_points: pool %u outside 1..%u", job->pool, kFpMaxPool);
+  if (job->samples < 1 || job->samples > kFpMaxSamples)
+    return c->fail(CSG_ERR_INVALID, "farthest_points: samples %u outside 1..%u", job->samples, kFpMaxSamples);
+  if (!job->xyz) return c->fail(CSG_ERR_INVALID, "farthest_points: xyz must not be NULL");
+  if (job->n_payloads > kFpMaxPayloads)
+    return c->fail(CSG_ERR_INVALID, "farthest_points: %u payloads, at most %u", job->n_payloads, kFpMaxPayloads);
+  if (!job->fp_index && !job->fp_xyz && !job->fp_dist2 && !job->fp_count && job->n_payloads == 0)
+    return c->fail(CSG_ERR_INVALID, "farthest_points: no output");
+  for (uint32_t p = 0; p < job->n_payloads; ++p) {
+    const csg_fps_payload& pl = job->payloads[p];
+    if (!pl.src || !pl.dst) return c->fail(CSG_ERR_INVALID, "farthest_points: payload %u: src and dst must not be NULL", p);
+    if (pl.row_bytes < 1 || pl.row_bytes > kFpMaxRowBytes)
+      return c->fail(CSG_ERR_INVALID, "farthest_points: payload %u: row_bytes %u outside 1..%u", p, pl.row_bytes, kFpMaxRowBytes);
+  }
+  if (((uintptr_t)job->xyz | (uintptr_t)job->counts | (uintptr_t)job->set_keys | (uintptr_t)job->fp_index |
+       (uintptr_t)job->fp_xyz | (uintptr_t)job->fp_dist2 | (uintptr_t)job->fp_count) & 3u)
+    return c->fail(CSG_ERR_INVALID, "farthest_points: every pointer but the payloads' must be 4-byte aligned");
+  {   // no output may overlap a source or another output: sets run concurrently and read what others write
+    struct Range { const void* p; size_t bytes; };
+    const size_t S = n_sets, C = job->rows, K = job->samples;
+    Range src[3 + kFpMaxPayloads] = {{job->xyz, S * C * 12u}, {job->counts, S * 4u}, {job->set_keys, S * 4u}};
+    Range dst[4 + kFpMaxPayloads] = {{job->fp_index, S * K * 4u}, {job->fp_xyz, S * K * 12u}, {job->fp_dist2, S * K * 4u},
+                                     {job->fp_count, S * 8u}};
+    for (uint32_t p = 0; p < job->n_payloads; ++p) {
+      src[3 + p] = {job->payloads[p].src, S * C * job->payloads[p].row_bytes};
+      dst[4 + p] = {job->payloads[p].dst, S * K * job->payloads[p].row_bytes};
+    }
+    auto overlap = [](const Range& x, const Range& y) {
+      const uintptr_t x0 = (uintptr_t)x.p, y0 = (uintptr_t)y.p;
+      return x.p && y.p && x0 < y0 + y.bytes && y0 < x0 + x.bytes;
+    };
+    const uint32_t n_src = 3 + job->n_payloads, n_dst = 4 + job->n_payloads;
+    for (uint32_t d = 0; d < n_dst; ++d) {
+      for (uint32_t s = 0; s < n_src; ++s)
+        if (overlap(dst[d], src[s])) return c->fail(CSG_ERR_INVALID, "farthest_points: an output overlaps a source");
+      for (uint32_t e = d + 1; e < n_dst; ++e)
+        if (overlap(dst[d], dst[e])) return c->fail(CSG_ERR_INVALID, "farthest_points: two outputs overlap");
+    }
+  }
+  hipStream_t st;
+  CSG_TRY(pass_stream(c, stream, &st));
+  FpsArgs a{};
+  a.C = job->rows;
+  a.P = job->pool;
+  a.K = job->samples;
+  a.seed = job->seed;
+  a.n_payloads = job->n_payloads;
+  a.xyz = job->xyz;
+  a.counts = job->counts;
+  a.set_keys = job->set_keys;
+  a.fp_index = job->fp_index;
+  a.fp_xyz = job->fp_xyz;
+  a.fp_dist2 = job->fp_dist2;
+  a.fp_count = job->fp_count;
+  for (uint32_t p = 0; p < job->n_payloads; ++p)
+    a.payload[p] = {static_cast<const uint8_t*>(job->payloads[p].src), static_cast<uint8_t*>(job->payloads[p].dst),
+                    job->payloads[p].row_bytes, job->payloads[p].fill & 0xFFu};
+  constexpr uint32_t kRange = 1u << 30;   // workgroups of a launch
+  for (uint32_t s0 = 0; s0 < n_sets;) {
+    const uint32_t n = std::min(kRange, n_sets - s0);
+    a.first = s0;
+    launch_fps(a, n, st);
+    s0 += n;
+  }
+  HIP_TRY(c, hipGetLastError());
+  return CSG_OK;
 }
 
 // Amodal crop masks: reads the scene tables (synced here as a render syncs them) and the caller's

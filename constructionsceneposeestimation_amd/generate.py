@@ -33,8 +33,9 @@ same files:
                                     the GPU on a world-fixed grid of --voxel-size metres, one record per
                                     (cell, object): centroid, mean colour, ``label`` = the mask's inst_idx
                                     (-1 background) and point count, 23 B per record, voxel_cloud.read_ply;
-                                    + pointcloud/objects.json as obj_coords' and the grid; no reference
-                                    counterpart)
+                                    + pointcloud/objects.json as obj_coords' and the grid; with
+                                    --voxel-points K at most K records, chosen by farthest-point sampling
+                                    on the GPU and stored in that order; no reference counterpart)
   depth/sensor16_%06d.png          (optional "depth_sensor16_png": the depth a stereo depth camera registered to
                                     the colour camera would return -- half-occlusion holes, window erosion,
                                     quantised and noisy disparity (depth_sensor.StereoModel, made on the GPU
@@ -217,7 +218,8 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
              jpeg_quality: int = 95, jpeg_subsampling: str = "420", bop_rgb: str = "png",
              voxel_size: float = voxel_cloud.DEFAULT_VOXEL_SIZE, voxel_capacity: int = 0,
              depth_sensor_preset: Optional[str] = None, sensor_baseline: Optional[float] = None,
-             sensor_noise_px: Optional[float] = None, sensor_seed: int = 0) -> dict:
+             sensor_noise_px: Optional[float] = None, sensor_seed: int = 0,
+             voxel_points: int = 0, voxel_points_seed: int = 0) -> dict:
     """Render ``frames`` on one GPU and write them (``outputs``, default the
     reference's set; ``depth`` / ``depth_csv`` / ``pointcloud`` / ``normals``
     add the depth .npy, the depth .npy + CSV, the point cloud, the normals).
@@ -280,7 +282,13 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
     there behind the render (Renderer.voxel_cloud_host, csg_voxel_cloud) and only
     they cross PCIe.  ``voxel_capacity``: records per frame the pass starts with
     (0: voxel_cloud.DEFAULT_VOXEL_CAPACITY); a renderer keeps what its retries
-    settled on.  Not with "bop".
+    settled on.  Not with "bop".  ``voxel_points`` = K > 0 (at most 16384)
+    reduces every cloud to at most K records by farthest-point sampling on the
+    device (Renderer.voxel_cloud_host's ``keep``, csg_farthest_points), in
+    farthest-point order: the first records of a file are a coarser cloud of
+    the same frame.  The start is a function of ``voxel_points_seed`` and the
+    frame id, not of batching or sharding.  ``pointcloud/objects.json`` and the
+    summary then record ``voxel_points`` and the seed.
     ``outputs`` with "depth_sensor16_png": ``depth/sensor16_%06d.png``, the depth
     a stereo depth camera would return for the frame (depth_sensor.py): the
     model is ``depth_sensor_preset`` of depth_sensor.PRESETS (default "site")
@@ -309,6 +317,8 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
     if normals:
         outs.add("normals")
     check_bop(outs)
+    if not 0 <= int(voxel_points) <= 16384:
+        raise ValueError(f"voxel_points {voxel_points!r} outside 0..16384")
     want_bop = BOP_OUTPUT in outs
     if bop_rgb not in ("png", "jpg"):
         raise ValueError(f"bop_rgb {bop_rgb!r}: 'png' or 'jpg'")
@@ -333,6 +343,8 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
     want_vox = "pointcloud_voxel_ply" in outs
     if want_vox and not (np.isfinite(float(voxel_size)) and float(voxel_size) > 0 and int(voxel_capacity) >= 0):
         raise ValueError(f"voxel_size {voxel_size!r}: a finite number > 0; voxel_capacity {voxel_capacity!r}: >= 0")
+    vox_keep = {"voxel_points": int(voxel_points), "voxel_points_seed": int(voxel_points_seed) & 0xFFFFFFFF} \
+        if int(voxel_points) else {}
     want_sens = "depth_sensor16_png" in outs
     if want_sens:
         s16 = float(depth16_counts_per_metre)
@@ -352,7 +364,7 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
             json.dump({"objects": objs}, fh, indent=2)
     if want_vox:   # what a record's label names, and the grid
         with open(os.path.join(out_dir, "pointcloud", "objects.json"), "w") as fh:
-            json.dump({"objects": objs, "voxel_size": float(np.float32(voxel_size))}, fh, indent=2)
+            json.dump({"objects": objs, "voxel_size": float(np.float32(voxel_size)), **vox_keep}, fh, indent=2)
     if "amodal_rle" in outs and "mask_rle" not in outs:
         raise ValueError("output amodal_rle adds to the annotations of mask_rle: ask for both")
     if "mask_rle" in outs:
@@ -565,7 +577,9 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                 raise RuntimeError(f"pointcloud_voxel_ply: the batch kept {n0} point, {n1} id and {n2} RGB images, "
                                    f"{len(fb)} frames rendered")
             recs, vox_cap[id(r)], _ = r.voxel_cloud_host(len(fb), voxel_size, points=pts, rgb=rgb, instance=ids,
-                                                         capacity=vox_cap.get(id(r), int(voxel_capacity)))
+                                                         capacity=vox_cap.get(id(r), int(voxel_capacity)),
+                                                         keep=int(voxel_points), keep_seed=int(voxel_points_seed),
+                                                         frame_keys=np.asarray(fb, np.uint32))
             voxr[0] = [(voxel_cloud.ply_bytes(x), len(x)) for x in recs]
             return sum(x.nbytes for x in recs)
 
@@ -836,7 +850,7 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
         summary["voxel_cloud"] = {"voxel_size": float(np.float32(voxel_size)),
                                   "capacity": max(vox_cap.values()) if vox_cap else int(voxel_capacity),
                                   "voxels_per_frame": round(vox_stats["voxels"] / max(vox_stats["frames"], 1), 1),
-                                  "voxels_max": vox_stats["voxels_max"]}
+                                  "voxels_max": vox_stats["voxels_max"], **vox_keep}
     return summary
 
 
@@ -889,6 +903,11 @@ def main(argv=None):
     ap.add_argument("--voxel-capacity", type=int, default=0,
                     help=f"voxel records per frame the pass starts with (0: {voxel_cloud.DEFAULT_VOXEL_CAPACITY}; "
                          "doubled while a frame overflows, and kept)")
+    ap.add_argument("--voxel-points", type=int, default=0,
+                    help="keep at most this many records of each voxel cloud, chosen by farthest-point sampling on "
+                         "the GPU and stored in that order (0: all; at most 16384)")
+    ap.add_argument("--voxel-points-seed", type=int, default=0,
+                    help="seed of the farthest-point start (a frame's key is its frame id)")
     ap.add_argument("--depth-sensor", default=None, metavar="PRESET", choices=sorted(depth_sensor.PRESETS),
                     help="stereo model of the depth_sensor16_png output (depth_sensor.PRESETS; default site)")
     ap.add_argument("--sensor-baseline", type=float, default=None,
@@ -914,7 +933,8 @@ def main(argv=None):
                        amodal_kinds=tuple(x.strip() for x in a.amodal_kinds.split(",") if x.strip()),
                        jpeg_quality=a.jpeg_quality, jpeg_subsampling=a.jpeg_subsampling, bop_rgb=a.bop_rgb,
                        voxel_size=a.voxel_size, voxel_capacity=a.voxel_capacity, depth_sensor_preset=a.depth_sensor,
-                       sensor_baseline=a.sensor_baseline, sensor_noise_px=a.sensor_noise_px, sensor_seed=a.sensor_seed)
+                       sensor_baseline=a.sensor_baseline, sensor_noise_px=a.sensor_noise_px, sensor_seed=a.sensor_seed,
+                       voxel_points=a.voxel_points, voxel_points_seed=a.voxel_points_seed)
     print(json.dumps(summary))
 
 

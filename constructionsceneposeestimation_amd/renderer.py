@@ -463,7 +463,8 @@ class Renderer:
     def render_crops(self, frames: np.ndarray, size: int = 128, per_frame: int = 8, min_pixels: int = 64,
                      pad: float = 1.5, kinds: Sequence[str] = DYNAMIC_KINDS,
                      want: Iterable[str] = ("rgb", "mask", "coords"), object_frames=None,
-                     rgb_filter: str = "bilinear", samples: int = 1024, seed: int = 0) -> Dict[str, np.ndarray]:
+                     rgb_filter: str = "bilinear", samples: int = 1024, seed: int = 0,
+                     sampling: str = "stratified", candidates: int = 4096) -> Dict[str, np.ndarray]:
         """Render ``frames`` and deliver only their object crops to the host:
         chunks of ``max_frames`` are rendered into device tensors (torch),
         cropped on the same stream, and the crops and their ``info`` copied to
@@ -481,7 +482,17 @@ class Renderer:
         ``pt_coords`` (n, K, N, 3) uint16 with N = ``samples``, drawn under
         ``seed`` with the frames' own ids as keys, so a frame's samples do not
         depend on its place in ``frames``; ``pt_coords`` needs the tables
-        "coords" needs);
+        "coords" needs).  ``sampling`` = "fps" spreads the samples in 3D: each
+        chunk draws ``candidates`` = Nc stratified samples per slot (a multiple
+        of 4 in 16..16384) into device buffers and :meth:`farthest_points`
+        reduces them to N <= 16384 on the same stream, under the keys
+        ``frame_id * 64 + slot``; only the N chosen samples cross PCIe.  The
+        samples then come in farthest-point order (every prefix is a run of its
+        own), ``pt_count`` is unchanged, and two keys are added:
+        ``pt_spread`` (n, K) uint32, the distinct samples ``t0`` of each slot
+        (later ones repeat the run), and ``pt_radius2`` (n, K) float32, the
+        squared distance at which the last of them was chosen (every candidate
+        lies within it of a sample).  An empty slot reads as without it;
         ``kinds`` the object
         kinds that may be cropped (:func:`crops.eligible_labels`).  Returns
         ``crop_rgb`` / ``crop_mask`` / ``crop_coords`` / ``crop_depth`` (those
@@ -505,6 +516,12 @@ class Renderer:
             raise CsgError(f"render_crops: want {sorted(want)} must be a non-empty subset of rgb, mask, coords, depth, "
                            "amodal, amodal_depth, amodal_coords, points")
         pts, N = "points" in want, int(samples)
+        if sampling not in ("stratified", "fps"):
+            raise ValueError(f"render_crops: sampling {sampling!r} is not one of 'stratified', 'fps'")
+        fps, Nc = pts and sampling == "fps", int(candidates)
+        if fps and not (16 <= Nc <= 16384 and Nc % 4 == 0 and 1 <= N <= 16384):
+            raise CsgError(f"render_crops: sampling='fps' needs candidates {Nc} a multiple of 4 in 16..16384 and "
+                           f"samples {N} in 1..16384")
         for set_id, of in (object_frames or {}).items():
             self.set_object_frames(int(set_id), of)
         dev = torch.device("cuda", self.device)
@@ -533,6 +550,14 @@ class Renderer:
                            "pt_coords": ("points", (K, N, 3), torch.int16)})
             intr = torch.from_numpy(intrinsics_rows(frames)).to(dev)
             keys = torch.from_numpy(np.ascontiguousarray(frames["frame_id"]).view(np.int32)).to(dev)
+        if fps:
+            shapes.update({"pt_spread": ("points", (K,), torch.int32), "pt_radius2": ("points", (K,), torch.float32)})
+            cand = {"pt_choose": dbuf(True, (m, K, Nc), torch.int32), "pt_xyz": dbuf(True, (m, K, Nc, 3), torch.float32),
+                    "pt_rgb": dbuf(True, (m, K, Nc, 3), torch.uint8), "pt_coords": dbuf(True, (m, K, Nc, 3), torch.int16)}
+            fp_d2, fp_n = dbuf(True, (m, K, N), torch.float32), dbuf(True, (m, K, 2), torch.int32)
+            set_keys = torch.from_numpy(((frames["frame_id"].astype(np.uint32)[:, None] * np.uint32(64)
+                                          + np.arange(K, dtype=np.uint32)[None, :]).astype(np.uint32))
+                                        .view(np.int32)).to(dev)
         d_out = {k: dbuf(w is None or w in want, (m,) + sh, dt) for k, (w, sh, dt) in shapes.items()}
         h_out = {k: torch.empty((n,) + sh, dtype=dt, pin_memory=True)
                  for k, (w, sh, dt) in shapes.items() if d_out[k] is not None}
@@ -560,7 +585,25 @@ class Renderer:
                 elif "amodal" in want:
                     self.crop_amodal(frames[s:e], size=S, per_frame=K, info=ptr(d_out["info"]),
                                      crop_amodal=ptr(d_out["crop_amodal"]), stream=stream.cuda_stream)
-                if pts:
+                if fps:
+                    self.sample_points(e - s, samples=Nc, per_frame=K, seed=seed, instance=ptr(src["instance"]),
+                                       info=ptr(d_out["info"]), depth=ptr(src["depth"]),
+                                       intrinsics=intr.data_ptr() + 16 * s, rgb=ptr(src["rgb"]),
+                                       obj_coords=ptr(src["obj_coords"]), frame_keys=keys.data_ptr() + 4 * s,
+                                       pt_count=ptr(d_out["pt_count"]), pt_choose=ptr(cand["pt_choose"]),
+                                       pt_xyz=ptr(cand["pt_xyz"]), pt_rgb=ptr(cand["pt_rgb"]),
+                                       pt_coords=ptr(cand["pt_coords"]), stream=stream.cuda_stream)
+                    self.farthest_points((e - s) * K, rows=Nc, pool=Nc, samples=N, xyz=ptr(cand["pt_xyz"]),
+                                         counts=ptr(d_out["pt_count"]), set_keys=set_keys.data_ptr() + 4 * K * s,
+                                         seed=seed, fp_xyz=ptr(d_out["pt_xyz"]), fp_dist2=ptr(fp_d2), fp_count=ptr(fp_n),
+                                         payloads=((ptr(cand["pt_choose"]), ptr(d_out["pt_choose"]), 4, 0xFF),
+                                                   (ptr(cand["pt_rgb"]), ptr(d_out["pt_rgb"]), 3, 0),
+                                                   (ptr(cand["pt_coords"]), ptr(d_out["pt_coords"]), 6, 0)),
+                                         stream=stream.cuda_stream)
+                    d_out["pt_spread"].copy_(fp_n[:, :, 0])
+                    last = (fp_n[:, :, 0].long() - 1).clamp_(0, N - 1)   # (an empty slot: entry 0, which is 0.0)
+                    d_out["pt_radius2"].copy_(torch.gather(fp_d2, 2, last[:, :, None])[:, :, 0])
+                elif pts:
                     self.sample_points(e - s, samples=N, per_frame=K, seed=seed, instance=ptr(src["instance"]),
                                        info=ptr(d_out["info"]), depth=ptr(src["depth"]),
                                        intrinsics=intr.data_ptr() + 16 * s, rgb=ptr(src["rgb"]),
@@ -576,7 +619,7 @@ class Renderer:
         for k in ("crop_coords", "crop_amodal_coords", "pt_coords"):
             if k in out:
                 out[k] = out[k].view(np.uint16)
-        for k in ("pt_count", "pt_choose"):
+        for k in ("pt_count", "pt_choose", "pt_spread"):
             if k in out:
                 out[k] = out[k].view(np.uint32)
         info = out["info"].view(CROP_INFO_DTYPE).reshape(n, K)
@@ -959,7 +1002,8 @@ class Renderer:
 
     def voxel_cloud_host(self, n: int, voxel_size: float = DEFAULT_VOXEL_SIZE, *, points: int, rgb: int = 0,
                          instance: int = 0, capacity: int = 0, height: Optional[int] = None,
-                         width: Optional[int] = None, n_labels: Optional[int] = None, stream: int = 0):
+                         width: Optional[int] = None, n_labels: Optional[int] = None, stream: int = 0,
+                         keep: int = 0, keep_pool: int = 16384, keep_seed: int = 0, frame_keys=None):
         """:meth:`voxel_cloud` of device images (pointers ``points``, ``rgb``,
         ``instance``), delivered to the host: returns ``(frames, capacity,
         dropped)`` where ``frames`` is a list of ``n`` structured arrays of
@@ -972,11 +1016,22 @@ class Renderer:
         cross PCIe: the pass runs on a stream of the wrapper's own, and the
         frames' records are packed on the device and copied once.  ``stream``
         (a raw handle, 0: none) is the stream still writing the sources, if
-        any: it is waited for first.  Synchronous."""
+        any: it is waited for first.  Synchronous.
+
+        ``keep`` = K > 0 reduces every cloud to at most K records by
+        :meth:`farthest_points` on the device, once the capacity has settled:
+        at most ``keep_pool`` records of a frame, evenly strided, are
+        candidates, the start is hashed from ``keep_seed`` and the frame's key
+        (``frame_keys`` (n,) uint32; None: the frame's place), and each frame
+        returns its first ``min(K, t0)`` records in farthest-point order (every
+        prefix of them is such a reduction too).  Only those cross PCIe."""
         import torch
         n = int(n)
         H = self.height if height is None else int(height)
         W = self.width if width is None else int(width)
+        keep = int(keep)
+        if keep < 0 or keep > 16384:
+            raise CsgError(f"voxel_cloud_host: keep {keep} outside 0..16384")
         cap = min(int(capacity) or DEFAULT_VOXEL_CAPACITY, H * W)
         dev = torch.device("cuda", self.device)
         if stream:
@@ -1003,6 +1058,23 @@ class Renderer:
                     raise CsgError("voxel_cloud_host: a frame overflows a capacity of H * W")
                 cap = min(2 * cap, H * W)
             totals = tot[0].astype(np.int64)
+            if keep:   # the first min(K, t0) farthest-point samples of each frame instead of its records
+                d_key = None if frame_keys is None else \
+                    torch.from_numpy(np.ascontiguousarray(frame_keys, np.uint32).reshape(n).view(np.int32)).to(dev)
+                k_xyz = torch.empty((n, keep, 3), dtype=torch.float32, device=dev)
+                k_rgb = torch.empty((n, keep, 3), dtype=torch.uint8, device=dev)
+                k_lab = torch.empty((n, keep), dtype=torch.int32, device=dev)
+                k_cnt = torch.empty((n, keep), dtype=torch.int32, device=dev)
+                k_n = torch.empty((n, 2), dtype=torch.int32, device=dev)
+                self.farthest_points(n, rows=cap, pool=keep_pool, samples=keep, xyz=d_xyz.data_ptr(),
+                                     counts=d_tot[0].data_ptr(), seed=keep_seed,
+                                     set_keys=d_key.data_ptr() if d_key is not None else 0, fp_xyz=k_xyz.data_ptr(),
+                                     fp_count=k_n.data_ptr(),
+                                     payloads=((d_rgb.data_ptr(), k_rgb.data_ptr(), 3, 0),
+                                               (d_lab.data_ptr(), k_lab.data_ptr(), 4, 0xFF),
+                                               (d_cnt.data_ptr(), k_cnt.data_ptr(), 4, 0)), stream=st.cuda_stream)
+                totals = k_n.cpu().numpy().view(np.uint32)[:, 0].astype(np.int64)   # t0 <= K
+                d_xyz, d_rgb, d_lab, d_cnt = k_xyz, k_rgb, k_lab, k_cnt
             parts = []
             for t in (d_xyz, d_rgb, d_lab, d_cnt):   # the records in use, and no more
                 parts.append(torch.cat([t[f, :int(totals[f])] for f in range(n)]).cpu().numpy() if n else None)
@@ -1114,6 +1186,92 @@ class Renderer:
         p, nf = C.c_void_p(), C.c_uint32()
         self._check(self.lib.csg_last_depth(self.ctx, C.byref(p), C.byref(nf)), "last_depth")
         return int(p.value or 0), int(nf.value)
+
+    # -- farthest-point sampling ------------------------------------------------------------
+    def farthest_points(self, n_sets: int, *, rows: int, pool: int = 16384, samples: int, xyz: int, counts: int = 0,
+                        set_keys: int = 0, seed: int = 0, fp_index: int = 0, fp_xyz: int = 0, fp_dist2: int = 0,
+                        fp_count: int = 0, payloads=(), stream: int = 0) -> None:
+        """Enqueue the farthest-point samples of ``n_sets`` point sets
+        (csg_farthest_points; raw device pointers, like :meth:`sample_points`):
+        ``xyz`` (S, C, 3) float32 with C = ``rows``, of which set s has
+        ``counts[s]`` rows in use (``counts`` (S,) uint32; 0: all C;
+        0xFFFFFFFF, the voxel clouds' overflow mark: none).  At most ``pool``
+        rows of a set are candidates (:func:`farthest_points.candidate_rows`);
+        rows with a coordinate that is not finite are skipped.  ``samples`` = K
+        are chosen: a start hashed from ``seed`` and the set's key
+        (``set_keys`` (S,) uint32; 0: the set's place), then always the
+        candidate farthest from those chosen, the lowest on ties.
+        ``fp_index`` (S, K) uint32 gets the rows, ``fp_xyz`` (S, K, 3) float32
+        their points, ``fp_dist2`` (S, K) float32 the squared distance at which
+        each was chosen (+inf first, then non-increasing) and ``fp_count``
+        (S, 2) uint32 ``t0`` (the distinct samples; entries past it repeat the
+        run and have distance 0) and the valid candidates.  ``payloads`` is up
+        to 4 tuples ``(src, dst, row_bytes, fill)``: rows of ``src``
+        (S, C, row_bytes) are gathered to ``dst`` (S, K, row_bytes) by
+        ``fp_index``; an empty set's rows are ``fill`` bytes.  Any output may be
+        0, not all.  On the stream of the pass that wrote the sources no
+        synchronisation is needed in between."""
+        payloads = tuple(payloads)
+        if len(payloads) > _lib.FPS_MAX_PAYLOADS:
+            raise CsgError(f"farthest_points: {len(payloads)} payloads, at most {_lib.FPS_MAX_PAYLOADS}")
+        job = _lib.FpsJob(int(rows), int(pool), int(samples), int(seed) & 0xFFFFFFFF, len(payloads), 0, xyz or None,
+                          counts or None, set_keys or None, fp_index or None, fp_xyz or None, fp_dist2 or None,
+                          fp_count or None)
+        for i, (src, dst, row_bytes, fill) in enumerate(payloads):
+            job.payloads[i] = _lib.FpsPayload(src or None, dst or None, int(row_bytes), int(fill) & 0xFF)
+        self._check(self.lib.csg_farthest_points(self.ctx, C.byref(job), int(n_sets), stream or None),
+                    "farthest_points")
+
+    def farthest_points_host(self, xyz, counts=None, *, samples: int, pool: int = 16384, seed: int = 0,
+                             set_keys=None, payloads=()) -> dict:
+        """:meth:`farthest_points` of host arrays, delivered to the host:
+        ``xyz`` (S, C, 3) float32, ``counts`` and ``set_keys`` (S,) uint32 or
+        None, ``payloads`` up to 4 arrays (S, C, ...) of any dtype (or tuples
+        ``(array, fill)``; the fill byte defaults to 0).  Returns a dict with
+        ``"index"`` (S, K) uint32, ``"xyz"`` (S, K, 3) float32, ``"dist2"``
+        (S, K) float32, ``"count"`` (S, 2) uint32 and ``"payloads"``, the list
+        of the gathered arrays (S, K, ...).  Synchronous."""
+        import torch
+        xyz = np.ascontiguousarray(xyz, np.float32)
+        if xyz.ndim != 3 or xyz.shape[2] != 3:
+            raise CsgError(f"farthest_points_host: xyz of shape {xyz.shape} is not (S, C, 3)")
+        S, Cr, K = xyz.shape[0], xyz.shape[1], int(samples)
+        dev = torch.device("cuda", self.device)
+        st = self.span_stream()
+
+        def up(a):   # bit copies: torch has no unsigned 32-bit tensors
+            return torch.from_numpy(np.ascontiguousarray(a).reshape(-1).view(np.uint8)).to(dev)
+
+        with torch.cuda.stream(st):
+            d_xyz = up(xyz)
+            d_cnt = None if counts is None else up(np.ascontiguousarray(counts, np.uint32).reshape(S))
+            d_key = None if set_keys is None else up(np.ascontiguousarray(set_keys, np.uint32).reshape(S))
+            d_idx = torch.empty((S, K), dtype=torch.int32, device=dev)
+            d_pts = torch.empty((S, K, 3), dtype=torch.int32, device=dev)
+            d_d2 = torch.empty((S, K), dtype=torch.int32, device=dev)
+            d_n = torch.empty((S, 2), dtype=torch.int32, device=dev)
+            pl, keep = [], []
+            for p in payloads:
+                arr, fill = p if isinstance(p, tuple) else (p, 0)
+                arr = np.ascontiguousarray(arr)
+                if arr.ndim < 2 or arr.shape[:2] != (S, Cr):
+                    raise CsgError(f"farthest_points_host: a payload of shape {arr.shape} is not (S, C, ...)")
+                rb = arr.dtype.itemsize * int(np.prod(arr.shape[2:], dtype=np.int64))
+                d_src = up(arr)
+                d_dst = torch.empty((S, K, rb), dtype=torch.uint8, device=dev)
+                keep.append((arr, d_src, d_dst))
+                pl.append((d_src.data_ptr(), d_dst.data_ptr(), rb, fill))
+            self.farthest_points(S, rows=Cr, pool=pool, samples=K, xyz=d_xyz.data_ptr(),
+                                 counts=d_cnt.data_ptr() if d_cnt is not None else 0,
+                                 set_keys=d_key.data_ptr() if d_key is not None else 0, seed=seed,
+                                 fp_index=d_idx.data_ptr(), fp_xyz=d_pts.data_ptr(), fp_dist2=d_d2.data_ptr(),
+                                 fp_count=d_n.data_ptr(), payloads=pl, stream=st.cuda_stream)
+            out = {"index": d_idx.cpu().numpy().view(np.uint32), "xyz": d_pts.cpu().numpy().view(np.float32),
+                   "dist2": d_d2.cpu().numpy().view(np.float32), "count": d_n.cpu().numpy().view(np.uint32),
+                   "payloads": [d_dst.cpu().numpy().reshape(-1).view(arr.dtype).reshape((S, K) + arr.shape[2:])
+                                for arr, _, d_dst in keep]}
+            st.synchronize()
+        return out
 
     def keep_rgb(self, keep: bool = True) -> None:
         """Host-output batches (:meth:`render`, :meth:`render_files`) render

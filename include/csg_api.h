@@ -76,6 +76,8 @@
  *   csg_sensor_depth .......... (new) a depth image as a stereo depth camera would return
  *                               it: half-occlusion holes, window erosion, quantised and noisy
  *                               disparity, with the cause of every missing value
+ *   csg_farthest_points ....... (new) farthest-point samples of point sets (the point samples,
+ *                               the voxel clouds), with payload rows carried along
  *   csg_last_error / csg_destroy
  *
  * Threading: several contexts may share a device (each has its own stream
@@ -1251,6 +1253,104 @@ typedef struct {
   uint32_t* sensor_count;      /* [n][7] */
 } csg_sensor_job;
 int csg_sensor_depth(csg_ctx* ctx, const csg_sensor_job* job, uint32_t n_frames, void* stream);
+
+/* Farthest-point sampling of point sets: K samples of each set, the first a
+ * hashed start and every later one the candidate farthest from all samples chosen
+ * before it -- the reduction of a cloud to a fixed size that PointNet++, VoteNet,
+ * PVN3D and FFB6D perform on their inputs, here on the outputs of
+ * csg_sample_object_points (rows of a slot, pt_count as counts) and
+ * csg_voxel_cloud (rows of a frame, vx_total as counts).  Every prefix of a run is
+ * itself a run.  A stand-alone pass on device memory only, like csg_sensor_depth:
+ * it needs no scene and no earlier render.  S = n_sets, C = rows, P = pool,
+ * K = samples.  Every float operation below is float32 and rounds once (no
+ * contraction).
+ *
+ * Rows of a set.  m_s = C when counts is NULL; m_s = 0 when counts[s] ==
+ * 0xFFFFFFFF (csg_voxel_cloud's overflow mark: those rows are unspecified);
+ * otherwise m_s = min(counts[s], C).
+ *
+ * Candidates.  c_s = min(m_s, P).  Candidate j, 0 <= j < c_s, is row
+ * r_j = ((uint64)j * m_s) / c_s: j itself when m_s <= P, an even stride through
+ * the rows otherwise; strictly increasing.  A candidate is valid iff its three
+ * coordinates are finite.  v_s is the number of valid candidates.
+ *
+ * Distance.  For points a and b: dx = fl32(ax - bx), likewise dy and dz;
+ *   d2 = fl32(fl32(fl32(dx*dx) + fl32(dy*dy)) + fl32(dz*dz)).
+ * For valid candidates it is never NaN and never negative zero; it may be +inf.
+ *
+ * Start.  key_s = set_keys[s], or s when set_keys is NULL.
+ *   h = fmix32(fmix32(seed ^ key_s) ^ 0x9E3779B9u), fmix32 as under
+ *   csg_sample_object_points; j0 = (uint32)(((uint64)h * c_s) >> 32).
+ * The start is the valid candidate j that minimises (j + c_s - j0) % c_s: the
+ * first valid one at or after j0, cyclically.
+ *
+ * Steps.  mind_j = +inf for every valid j.  Step 0 chooses the start, and
+ * fp_dist2[s][0] = +inf.  After choosing candidate a, mind_j = min(mind_j,
+ * d2(p_j, p_a)) for every valid j, so mind_a becomes 0.  Step t >= 1: g is the
+ * maximum of mind_j over the valid j.  If g == 0, t0 = t and the run stops (every
+ * valid candidate coincides with a sample).  Otherwise the step chooses the lowest
+ * j with mind_j == g, and fp_dist2[s][t] = g.  If all K steps choose, t0 = K.
+ * fp_dist2[s][1 .. t0 - 1] is therefore non-increasing, and every valid
+ * candidate lies within fp_dist2[s][t0 - 1] (squared) of a sample.
+ *
+ * Outputs.  For t < t0: fp_index[s][t] = r_j, the row within the set, and
+ * fp_xyz[s][t] is that row, bit for bit.  For t >= t0 (the wrap, as the point
+ * samples wrap with s mod M): fp_index and fp_xyz repeat entry t mod t0, and
+ * fp_dist2 = 0.0f.  fp_count[s] = {t0, v_s}.
+ * The empty set (v_s == 0): fp_count = {0, 0}, fp_index all 0xFFFFFFFF, fp_xyz
+ * the bits 0x7FC00000, fp_dist2 0.0f.
+ *
+ * Payload gathers.  Up to 4 records {src, dst, row_bytes, fill}: src is
+ * [S][C][row_bytes], dst is [S][K][row_bytes], row_bytes is 1..64, and rows are
+ * copied as bytes: dst[s][t] = src[s][fp_index[s][t]]; in an empty set every byte
+ * of the dst rows is `fill` (its low 8 bits).  This carries colours, labels or
+ * pixel indices along without a second pass.
+ *
+ * Every element of every requested output is written.  The result is a pure
+ * function of the inputs: it does not depend on scheduling, on the set's place
+ * in the call except through its key, or on how the kernel partitions the
+ * candidates (no atomics, no float reductions; ties go to the lowest j).  No
+ * coordinate or count yields an address outside the arrays described.
+ *
+ * Enqueues on `stream` (NULL = the context's stream) and returns; behind the
+ * pass that wrote the sources on the same stream it needs no synchronisation.
+ * csg_synchronize waits for it under the rule for the crops.  The pass has no
+ * scratch: a set's candidates live in the registers of one workgroup, which is
+ * why P is at most 16384 (larger sets go through the stride of the candidates).
+ *
+ * Returns -1 for a NULL ctx.  CSG_ERR_INVALID, nothing enqueued or written: job
+ * NULL; n_sets == 0; rows outside 1..2^24; pool outside 1..16384; samples
+ * outside 1..16384; xyz NULL; no output at all (no fp_* and no payload); more
+ * than 4 payloads; a payload with a NULL src or dst, or row_bytes outside
+ * 1..64; an output that overlaps a source or another output; a pointer that is
+ * not aligned to 4 bytes (xyz, counts, set_keys, fp_index, fp_xyz, fp_dist2 and
+ * fp_count; payloads need no alignment). */
+#define CSG_FPS_MAX_PAYLOADS 4u
+typedef struct {            /* 24 bytes */
+  const void* src;          /* [S][C][row_bytes], device memory */
+  void*       dst;          /* [S][K][row_bytes], device memory */
+  uint32_t    row_bytes;    /* 1..64 */
+  uint32_t    fill;         /* low 8 bits: every byte of an empty set's rows */
+} csg_fps_payload;
+typedef struct {
+  uint32_t rows;               /* C: rows per set, 1..2^24 */
+  uint32_t pool;               /* P: candidates per set at most, 1..16384 */
+  uint32_t samples;            /* K: 1..16384 */
+  uint32_t seed;
+  uint32_t n_payloads;         /* 0..CSG_FPS_MAX_PAYLOADS */
+  uint32_t pad;
+  /* sources, device memory */
+  const float*    xyz;         /* [S][C][3], always */
+  const uint32_t* counts;      /* [S], or NULL: every set has C rows */
+  const uint32_t* set_keys;    /* [S], or NULL: key_s = s */
+  /* outputs, device memory; any may be NULL, not all unless there is a payload */
+  uint32_t* fp_index;          /* [S][K] */
+  float*    fp_xyz;            /* [S][K][3] */
+  float*    fp_dist2;          /* [S][K] */
+  uint32_t* fp_count;          /* [S][2] = t0, v_s */
+  csg_fps_payload payloads[CSG_FPS_MAX_PAYLOADS];
+} csg_fps_job;
+int csg_farthest_points(csg_ctx* ctx, const csg_fps_job* job, uint32_t n_sets, void* stream);
 
 /* Stand-alone 3D->2D projection (host buffers): uv [n][2], vis [n] without a
  * depth test (1 = in front and inside the image, 0 otherwise). */
