@@ -25,8 +25,14 @@ Conventions.  ``obj_id = inst_idx + 1``: each scene object is its own model,
 because instances of one class differ in geometry.  The model frame is the
 object's local frame times the scale of its world transform, in millimetres;
 poses take it to OpenCV's camera (x right, y down, z forward), which is
-``diag(1, -1, -1)`` times the USD camera the renderer uses.  A frame lists the
-objects of the eligible kinds with amodal pixels (``px_count_all > 0``), in
+``diag(1, -1, -1)`` times the USD camera the renderer uses.  ``cam_K`` follows
+OpenCV's pixel convention: integer pixel coordinates are pixel centres.
+``K (R m + t)`` of the surface point drawn in pixel (x, y) is (x, y) z: the
+renderer samples that pixel at (x + 1/2, y + 1/2) with its principal point at
+(W/2, H/2), so ``cam_K``, ``camera.json`` and ``scene_camera.json`` hold
+cx = W/2 - 1/2, cy = H/2 - 1/2.  The label JSON,
+``crops.crop_intrinsics`` and ``object_points.intrinsics_rows`` keep the
+renderer's convention.  A frame lists the objects of the eligible kinds with amodal pixels (``px_count_all > 0``), in
 ascending ``inst_idx``; the list position is the ``gt_id`` of the mask names.
 An object inside the frame but wholly hidden is listed with ``visib_fract`` 0,
 ``bbox_visib`` [-1, -1, -1, -1] and an all-zero ``mask_visib`` file.
@@ -93,9 +99,11 @@ def check_depth_scale(near: float, counts_per_metre: float) -> None:
 
 # -- poses ---------------------------------------------------------------------------------
 def cam_K(proj: np.ndarray) -> np.ndarray:
-    """3 x 3 OpenCV intrinsics of a frame's pixel projection (camera_math.Intrinsics.pixel_projection)."""
+    """3 x 3 OpenCV intrinsics of a frame's pixel projection (camera_math.Intrinsics.pixel_projection).
+    The renderer samples pixel (x, y) at (x + 1/2, y + 1/2) of its continuous image coordinates; OpenCV's
+    integer coordinates are pixel centres, so the principal point moves by half a pixel: cx - 1/2, cy - 1/2."""
     P = np.asarray(proj, np.float64).reshape(4, 4)
-    return np.array([[P[0, 0], 0.0, -P[0, 2]], [0.0, -P[1, 1], -P[1, 2]], [0.0, 0.0, 1.0]])
+    return np.array([[P[0, 0], 0.0, -P[0, 2] - 0.5], [0.0, -P[1, 1], -P[1, 2] - 0.5], [0.0, 0.0, 1.0]])
 
 
 def epoch_models(object_frames: Sequence[np.ndarray]) -> Dict[str, np.ndarray]:

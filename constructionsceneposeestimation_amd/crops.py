@@ -75,7 +75,9 @@ def crop_intrinsics(intr, info: np.ndarray, S: int) -> np.ndarray:
     ``fx / step, fy / step, (cx - x0) / step, (cy - y0) / step`` with the
     frame's ``intr`` (``camera_math.Intrinsics``).  It uses the image
     convention of ``keypoints_uv`` (u right, v down, both positive focal
-    lengths).  Empty slots (label -1) get NaN."""
+    lengths) and the renderer's continuous pixel coordinates: crop sample
+    (i, j) lies at (i + 1/2, j + 1/2).  (``bop.cam_K`` alone uses OpenCV's
+    pixel-centre convention, half a pixel less.)  Empty slots (label -1) get NaN."""
     step, x0, y0 = _steps(info, S)
     K = np.zeros(step.shape + (3, 3), np.float64)
     K[..., 0, 0] = intr.fx / step

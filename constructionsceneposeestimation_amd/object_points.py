@@ -21,7 +21,9 @@ def intrinsics_rows(frames: np.ndarray) -> np.ndarray:
     """``fx, fy, cx, cy`` float32 (n, 4) of frame records (``renderer.FRAME_DTYPE``),
     read from each frame's pixel projection (``camera_math.Intrinsics.pixel_projection``:
     rows ``[fx, 0, -cx, 0]`` and ``[0, -fy, -cy, 0]``): the ``intrinsics`` source of
-    :meth:`renderer.Renderer.sample_points`."""
+    :meth:`renderer.Renderer.sample_points`.  They keep the renderer's convention,
+    in which pixel (x, y) is sampled at (x + 1/2, y + 1/2) (``bop.cam_K`` alone
+    uses OpenCV's pixel-centre convention, half a pixel less)."""
     proj = np.asarray(frames["proj"], np.float32).reshape(-1, 16)
     return np.ascontiguousarray(np.stack([proj[:, 0], -proj[:, 5], -proj[:, 2], -proj[:, 6]], axis=1), np.float32)
 

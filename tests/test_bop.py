@@ -58,14 +58,15 @@ def test_pose_projects_the_box_centre(wl):
             if abs(q[3]) < 1e-3:
                 continue
             p = K @ (R @ c_model + t)
-            assert np.abs(p[:2] / p[2] - q[:2] / q[3]).max() < 1e-6, (f, j)
+            # OpenCV's integer coordinates are pixel centres: the renderer's (u, v) reads (u - 1/2, v - 1/2)
+            assert np.abs(p[:2] / p[2] - (q[:2] / q[3] - 0.5)).max() < 1e-6, (f, j)
             assert abs(p[2] / 1000.0 - q[3]) < 1e-9 * max(1.0, abs(q[3]))   # depth along the optical axis, mm -> m
             n += 1
     assert n >= 40
     rec = bop.camera_record(V, P, 250.0)
     Rw = np.array(rec["cam_R_w2c"]).reshape(3, 3)
     assert abs(np.linalg.det(Rw) - 1.0) < 1e-12 and rec["depth_scale"] == 4.0
-    assert rec["cam_K"] == [wl.intr.fx, 0.0, wl.intr.cx, 0.0, wl.intr.fy, wl.intr.cy, 0.0, 0.0, 1.0]
+    assert rec["cam_K"] == [wl.intr.fx, 0.0, wl.intr.cx - 0.5, 0.0, wl.intr.fy, wl.intr.cy - 0.5, 0.0, 0.0, 1.0]
     Cw = np.linalg.inv(V)[:3, 3]                                    # the camera's position maps to the origin
     assert np.abs(Rw @ Cw * 1000.0 + np.array(rec["cam_t_w2c"])).max() < 1e-6
 
