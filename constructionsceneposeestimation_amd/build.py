@@ -28,7 +28,7 @@ DEPS = SOURCES + [os.path.join(PKG, "csrc", "csg_ctx.h"), os.path.join(PKG, "csr
                   os.path.join(PKG, "csrc", "csg_points.h"),
                   os.path.join(PKG, "csrc", "csg_amodal_spans.h"), os.path.join(PKG, "csrc", "csg_raster_math.h"),
                   os.path.join(PKG, "csrc", "csg_amodal_tri.inc"),
-                  os.path.join(PKG, "csrc", "csg_alpha_box.h"),
+                  os.path.join(PKG, "csrc", "csg_alpha_box.h"), os.path.join(PKG, "csrc", "csg_alpha_cut.h"),
                   os.path.join(PKG, "csrc", "csg_mask_png.h"), os.path.join(PKG, "csrc", "csg_bitio.h"),
                   os.path.join(PKG, "csrc", "csg_jpeg.h"), os.path.join(PKG, "csrc", "csg_voxels.h"),
                   os.path.join(PKG, "csrc", "csg_sensor.h"), os.path.join(PKG, "csrc", "csg_fps.h"),

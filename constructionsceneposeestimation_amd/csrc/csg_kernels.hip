@@ -209,7 +209,7 @@ typedef uint32_t v4u32 __attribute__((ext_vector_type(4)));
 // per-vertex variant -- each slice's distinct vertices transformed once into
 // LDS -- was bit-exact and 8% slower: profiles/r06/ab/setup_verts.txt.)
 __device__ __forceinline__ void setup_chunk(const SceneDev& s, const BatchDev& b, const Chunk& ch, uint32_t f,
-                                            int tid, int lane, uint4* sw);
+                                            int tid, int lane, uint4* sw, uint4* park);
 
 // Grid: x = frame (fast), (y, z) = chunk.  Consecutive workgroups take the
 // same chunk for successive frames, so a chunk's triangles (and its clip
@@ -235,11 +235,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
   }
   static_assert(16 * kRecGroups <= 2 * 64, "two chunk stores per lane");
   __shared__ uint4 tstage[kBlock / 64][16 * kRecGroups];
-  setup_chunk(s, b, ch, f, tid, lane, tstage[tid >> 6]);
+  // One record's groups 0-1 per lane, parked here across the alpha trim (its guard and cut need the
+  // registers; held in them, k_setup went to scratch).  Lane-private: program order is all it needs.
+  __shared__ uint4 tpark[2][kBlock];
+  setup_chunk(s, b, ch, f, tid, lane, tstage[tid >> 6], &tpark[0][tid]);
 }
 
 __device__ __forceinline__ void setup_chunk(const SceneDev& s, const BatchDev& b, const Chunk& ch, uint32_t f,
-                                            int tid, int lane, uint4* sw) {
+                                            int tid, int lane, uint4* sw, uint4* park) {
   const uint32_t i = ch.inst;
   const float* Cm = b.clip + ((size_t)f * s.n_inst + i) * 12;
 
@@ -352,23 +355,34 @@ __device__ __forceinline__ void setup_chunk(const SceneDev& s, const BatchDev& b
             for (int k = 0; k < 6; ++k) uv[k] = tu[k];
             uv_planes(h.A, h.B, h.C, h.invdet, uv, U, V);
             // Alpha trim: the pixel box shrinks to where (u, v) can reach the triangle's opaque
-            // uv box; a triangle without a passing quad emits nothing (csg_raster_math.h).
+            // uv box; a triangle without a passing quad emits nothing (the guards: csg_raster_math.h,
+            // the cut: csg_alpha_cut.h).  The record's groups 0-1 wait in LDS meanwhile (k_setup).
             if (is.trim && nq == 3 && in0 && in1 && in2 && nrec == 1) {
-              const float4 bx = s.tri_abox[g];
-              const bool none = bx.x > bx.y;   // "empty"; "full" is infinite
-              const float B = none ? 0.0f : fmaxf(fmaxf(fabsf(bx.x), fabsf(bx.y)), fmaxf(fabsf(bx.z), fabsf(bx.w)));
+              const float4 bx0 = s.tri_abox[g];
+              const bool none = bx0.x > bx0.y;   // "empty"; "full" is infinite
+              const float B = none ? 0.0f : fmaxf(fmaxf(fabsf(bx0.x), fabsf(bx0.y)), fmaxf(fabsf(bx0.z), fabsf(bx0.w)));
               float m;
+              park[0] = r0.g0;
+              park[kBlock] = r0.g1;
+              asm volatile("" ::: "memory");
+              bool left = true;
               if (B < INFINITY &&
                   alpha_trim_guard(v, uv, U, V, D, (float)max(atex_wh & 0xFFFFu, atex_wh >> 16), B, m)) {
-                int px0 = (int)(r0.g1.z & 0xFFFFu), py0 = (int)(r0.g1.z >> 16);
-                int px1 = (int)(r0.g1.w & 0xFFFFu), py1 = (int)(r0.g1.w >> 16);
-                if (none || !alpha_trim_box(U, V, D, bx, m, px0, py0, px1, py1)) {
-                  nrec = 0;
-                } else {
-                  r0.g1.z = (uint32_t)px0 | ((uint32_t)py0 << 16);
-                  r0.g1.w = (uint32_t)px1 | ((uint32_t)py1 << 16);
-                }
+                // the box is read again for the cut (an L1 hit), not held across the guard, where it was
+                // among the values that went to scratch (the barrier keeps the two loads apart)
+                asm volatile("" ::: "memory");
+                const float4 bx = s.tri_abox[g];
+                const uint4 p0 = park[0], p1 = park[kBlock];
+                uint32_t lo = p1.z, hi = p1.w;
+                left = !none && alpha_cut_box((int32_t)p0.x, (int32_t)p0.y, (int32_t)p0.z, (int32_t)p0.w, (int32_t)p1.x,
+                                              (int32_t)p1.y, U, V, D, bx.x, bx.y, bx.z, bx.w, m, lo, hi);
+                reinterpret_cast<uint32_t*>(park + kBlock)[2] = lo;
+                reinterpret_cast<uint32_t*>(park + kBlock)[3] = hi;
               }
+              asm volatile("" ::: "memory");
+              r0.g0 = park[0];
+              r0.g1 = park[kBlock];
+              if (!left) nrec = 0;
             }
           }
           c2 = make_uint4(uid, atex, __float_as_uint(D[0]), __float_as_uint(D[1]));

@@ -7,6 +7,7 @@
 #pragma once
 #include <math.h>
 
+#include "csg_alpha_cut.h"
 #include "csg_kernels.h"
 
 namespace csg {
@@ -299,17 +300,15 @@ __device__ __forceinline__ bool make_rec(const SceneDev& s, const float* su, con
 // ---------------------------------------------------------------------------
 // Alpha trim: k_setup shrinks the pixel box of an
 // alpha-tested record to the pixels whose (u, v) can fall inside the
-// triangle's opaque uv box (csg_alpha_box.h).  Every dropped pixel centre
+// triangle's opaque uv box (csg_alpha_box.h): the guards below, then the cut
+// (csg_alpha_cut.h: the snapped triangle clipped by the box's four half-planes).
+// Every dropped pixel centre
 // provably fails alpha_pass as k_raster's fragment() evaluates it, so no output
 // changes.  Only unclipped triangles are trimmed (one record, whose covered
 // pixel centres lie inside the snapped triangle).
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ float rcp_w(float w);
 constexpr float kTrimEps = 0x1p-20f;   // 4x the rounding of any expression bounded below (at most 2^-22 of its magnitude sum)
-#ifndef CSG_TRIM_PASSES
-#define CSG_TRIM_PASSES 2
-#endif
-constexpr int kTrimPasses = CSG_TRIM_PASSES;   // x / y rounds over the four half-planes (A/B: profiles/HISTORY.md)
 
 // The guards.  `v` are the clip-space vertices (W >= near), uv their texture
 // coordinates, U V D the record's planes, T = max(tw, th).  With
@@ -362,58 +361,6 @@ __device__ __forceinline__ bool alpha_trim_guard(const Cv3* v, const float* uv, 
   if (!(kTrimEps * T * ((S + umax * Sd) + (umax + 1.0f) * dmin) <= 0.25f * dmin)) return false;      // (a)
   m = kTrimEps * (S + B * Sd);
   return m < INFINITY;
-}
-
-// Shrink the pixel range [lo, hi] of one axis against the half-plane
-// g(t, o) = (a * t + b * o) + c >= 0 (t: this axis' pixel centre, o in [o0, o1]
-// the other's): a line of pixels goes when g < -m at both of its ends.  g is
-// monotone in t, so the lines that go are a prefix (a > 0) or a suffix (a < 0);
-// the reciprocal only proposes the bound, the line next to it is then evaluated
-// and decides (one retry a line further in, else no change).
-__device__ __forceinline__ void trim_axis(float a, float b, float c, float m, float o0, float o1, int& lo, int& hi) {
-  if (!(a != 0.0f) || lo > hi) return;
-  const float est = -((fmaxf(b * o0, b * o1) + c) + m) * __builtin_amdgcn_rcpf(a);   // g = -m at t = est
-  const float e = fminf(fmaxf(est - 0.5f, (float)lo - 1.0f), (float)hi + 1.0f);
-  auto gone = [&](int p) {
-    const float t = (float)p + 0.5f;
-    return fmaxf((a * t + b * o0) + c, (a * t + b * o1) + c) < -m;
-  };
-  if (a > 0.0f) {
-    int n = max((int)ceilf(e), lo);    // the first line kept
-    if (n > lo && !gone(n - 1)) {
-      --n;
-      if (n > lo && !gone(n - 1)) n = lo;
-    }
-    lo = n;
-  } else {
-    int n = min((int)floorf(e), hi);   // the last line kept
-    if (n < hi && !gone(n + 1)) {
-      ++n;
-      if (n < hi && !gone(n + 1)) n = hi;
-    }
-    hi = n;
-  }
-}
-
-// The record's pixel box against the opaque uv box bx = u_lo u_hi v_lo v_hi
-// (finite).  False: no pixel is left.
-__device__ __forceinline__ bool alpha_trim_box(const float* U, const float* V, const float* D, float4 bx, float m,
-                                               int& px0, int& py0, int& px1, int& py1) {
-  // u >= u_lo, u <= u_hi, v >= v_lo, v <= v_hi, each times D > 0: P - bound * D >= 0 or its negation.
-  // (The coefficients are formed where they are used: twelve of them held across the loop cost k_setup
-  // a wave of occupancy.)
-#pragma nounroll
-  for (int pass = 0; pass < kTrimPasses; ++pass) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float* P = k < 2 ? U : V;
-      const float bd = k == 0 ? bx.x : k == 1 ? bx.y : k == 2 ? bx.z : bx.w, sg = (k & 1) ? -1.0f : 1.0f;
-      const float h0 = sg * (P[0] - bd * D[0]), h1 = sg * (P[1] - bd * D[1]), h2 = sg * (P[2] - bd * D[2]);
-      trim_axis(h0, h1, h2, m, (float)py0 + 0.5f, (float)py1 + 0.5f, px0, px1);
-      trim_axis(h1, h0, h2, m, (float)px0 + 0.5f, (float)px1 + 0.5f, py0, py1);
-    }
-  }
-  return px0 <= px1 && py0 <= py1;
 }
 
 // q / w for q < 2^24, 1 <= w <= 256: float reciprocal estimate (off by at
