@@ -37,6 +37,7 @@ EXPORTED = (
     "csg_voxel_cloud", "csg_keep_points", "csg_last_points",
     "csg_sensor_depth", "csg_keep_depth", "csg_last_depth",
     "csg_farthest_points",
+    "csg_lens_map", "csg_lens_remap", "csg_lens_points",
 )
 
 
@@ -207,6 +208,31 @@ class FpsJob(C.Structure):
                 ("payloads", FpsPayload * FPS_MAX_PAYLOADS)]
 
 
+class LensModel(C.Structure):
+    """csg_lens_model (csg_lens_map, csg_lens_points)."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("src_width", C.c_uint32), ("src_height", C.c_uint32),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("k1", C.c_double), ("k2", C.c_double), ("p1", C.c_double), ("p2", C.c_double), ("k3", C.c_double),
+                ("k4", C.c_double), ("k5", C.c_double), ("k6", C.c_double),
+                ("sfx", C.c_double), ("sfy", C.c_double), ("scx", C.c_double), ("scy", C.c_double)]
+
+
+LENS_FILTERS = {"bilinear": 0, "nearest": 1}  # CSG_LENS_FILTER_*
+
+
+class LensJob(C.Structure):
+    """csg_lens_job (csg_lens_remap, csg_lens_points)."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("src_width", C.c_uint32), ("src_height", C.c_uint32),
+                ("n_labels", C.c_uint32), ("rgb_filter", C.c_uint32), ("map", C.c_void_p),
+                ("rgb", C.c_void_p), ("instance", C.c_void_p), ("depth", C.c_void_p), ("obj_coords", C.c_void_p),
+                ("lens_rgb", C.c_void_p), ("lens_instance", C.c_void_p), ("lens_depth", C.c_void_p),
+                ("lens_coords", C.c_void_p), ("lens_valid", C.c_void_p), ("lens_stats", C.c_void_p),
+                ("lens_count", C.c_void_p),
+                ("model", C.POINTER(LensModel)), ("n_keypoints", C.c_uint32), ("pad", C.c_uint32),
+                ("keypoints_uv", C.c_void_p), ("keypoints_vis", C.c_void_p), ("lens_uv", C.c_void_p),
+                ("lens_vis", C.c_void_p)]
+
+
 class EncodeJob(C.Structure):
     """csg_encode_job (csg_encode_files)."""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n_frames", C.c_uint32), ("file_kinds", C.c_uint32),
@@ -296,6 +322,9 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     lib.csg_last_points.argtypes = [vp, C.POINTER(vp), C.POINTER(u32)]
     lib.csg_sensor_depth.argtypes = [vp, C.POINTER(SensorJob), u32, vp]
     lib.csg_farthest_points.argtypes = [vp, C.POINTER(FpsJob), u32, vp]
+    lib.csg_lens_map.argtypes = [C.POINTER(LensModel), vp, vp]
+    lib.csg_lens_remap.argtypes = [vp, C.POINTER(LensJob), u32, vp]
+    lib.csg_lens_points.argtypes = [vp, C.POINTER(LensJob), u32, vp]
     lib.csg_keep_depth.argtypes = [vp, i32]
     lib.csg_last_depth.argtypes = [vp, C.POINTER(vp), C.POINTER(u32)]
     lib.csg_keep_rgb.argtypes = [vp, i32]

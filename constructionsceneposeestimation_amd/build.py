@@ -20,7 +20,7 @@ SOURCES = [os.path.join(PKG, "csrc", "csg_kernels.hip"), os.path.join(PKG, "csrc
            os.path.join(PKG, "csrc", "csg_points.hip"), os.path.join(PKG, "csrc", "csg_amodal_spans.hip"),
            os.path.join(PKG, "csrc", "csg_mask_png.hip"), os.path.join(PKG, "csrc", "csg_jpeg.hip"),
            os.path.join(PKG, "csrc", "csg_voxels.hip"), os.path.join(PKG, "csrc", "csg_sensor.hip"),
-           os.path.join(PKG, "csrc", "csg_fps.hip"),
+           os.path.join(PKG, "csrc", "csg_fps.hip"), os.path.join(PKG, "csrc", "csg_lens.hip"),
            os.path.join(PKG, "csrc", "csg_api.cpp"), os.path.join(PKG, "csrc", "csg_passes.cpp")]
 DEPS = SOURCES + [os.path.join(PKG, "csrc", "csg_ctx.h"), os.path.join(PKG, "csrc", "csg_kernels.h"), os.path.join(PKG, "csrc", "csg_encode.h"),
                   os.path.join(PKG, "csrc", "csg_deflate.h"), os.path.join(PKG, "csrc", "csg_widen.h"),
@@ -32,6 +32,7 @@ DEPS = SOURCES + [os.path.join(PKG, "csrc", "csg_ctx.h"), os.path.join(PKG, "csr
                   os.path.join(PKG, "csrc", "csg_mask_png.h"), os.path.join(PKG, "csrc", "csg_bitio.h"),
                   os.path.join(PKG, "csrc", "csg_jpeg.h"), os.path.join(PKG, "csrc", "csg_voxels.h"),
                   os.path.join(PKG, "csrc", "csg_sensor.h"), os.path.join(PKG, "csrc", "csg_fps.h"),
+                  os.path.join(PKG, "csrc", "csg_lens.h"), os.path.join(PKG, "csrc", "csg_lens_map.h"),
                   os.path.join(ROOT, "include", "csg_api.h")]
 ARCH = os.environ.get("CSG_OFFLOAD_ARCH", "gfx950")
 IO_LIB = os.path.join(PKG, "libcsgio.so")

@@ -1,5 +1,5 @@
 // The stand-alone passes of libcsg.so (see include/csg_api.h): object crops, mask spans, mask PNGs, object
-// points, voxel clouds, stereo-camera depth, farthest points and the three amodal passes.  Each validates
+// points, voxel clouds, stereo-camera depth, farthest points, lens distortion and the three amodal passes.  Each validates
 // its job on the host, orders itself behind the last pass that used its scratch (PassOrder, csg_ctx.h), grows
 // that scratch and enqueues its kernels on the caller's stream.  None of them touches a render's work buffers.
 #include <stdlib.h>
@@ -13,6 +13,8 @@
 #include "csg_crops.h"
 #include "csg_ctx.h"
 #include "csg_fps.h"
+#include "csg_lens.h"
+#include "csg_lens_map.h"
 #include "csg_points.h"
 #include "csg_spans.h"
 
@@ -610,6 +612,139 @@ int csg_farthest_points(csg_ctx* c, const csg_fps_job* job, uint32_t n_sets, voi
     launch_fps(a, n, st);
     s0 += n;
   }
+  HIP_TRY(c, hipGetLastError());
+  return CSG_OK;
+}
+
+// Lens distortion.  The map is host arithmetic alone (csg_lens_map.h): no context, no GPU.
+int csg_lens_map(const csg_lens_model* m, int32_t* map, uint32_t* counts) { return lens_map(m, map, counts); }
+
+// The resampling: a stand-alone pass over device arrays (no scene state, no work buffers, no scratch: the
+// statistics are reduced into the outputs themselves); validates the job and enqueues the kernels.
+int csg_lens_remap(csg_ctx* c, const csg_lens_job* job, uint32_t n_frames, void* stream) {
+  if (!c) return CSG_ERR_INVALID;
+  if (!job) return c->fail(CSG_ERR_INVALID, "lens_remap: null job");
+  if (n_frames == 0) return c->fail(CSG_ERR_INVALID, "lens_remap: no frames");
+  CSG_TRY(check_frame_dims(c, "lens_remap", job->width, job->height));
+  CSG_TRY(check_frame_dims(c, "lens_remap", job->src_width, job->src_height));
+  if (job->rgb_filter != CSG_LENS_FILTER_BILINEAR && job->rgb_filter != CSG_LENS_FILTER_NEAREST)
+    return c->fail(CSG_ERR_INVALID, "lens_remap: rgb_filter %u is neither CSG_LENS_FILTER_BILINEAR nor _NEAREST",
+                   job->rgb_filter);
+  if (!job->map) return c->fail(CSG_ERR_INVALID, "lens_remap: map is NULL");
+  if (!job->lens_rgb && !job->lens_instance && !job->lens_depth && !job->lens_coords && !job->lens_valid &&
+      !job->lens_stats && !job->lens_count)
+    return c->fail(CSG_ERR_INVALID, "lens_remap: no output");
+  if (job->lens_rgb && !job->rgb) return c->fail(CSG_ERR_INVALID, "lens_remap: lens_rgb needs rgb");
+  if ((job->lens_instance || job->lens_stats) && !job->instance)
+    return c->fail(CSG_ERR_INVALID, "lens_remap: lens_instance and lens_stats need instance");
+  if (job->lens_depth && !job->depth) return c->fail(CSG_ERR_INVALID, "lens_remap: lens_depth needs depth");
+  if (job->lens_coords && !job->obj_coords) return c->fail(CSG_ERR_INVALID, "lens_remap: lens_coords needs obj_coords");
+  if (job->lens_stats) CSG_TRY(check_labels(c, "lens_remap", job->n_labels));
+  if (((uintptr_t)job->map & 7u) || ((uintptr_t)job->obj_coords & 1u) ||
+      (((uintptr_t)job->instance | (uintptr_t)job->depth | (uintptr_t)job->lens_rgb | (uintptr_t)job->lens_instance |
+        (uintptr_t)job->lens_depth | (uintptr_t)job->lens_coords | (uintptr_t)job->lens_stats | (uintptr_t)job->lens_count) & 3u))
+    return c->fail(CSG_ERR_INVALID, "lens_remap: map must be 8-byte aligned, obj_coords 2-byte, every other pointer but "
+                                    "rgb and lens_valid 4-byte");
+  const size_t P = (size_t)job->width * job->height, SP = (size_t)job->src_width * job->src_height, n = n_frames;
+  {   // no output may overlap a source, the map or another output
+    struct Range { const void* p; size_t bytes; };
+    const Range src[] = {{job->map, P * 8u}, {job->rgb, n * SP * 3u}, {job->instance, n * SP * 4u},
+                         {job->depth, n * SP * 4u}, {job->obj_coords, n * SP * 6u}};
+    const Range dst[] = {{job->lens_rgb, n * P * 3u}, {job->lens_instance, n * P * 4u}, {job->lens_depth, n * P * 4u},
+                         {job->lens_coords, n * P * 6u}, {job->lens_valid, n * P},
+                         {job->lens_stats, n * job->n_labels * 20u}, {job->lens_count, n * kLnCauses * 4u}};
+    auto overlap = [](const Range& x, const Range& y) {
+      const uintptr_t x0 = (uintptr_t)x.p, y0 = (uintptr_t)y.p;
+      return x.p && y.p && x0 < y0 + y.bytes && y0 < x0 + x.bytes;
+    };
+    constexpr size_t n_dst = sizeof dst / sizeof dst[0];
+    for (size_t d = 0; d < n_dst; ++d) {
+      for (const Range& s : src)
+        if (overlap(dst[d], s)) return c->fail(CSG_ERR_INVALID, "lens_remap: an output overlaps a source");
+      for (size_t e = d + 1; e < n_dst; ++e)
+        if (overlap(dst[d], dst[e])) return c->fail(CSG_ERR_INVALID, "lens_remap: two outputs overlap");
+    }
+  }
+  hipStream_t st;
+  CSG_TRY(pass_stream(c, stream, &st));
+  LensArgs a{};
+  a.W = job->width;
+  a.H = job->height;
+  a.SW = job->src_width;
+  a.SH = job->src_height;
+  a.n = n_frames;
+  a.n_labels = job->lens_stats ? job->n_labels : 0u;
+  a.nearest = job->rgb_filter == CSG_LENS_FILTER_NEAREST;
+  a.map = job->map;
+  a.rgb = job->rgb;
+  a.instance = job->instance;
+  a.depth = job->depth;
+  a.obj_coords = job->obj_coords;
+  a.lens_rgb = job->lens_rgb;
+  a.lens_instance = job->lens_instance;
+  a.lens_depth = job->lens_depth;
+  a.lens_coords = job->lens_coords;
+  a.lens_valid = job->lens_valid;
+  a.lens_stats = job->lens_stats;
+  a.lens_count = job->lens_count;
+  launch_lens(a, st);
+  HIP_TRY(c, hipGetLastError());
+  return CSG_OK;
+}
+
+// The keypoints through the forward model: validates, rounds the model to float32 and enqueues one kernel.
+int csg_lens_points(csg_ctx* c, const csg_lens_job* job, uint32_t n_frames, void* stream) {
+  if (!c) return CSG_ERR_INVALID;
+  if (!job) return c->fail(CSG_ERR_INVALID, "lens_points: null job");
+  if (n_frames == 0) return c->fail(CSG_ERR_INVALID, "lens_points: no frames");
+  if (!lens_model_ok(job->model)) return c->fail(CSG_ERR_INVALID, "lens_points: model is NULL or not one csg_lens_map takes");
+  if (job->n_keypoints < 1 || job->n_keypoints > 65536u)
+    return c->fail(CSG_ERR_INVALID, "lens_points: n_keypoints %u outside 1..65536", job->n_keypoints);
+  const size_t total = (size_t)n_frames * job->n_keypoints;
+  if (total > (1u << 30)) return c->fail(CSG_ERR_INVALID, "lens_points: more than 2^30 keypoints");
+  if (!job->keypoints_uv || !job->keypoints_vis || !job->lens_uv || !job->lens_vis)
+    return c->fail(CSG_ERR_INVALID, "lens_points: keypoints_uv, keypoints_vis, lens_uv and lens_vis must not be NULL");
+  if (((uintptr_t)job->keypoints_uv | (uintptr_t)job->keypoints_vis | (uintptr_t)job->lens_uv | (uintptr_t)job->lens_vis) & 3u)
+    return c->fail(CSG_ERR_INVALID, "lens_points: every pointer must be 4-byte aligned");
+  {
+    struct Range { const void* p; size_t bytes; };
+    const Range r[] = {{job->lens_uv, total * 8u}, {job->lens_vis, total * 4u}, {job->keypoints_uv, total * 8u},
+                       {job->keypoints_vis, total * 4u}};
+    for (size_t d = 0; d < 2; ++d)
+      for (size_t s = d + 1; s < 4; ++s) {
+        const uintptr_t x0 = (uintptr_t)r[d].p, y0 = (uintptr_t)r[s].p;
+        if (x0 < y0 + r[s].bytes && y0 < x0 + r[d].bytes)
+          return c->fail(CSG_ERR_INVALID, "lens_points: an output overlaps a source or the other output");
+      }
+  }
+  hipStream_t st;
+  CSG_TRY(pass_stream(c, stream, &st));
+  const csg_lens_model& m = *job->model;
+  LensPointArgs a{};
+  a.W = (float)m.width;
+  a.H = (float)m.height;
+  a.fx = (float)m.fx;
+  a.fy = (float)m.fy;
+  a.cx = (float)m.cx;
+  a.cy = (float)m.cy;
+  a.sfx = (float)m.sfx;
+  a.sfy = (float)m.sfy;
+  a.scx = (float)m.scx;
+  a.scy = (float)m.scy;
+  a.k1 = (float)m.k1;
+  a.k2 = (float)m.k2;
+  a.p1 = (float)m.p1;
+  a.p2 = (float)m.p2;
+  a.k3 = (float)m.k3;
+  a.k4 = (float)m.k4;
+  a.k5 = (float)m.k5;
+  a.k6 = (float)m.k6;
+  a.total = (uint32_t)total;
+  a.uv = job->keypoints_uv;
+  a.vis = job->keypoints_vis;
+  a.lens_uv = job->lens_uv;
+  a.lens_vis = job->lens_vis;
+  launch_lens_points(a, st);
   HIP_TRY(c, hipGetLastError());
   return CSG_OK;
 }

@@ -57,6 +57,15 @@ same files:
                                     that ``python -m constructionsceneposeestimation_amd.bop merge RUN_DIR``
                                     joins into scene_camera / scene_gt / scene_gt_info.json; no reference
                                     counterpart)
+  lens/{rgb,depth16}_%06d.png + lens/coco_%06d.json + lens/lens.json
+                                   (optional "lens": the frame as a camera with Brown-Conrady lens distortion
+                                    shows it, lens.py -- the run's frames are the pinhole source camera, the
+                                    output camera (--lens PRESET or --lens-coeffs, --lens-size) gets the widest
+                                    view the source holds; RGB, 16-bit depth and ids resampled on the GPU behind
+                                    the render, the COCO masks, boxes and keypoints of the distorted frame, and
+                                    lens.json with the model, both cameras in both pixel conventions, the map's
+                                    digest and the run's pixels per cause; the other kinds stay pinhole; no
+                                    reference counterpart)
   logs/generation_summary.json     (:2090; statistics, frame_logs, counters)
   logs/generation_detail.log       (:254-263, per-frame entries + report)
 
@@ -87,6 +96,7 @@ import numpy as np
 from . import bop
 from . import camera_math as cm
 from . import depth_sensor
+from . import lens
 from . import masks
 from . import prep_pool
 from . import voxel_cloud
@@ -129,6 +139,10 @@ REFERENCE_OUTPUTS = ("rgb", "mask", "depth_csv", "depth_png", "pointcloud")
 # image, depth and mask files and does not go with the other per-object mask outputs.
 BOP_OUTPUT = "bop"
 BOP_EXCLUDES = ("mask", "mask_rle", "amodal_rle")
+# The frames as a camera with lens distortion shows them (lens.py): an output kind of its own, not part of
+# "all" -- it brings its own camera, image, depth and annotation files under lens/; the other kinds of the
+# same run stay pinhole.
+LENS_OUTPUT = "lens"
 
 
 # outputs encoded on the GPU in thread mode -> their csg_outputs.file_kinds kind (_lib.FILE_KINDS)
@@ -155,9 +169,9 @@ def parse_outputs(spec: str) -> tuple:
     if spec == "all":
         return OUTPUTS
     out = tuple(x.strip() for x in spec.split(",") if x.strip())
-    bad = [x for x in out if x not in OUTPUTS + (BOP_OUTPUT,)]
+    bad = [x for x in out if x not in OUTPUTS + (BOP_OUTPUT, LENS_OUTPUT)]
     if bad:
-        raise ValueError(f"unknown outputs {bad}; choose from {OUTPUTS + (BOP_OUTPUT,)}")
+        raise ValueError(f"unknown outputs {bad}; choose from {OUTPUTS + (BOP_OUTPUT, LENS_OUTPUT)}")
     check_bop(out)
     if "amodal_rle" in out and "mask_rle" not in out:
         raise ValueError("output amodal_rle adds to the annotations of mask_rle: ask for both")
@@ -172,6 +186,39 @@ def check_bop(outs) -> None:
         raise ValueError("output bop has no place for voxel clouds: it does not go with pointcloud_voxel_ply")
     if BOP_OUTPUT in outs and "depth_sensor16_png" in outs:
         raise ValueError("output bop has no place for sensor depth: it does not go with depth_sensor16_png")
+    if BOP_OUTPUT in outs and LENS_OUTPUT in outs:
+        raise ValueError("output bop has no place for lens distortion: it does not go with lens")
+
+
+def lens_model(width: int, height: int, intr, preset: Optional[str] = None, coeffs=None,
+               size: Optional[Sequence[int]] = None) -> "lens.LensModel":
+    """The model of the lens output: the run's frames (``width`` x ``height`` with the intrinsics ``intr``) are
+    the source camera; the output camera has ``size`` = (W, H) (default the frames'), the coefficients
+    ``coeffs`` (k1 k2 p1 p2 k3 [k4 k5 k6]) or those of ``preset`` (lens.PRESETS, default "wide"), and the widest
+    view whose every pixel the source frame holds (lens.fit_output)."""
+    if coeffs is None:
+        name = preset or "wide"
+        if name not in lens.PRESETS:
+            raise ValueError(f"lens preset {name!r}: one of {sorted(lens.PRESETS)}")
+        coeffs = lens.PRESETS[name]
+    elif preset is not None:
+        raise ValueError("lens: a preset or coefficients, not both")
+    coeffs = tuple(float(v) for v in coeffs)
+    if len(coeffs) not in (5, 8) or not all(np.isfinite(coeffs)):
+        raise ValueError(f"lens coefficients {coeffs!r}: 5 or 8 finite numbers k1,k2,p1,p2,k3[,k4,k5,k6]")
+    W, H = (int(width), int(height)) if size is None else (int(size[0]), int(size[1]))
+    if not (1 <= W <= 8192 and 1 <= H <= 8192):
+        raise ValueError(f"lens size {W}x{H} outside 1..8192")
+    return lens.fit_output(lens.output_camera(coeffs, W, H, 1.0),
+                           (int(width), int(height), intr.fx, intr.fy, intr.cx, intr.cy))
+
+
+def _write_lens_fragment(path: str, frame_id: int, **kw) -> None:
+    """masks.coco_fragment of a lens frame, its image record naming the file beside it."""
+    frag = masks.coco_fragment(frame_id, **kw)
+    frag["image"]["file_name"] = f"rgb_{int(frame_id):06d}.png"
+    with open(path, "wb") as fh:
+        fh.write(masks.fragment_bytes(frag))
 
 
 def sensor_model(preset: Optional[str] = None, baseline: Optional[float] = None,
@@ -219,7 +266,8 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
              voxel_size: float = voxel_cloud.DEFAULT_VOXEL_SIZE, voxel_capacity: int = 0,
              depth_sensor_preset: Optional[str] = None, sensor_baseline: Optional[float] = None,
              sensor_noise_px: Optional[float] = None, sensor_seed: int = 0,
-             voxel_points: int = 0, voxel_points_seed: int = 0) -> dict:
+             voxel_points: int = 0, voxel_points_seed: int = 0, lens_preset: Optional[str] = None,
+             lens_coeffs: Optional[Sequence[float]] = None, lens_size: Optional[Sequence[int]] = None) -> dict:
     """Render ``frames`` on one GPU and write them (``outputs``, default the
     reference's set; ``depth`` / ``depth_csv`` / ``pointcloud`` / ``normals``
     add the depth .npy, the depth .npy + CSV, the point cloud, the normals).
@@ -352,6 +400,16 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
             raise ValueError(f"depth16_counts_per_metre {depth16_counts_per_metre!r}: a finite number > 0")
         sens_model = sensor_model(depth_sensor_preset, sensor_baseline, sensor_noise_px)
         sens_job = dict(sens_model.to_job_fields(), seed=int(sensor_seed) & 0xFFFFFFFF)
+    want_lens = LENS_OUTPUT in outs
+    if want_lens:
+        if writer_mode != "thread":
+            raise ValueError("output lens is made by GPU passes behind the render: writer_mode 'thread'")
+        s16 = float(depth16_counts_per_metre)
+        if not (np.isfinite(s16) and s16 > 0):
+            raise ValueError(f"depth16_counts_per_metre {depth16_counts_per_metre!r}: a finite number > 0")
+        lens_m = lens_model(wl.width, wl.height, wl.intr, lens_preset, lens_coeffs, lens_size)
+        lens_host_map, _ = lens.build_map(lens_m)
+        os.makedirs(os.path.join(out_dir, "lens"), exist_ok=True)
     if "obj_coords" in outs or want_vox:
         objs = []
         for o in wl.scene.objects:
@@ -425,7 +483,7 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
     if want_amodal and not (amodal_kinds is not None and "all" in amodal_kinds):
         amodal_el = eligible_labels(wl.scene, DYNAMIC_KINDS if amodal_kinds is None else tuple(amodal_kinds))
     fw = None       # thread mode: the native fragment writer (writers.FragmentWriter), made with the first poses
-    kp_by_obj = masks.keypoints_by_object(wl.kp_table) if want_rle and not gpu_files else None
+    kp_by_obj = masks.keypoints_by_object(wl.kp_table) if (want_rle and not gpu_files) or want_lens else None
     if want_rle or want_bop:    # host-output batches keep their ids on the device for the span pass
         for x in rends:
             x.keep_instance(True)
@@ -440,6 +498,13 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
     if want_sens:   # ... and their depth for the sensor pass
         for x in rends:
             x.keep_depth(True)
+    if want_lens:   # ... and their RGB, ids and depth for the lens pass
+        for x in rends:
+            x.keep_rgb(True)
+            x.keep_instance(True)
+            x.keep_depth(True)
+    lens_cap, lens_span_cap, lens_buf = {}, {}, {}   # per renderer: file bytes, span capacity, device arrays
+    lens_counts = np.zeros(3, np.int64)              # the run's pixels per cause
     sens_cap = {}   # renderer -> the bytes its last batch's sensor PNGs took
     sens_buf = {}   # renderer -> its device arrays for the pass (intrinsics, keys, sensor depth, counts)
     sens_counts = np.zeros(7, np.int64)   # the run's pixels per cause
@@ -614,6 +679,54 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
             sensr[0] = [(buf[int(offsets[k]):int(offsets[k + 1])].tobytes(), cnt[k].astype(np.int64)) for k in range(n)]
             return int(offsets[-1]) + cnt.nbytes
 
+        lensr = [None]  # the batch's per-frame lens files and annotation inputs, with "lens"
+
+        def lens_of_batch(out) -> int:
+            import torch
+            (rgb, n0), (ids, n1), (dep, n2) = r.last_rgb(), r.last_instance(), r.last_depth()
+            if not rgb or not ids or not dep or {n0, n1, n2} != {len(fb)}:
+                raise RuntimeError(f"lens: the batch kept {n0} RGB, {n1} id and {n2} depth images, {len(fb)} frames rendered")
+            n, dev, LW, LH, nl = len(fb), torch.device("cuda", r.device), lens_m.width, lens_m.height, r.n_labels
+            if id(r) not in lens_buf:   # the renderer's device arrays, made once for a full batch
+                lens_buf[id(r)] = (torch.empty((batch, LH, LW, 3), dtype=torch.uint8, device=dev),
+                                   torch.empty((batch, LH, LW), dtype=torch.int32, device=dev),
+                                   torch.empty((batch, LH, LW), dtype=torch.float32, device=dev),
+                                   torch.empty((batch, nl, 5), dtype=torch.int32, device=dev),
+                                   torch.empty((batch, 3), dtype=torch.int32, device=dev))
+            d_rgb, d_ids, d_dep, d_st, d_cnt = lens_buf[id(r)]
+            d_map = r.lens_map(lens_m, lens_host_map)
+            have_kp = "keypoints_uv" in out
+            if have_kp:
+                K = out["keypoints_uv"].shape[1]
+                d_uv = torch.from_numpy(np.ascontiguousarray(out["keypoints_uv"][:n])).to(dev)
+                d_vis = torch.from_numpy(np.ascontiguousarray(out["keypoints_vis"][:n])).to(dev)
+                o_uv, o_vis = torch.empty_like(d_uv), torch.empty_like(d_vis)
+            torch.cuda.current_stream(dev).synchronize()   # the uploads, before the context's stream reads them
+            # on the context's stream, behind the render and in front of the encoder, which waits for both
+            r.lens_remap(n, map=d_map.data_ptr(), width=LW, height=LH, rgb=rgb, instance=ids, depth=dep,
+                         lens_rgb=d_rgb.data_ptr(), lens_instance=d_ids.data_ptr(), lens_depth=d_dep.data_ptr(),
+                         lens_stats=d_st.data_ptr(), lens_count=d_cnt.data_ptr())
+            if have_kp:
+                r.lens_points(n, lens_m, n_keypoints=K, keypoints_uv=d_uv.data_ptr(), keypoints_vis=d_vis.data_ptr(),
+                              lens_uv=o_uv.data_ptr(), lens_vis=o_vis.data_ptr())
+            buf = np.empty(lens_cap.get(id(r), n * (5 * LW * LH + 8192)), np.uint8)
+            offsets, need = r.encode_files(n, LW, LH, ("rgb_png", "depth16_png"), buf, rgb=d_rgb.data_ptr(),
+                                           depth=d_dep.data_ptr(), depth16_counts_per_metre=depth16_counts_per_metre)
+            if offsets is None:   # the files did not fit: a larger buffer, no second pass
+                buf = np.empty(need + need // 4, np.uint8)
+                offsets = r.copy_files(buf, 2 * n)
+            lens_cap[id(r)] = max(lens_cap.get(id(r), 0), need + need // 4)
+            spans, lens_span_cap[id(r)] = r.mask_spans_host(n, d_ids.data_ptr(), capacity=lens_span_cap.get(id(r), 0),
+                                                            height=LH, width=LW)
+            st = d_st[:n].cpu().numpy().view(np.uint32)   # (the encoder has waited for the passes)
+            cnt = d_cnt[:n].cpu().numpy().view(np.uint32)
+            uv, vis = (o_uv.cpu().numpy(), o_vis.cpu().numpy()) if have_kp else (None, None)
+            lensr[0] = [dict(rgb=buf[int(offsets[2 * k]):int(offsets[2 * k + 1])].tobytes(),
+                             depth=buf[int(offsets[2 * k + 1]):int(offsets[2 * k + 2])].tobytes(), spans=spans[k],
+                             stats=st[k].copy(), count=cnt[k].astype(np.int64),
+                             uv=uv[k] if have_kp else None, vis=vis[k] if have_kp else None) for k in range(n)]
+            return int(offsets[-1]) + st.nbytes + cnt.nbytes + sum(o.nbytes + sp.nbytes for o, sp in spans)
+
         cur = [None]   # the cameras of the attempt being rendered
 
         def run(views, projs):
@@ -629,7 +742,8 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                 arrays["file_offsets"] = offsets
                 d2h.append(int(offsets[-1]) + wire_bytes(out) + (spans_of_batch() if want_rle else 0)
                            + (bop_of_batch() if want_bop else 0) + (jpgs_of_batch() if want_jpg else 0)
-                           + (voxels_of_batch() if want_vox else 0) + (sensor_of_batch() if want_sens else 0))
+                           + (voxels_of_batch() if want_vox else 0) + (sensor_of_batch() if want_sens else 0)
+                           + (lens_of_batch(out) if want_lens else 0))
             else:
                 out = r.render(fr, want=want, out={k: v[:len(fb)] for k, v in arrays.items()})
                 d2h.append(wire_bytes(out) + (spans_of_batch() if want_rle else 0)
@@ -660,7 +774,7 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                 out = run(*wl.frame_params(fb, attempts))
                 check = again
         te = time.time()
-        return fb, slot, out, (te - tr, tp - tw, tr - tp), attempts, checks, failed, (rle[0], arle[0], bopr[0], jpgr[0], voxr[0], sensr[0])
+        return fb, slot, out, (te - tr, tp - tw, tr - tp), attempts, checks, failed, (rle[0], arle[0], bopr[0], jpgr[0], voxr[0], sensr[0], lensr[0])
 
     ahead = ThreadPoolExecutor(max_workers=n_rend)
     prep = ThreadPoolExecutor(max_workers=max(1, n_prep))
@@ -676,7 +790,7 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
         queued = [ahead.submit(render_batch, b) for b in range(min(n_rend, len(starts)))]
         for b in range(len(starts)):
             tq = time.time()
-            fb, slot, out, (dt, dwait, dprep), attempts, checks, failed, (rle, arle, bopr, jpgr, voxr, sensr) = queued.pop(0).result()
+            fb, slot, out, (dt, dwait, dprep), attempts, checks, failed, (rle, arle, bopr, jpgr, voxr, sensr, lensr) = queued.pop(0).result()
             t_main_wait += time.time() - tq
             t_render += dt
             t_slot_wait += dwait
@@ -738,6 +852,18 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
                     files.append((file_path(out_dir, "depth_sensor16_png", f), "call",
                                   (partial(bop.write_bytes, data=sensr[k][0]),)))
                     sens_counts += sensr[k][1]
+                if want_lens:   # made on the GPU behind the batch; the annotations from the lens frame's own arrays
+                    lf = lensr[k]
+                    files.append((os.path.join(out_dir, "lens", f"rgb_{f:06d}.png"), "call",
+                                  (partial(bop.write_bytes, data=lf["rgb"]),)))
+                    files.append((os.path.join(out_dir, "lens", f"depth16_{f:06d}.png"), "call",
+                                  (partial(bop.write_bytes, data=lf["depth"]),)))
+                    files.append((os.path.join(out_dir, "lens", f"coco_{f:06d}.json"), "call",
+                                  (partial(_write_lens_fragment, frame_id=f, height=lens_m.height, width=lens_m.width,
+                                           poses=pose_cache[f // 10], inst_stats=lf["stats"], spans=lf["spans"][1],
+                                           offsets=lf["spans"][0], kp_by_obj=kp_by_obj, kp_uv=lf["uv"],
+                                           kp_vis=lf["vis"]),)))
+                    lens_counts += lf["count"]
                 if want_bop:   # the two images from the GPU encoders, the mask files, then the fragment
                     if f // bop.FRAMES_PER_SCENE not in bop_scenes and sink == "disk":
                         bop.make_dirs(out_dir, f // bop.FRAMES_PER_SCENE)
@@ -846,6 +972,15 @@ def generate(out_dir: str, frames: List[int], workload: str = "C3", seed: int = 
         with open(os.path.join(out_dir, "depth", "sensor.json"), "w") as fh:
             json.dump(meta, fh, indent=2)
         summary["depth_sensor"] = meta
+    if want_lens:
+        meta = {"model": lens_m.as_dict(), "opencv": lens_m.opencv(),
+                "pixel_convention": "model: pixel i covers [i, i + 1), centre i + 0.5; opencv: centre of pixel i at i",
+                "map_sha256": lens.map_digest(lens_host_map), "counts_per_metre": float(depth16_counts_per_metre),
+                "invalid": 0, "cause_names": list(lens.cause_names),
+                "cause_totals": {name: int(lens_counts[c]) for c, name in enumerate(lens.cause_names)}}
+        with open(os.path.join(out_dir, "lens", "lens.json"), "w") as fh:
+            json.dump(meta, fh, indent=2)
+        summary["lens"] = meta
     if want_vox:
         summary["voxel_cloud"] = {"voxel_size": float(np.float32(voxel_size)),
                                   "capacity": max(vox_cap.values()) if vox_cap else int(voxel_capacity),
@@ -867,7 +1002,7 @@ def main(argv=None):
     ap.add_argument("--width", type=int)
     ap.add_argument("--height", type=int)
     ap.add_argument("--outputs", default="reference",
-                    help=f"'reference' ({','.join(REFERENCE_OUTPUTS)}), 'all', or a comma list of {OUTPUTS + (BOP_OUTPUT,)}")
+                    help=f"'reference' ({','.join(REFERENCE_OUTPUTS)}), 'all', or a comma list of {OUTPUTS + (BOP_OUTPUT, LENS_OUTPUT)}")
     ap.add_argument("--depth", action="store_true", help="add depth .npy")
     ap.add_argument("--depth-csv", action="store_true", help="add depth .npy and CSV")
     ap.add_argument("--pointcloud", action="store_true")
@@ -915,6 +1050,11 @@ def main(argv=None):
     ap.add_argument("--sensor-noise-px", type=float, default=None,
                     help="standard deviation of the disparity noise in pixels, instead of the preset's")
     ap.add_argument("--sensor-seed", type=int, default=0, help="seed of the sensor noise (a frame's key is its frame id)")
+    ap.add_argument("--lens", default=None, metavar="PRESET", choices=sorted(lens.PRESETS),
+                    help="coefficients of the lens output (lens.PRESETS; default wide)")
+    ap.add_argument("--lens-coeffs", default=None, metavar="k1,k2,p1,p2,k3[,k4,k5,k6]",
+                    help="Brown-Conrady coefficients of the lens output in OpenCV's order, instead of a preset")
+    ap.add_argument("--lens-size", default=None, metavar="WxH", help="frame size of the lens output (default the run's)")
     ap.add_argument("--prep-workers", type=int, default=-1,
                     help="processes preparing batches ahead (-1: two for runs of >= 20 batches)")
     a = ap.parse_args(argv)
@@ -934,7 +1074,9 @@ def main(argv=None):
                        jpeg_quality=a.jpeg_quality, jpeg_subsampling=a.jpeg_subsampling, bop_rgb=a.bop_rgb,
                        voxel_size=a.voxel_size, voxel_capacity=a.voxel_capacity, depth_sensor_preset=a.depth_sensor,
                        sensor_baseline=a.sensor_baseline, sensor_noise_px=a.sensor_noise_px, sensor_seed=a.sensor_seed,
-                       voxel_points=a.voxel_points, voxel_points_seed=a.voxel_points_seed)
+                       voxel_points=a.voxel_points, voxel_points_seed=a.voxel_points_seed, lens_preset=a.lens,
+                       lens_coeffs=[float(v) for v in a.lens_coeffs.split(",")] if a.lens_coeffs else None,
+                       lens_size=[int(v) for v in a.lens_size.lower().split("x")] if a.lens_size else None)
     print(json.dumps(summary))
 
 

@@ -1187,6 +1187,114 @@ class Renderer:
         self._check(self.lib.csg_last_depth(self.ctx, C.byref(p), C.byref(nf)), "last_depth")
         return int(p.value or 0), int(nf.value)
 
+    # -- lens distortion --------------------------------------------------------------------
+    def lens_map(self, model, host_map: Optional[np.ndarray] = None):
+        """The device map of ``model`` (a :class:`lens.LensModel`): an (H, W, 2) int32 tensor made once by
+        :func:`lens.build_map` (or uploaded from ``host_map``, the same map made earlier) and cached per model."""
+        import torch
+        from . import lens as _lens
+        cache = self.__dict__.setdefault("_lens_maps", {})
+        if model not in cache:
+            mp = _lens.build_map(model)[0] if host_map is None else np.ascontiguousarray(host_map, np.int32)
+            if mp.shape != (model.height, model.width, 2):
+                raise CsgError(f"lens_map: a map of shape {mp.shape} for a {model.width} x {model.height} camera")
+            cache[model] = torch.from_numpy(mp).to(torch.device("cuda", self.device))
+        return cache[model]
+
+    def lens_remap(self, n: int, *, map: int, width: int, height: int, src_width: Optional[int] = None,
+                   src_height: Optional[int] = None, rgb: int = 0, instance: int = 0, depth: int = 0,
+                   obj_coords: int = 0, lens_rgb: int = 0, lens_instance: int = 0, lens_depth: int = 0,
+                   lens_coords: int = 0, lens_valid: int = 0, lens_stats: int = 0, lens_count: int = 0,
+                   n_labels: Optional[int] = None, rgb_filter: str = "bilinear", stream: int = 0) -> None:
+        """Enqueue the lens resampling of ``n`` frames (csg_lens_remap; raw device pointers, like
+        :meth:`sensor_depth`): the sources ``rgb`` (n, SH, SW, 3) uint8, ``instance`` (n, SH, SW) int32,
+        ``depth`` (n, SH, SW) float32 and ``obj_coords`` (n, SH, SW, 3) uint16 of the source camera
+        (``src_width`` x ``src_height``, default the renderer's) through ``map`` (H, W, 2) int32 into
+        ``lens_rgb``, ``lens_instance``, ``lens_depth``, ``lens_coords``, ``lens_valid`` (n, H, W) uint8 (0 valid,
+        else ``lens.cause_names``), ``lens_stats`` (n, n_labels, 5) uint32 as ``inst_stats`` and
+        ``lens_count`` (n, 3) uint32.  Any output may be 0, not all; each needs its source.  ``rgb_filter``:
+        "bilinear" (8-bit fixed point, four taps) or "nearest"."""
+        if rgb_filter not in _lib.LENS_FILTERS:
+            raise CsgError(f"lens_remap: rgb_filter {rgb_filter!r}: one of {sorted(_lib.LENS_FILTERS)}")
+        job = _lib.LensJob(int(width), int(height), self.width if src_width is None else int(src_width),
+                           self.height if src_height is None else int(src_height),
+                           self.n_labels if n_labels is None else int(n_labels), _lib.LENS_FILTERS[rgb_filter],
+                           map or None, rgb or None, instance or None, depth or None, obj_coords or None,
+                           lens_rgb or None, lens_instance or None, lens_depth or None, lens_coords or None,
+                           lens_valid or None, lens_stats or None, lens_count or None)
+        self._check(self.lib.csg_lens_remap(self.ctx, C.byref(job), int(n), stream or None), "lens_remap")
+
+    def lens_points(self, n: int, model, *, n_keypoints: int, keypoints_uv: int, keypoints_vis: int, lens_uv: int,
+                    lens_vis: int, stream: int = 0) -> None:
+        """Enqueue the keypoints of ``n`` frames through ``model``'s forward model (csg_lens_points; raw device
+        pointers): ``keypoints_uv`` (n, K, 2) float32 source pixels and ``keypoints_vis`` (n, K) int32 into
+        ``lens_uv`` and ``lens_vis`` of the output camera (:func:`lens.distort_points` is the definition)."""
+        m = model.to_c()
+        job = _lib.LensJob()
+        job.model = C.pointer(m)
+        job.n_keypoints = int(n_keypoints)
+        job.keypoints_uv, job.keypoints_vis = keypoints_uv or None, keypoints_vis or None
+        job.lens_uv, job.lens_vis = lens_uv or None, lens_vis or None
+        self._check(self.lib.csg_lens_points(self.ctx, C.byref(job), int(n), stream or None), "lens_points")
+
+    def lens_remap_host(self, n: int, model, *, rgb: int = 0, instance: int = 0, depth: int = 0, obj_coords: int = 0,
+                        keypoints_uv=None, keypoints_vis=None, n_labels: Optional[int] = None,
+                        rgb_filter: str = "bilinear", stream: int = 0) -> dict:
+        """:meth:`lens_remap` of the kept device images of a host-output batch (``keep_rgb`` / ``last_rgb``,
+        ``keep_instance`` / ``last_instance``, ``keep_depth`` / ``last_depth``; ``obj_coords`` a pointer of the
+        caller's), delivered to the host: a dict with ``"rgb"``, ``"instance"`` and ``"stats"``, ``"depth"``,
+        ``"coords"`` as far as their sources are given, and always ``"valid"`` and ``"count"``.  The source
+        camera of ``model`` must have the size of the images.  With ``keypoints_uv`` (n, K, 2) and
+        ``keypoints_vis`` (n, K) host arrays also ``"keypoints_uv"`` and ``"keypoints_vis"`` in the output
+        camera (:meth:`lens_points`).  The pass runs on a stream of the wrapper's own; ``stream`` (a raw handle,
+        0: none) is the stream still writing the sources, if any: it is waited for first.  Synchronous."""
+        import torch
+        n = int(n)
+        H, W, SH, SW = int(model.height), int(model.width), int(model.src_height), int(model.src_width)
+        L = self.n_labels if n_labels is None else int(n_labels)
+        dev = torch.device("cuda", self.device)
+        if stream:
+            torch.cuda.ExternalStream(stream, device=dev).synchronize()
+        else:
+            self.synchronize()
+        d_map = self.lens_map(model)
+        st = self.span_stream()
+        with torch.cuda.stream(st):
+            d_out = {"valid": torch.empty((n, H, W), dtype=torch.uint8, device=dev),
+                     "count": torch.empty((n, 3), dtype=torch.int32, device=dev)}
+            if rgb:
+                d_out["rgb"] = torch.empty((n, H, W, 3), dtype=torch.uint8, device=dev)
+            if instance:
+                d_out["instance"] = torch.empty((n, H, W), dtype=torch.int32, device=dev)
+                d_out["stats"] = torch.empty((n, L, 5), dtype=torch.int32, device=dev)
+            if depth:
+                d_out["depth"] = torch.empty((n, H, W), dtype=torch.float32, device=dev)
+            if obj_coords:
+                d_out["coords"] = torch.empty((n, H, W, 3), dtype=torch.int16, device=dev)
+            ptr = {k: (d_out[k].data_ptr() if k in d_out else 0) for k in
+                   ("rgb", "instance", "stats", "depth", "coords", "valid", "count")}
+            self.lens_remap(n, map=d_map.data_ptr(), width=W, height=H, src_width=SW, src_height=SH, rgb=rgb,
+                            instance=instance, depth=depth, obj_coords=obj_coords, lens_rgb=ptr["rgb"],
+                            lens_instance=ptr["instance"], lens_depth=ptr["depth"], lens_coords=ptr["coords"],
+                            lens_valid=ptr["valid"], lens_stats=ptr["stats"], lens_count=ptr["count"], n_labels=L,
+                            rgb_filter=rgb_filter, stream=st.cuda_stream)
+            if keypoints_uv is not None:
+                uv = np.ascontiguousarray(keypoints_uv, np.float32)
+                K = uv.shape[1]
+                d_uv = torch.from_numpy(uv.reshape(n, K, 2)).to(dev)
+                d_vis = torch.from_numpy(np.ascontiguousarray(keypoints_vis, np.int32).reshape(n, K)).to(dev)
+                d_out["keypoints_uv"] = torch.empty_like(d_uv)
+                d_out["keypoints_vis"] = torch.empty_like(d_vis)
+                self.lens_points(n, model, n_keypoints=K, keypoints_uv=d_uv.data_ptr(), keypoints_vis=d_vis.data_ptr(),
+                                 lens_uv=d_out["keypoints_uv"].data_ptr(), lens_vis=d_out["keypoints_vis"].data_ptr(),
+                                 stream=st.cuda_stream)
+            out = {k: t.cpu().numpy() for k, t in d_out.items()}
+            st.synchronize()
+        for k, dt in (("count", np.uint32), ("stats", np.uint32), ("coords", np.uint16)):
+            if k in out:
+                out[k] = out[k].view(dt)
+        return out
+
     # -- farthest-point sampling ------------------------------------------------------------
     def farthest_points(self, n_sets: int, *, rows: int, pool: int = 16384, samples: int, xyz: int, counts: int = 0,
                         set_keys: int = 0, seed: int = 0, fp_index: int = 0, fp_xyz: int = 0, fp_dist2: int = 0,

@@ -78,6 +78,8 @@
  *                               disparity, with the cause of every missing value
  *   csg_farthest_points ....... (new) farthest-point samples of point sets (the point samples,
  *                               the voxel clouds), with payload rows carried along
+ *   csg_lens_map / csg_lens_remap / csg_lens_points  (new) frames and their labels as a
+ *                               camera with lens distortion (Brown-Conrady) shows them
  *   csg_last_error / csg_destroy
  *
  * Threading: several contexts may share a device (each has its own stream
@@ -1351,6 +1353,149 @@ typedef struct {
   csg_fps_payload payloads[CSG_FPS_MAX_PAYLOADS];
 } csg_fps_job;
 int csg_farthest_points(csg_ctx* ctx, const csg_fps_job* job, uint32_t n_sets, void* stream);
+
+/* Lens distortion (Brown-Conrady, OpenCV's rational model): pinhole frames of a
+ * "source camera" resampled into the frames of an "output camera" whose lens
+ * distorts, with every label moved along -- ids, depth, object coordinates,
+ * per-label boxes and keypoints.  Three calls: csg_lens_map makes the lens's
+ * map on the host, once; csg_lens_remap resamples frames by a map;
+ * csg_lens_points moves keypoints by the forward model.
+ *
+ * Pixels.  Pixel i covers [i, i + 1) and its centre is i + 0.5, in both cameras
+ * (cx = width / 2 for a centred lens; OpenCV's numbers are these minus 1/2).
+ *
+ * Model.  Normalised pinhole (x, y) to normalised distorted (xd, yd):
+ *   r2 = x^2 + y^2
+ *   R  = (1 + k1 r2 + k2 r2^2 + k3 r2^3) / (1 + k4 r2 + k5 r2^2 + k6 r2^3)
+ *   xd = x R + 2 p1 x y + p2 (r2 + 2 x^2)
+ *   yd = y R + p1 (r2 + 2 y^2) + 2 p2 x y
+ * The output pixel of a point is (fx xd + cx, fy yd + cy), its source pixel
+ * (sfx x + scx, sfy y + scy).
+ *
+ * csg_lens_map needs no context and no GPU.  For every output pixel it inverts
+ * the model by Newton's method in float64 (16 steps whatever the data, the
+ * analytic Jacobian, every operation rounded once; the order of operations is
+ * the header comment of csrc/csg_lens_map.h, restated by tests/lens_ref.py) and
+ * writes map[j][i] = (qx, qy), the source position in 1/256 source pixel
+ * (qx = floor(sx * 256 + 0.5)), or (INT32_MIN, cause) where the pixel shows
+ * nothing, the first rule that applies giving the cause:
+ *   1 no preimage  a value is not finite, the forward model of the result misses
+ *                  the pixel's centre by more than 2^-10 output pixels, or the
+ *                  Jacobian there does not have both determinant > 0 and trace
+ *                  > 0 (the result lies beyond the fold of a strong barrel lens)
+ *   2 outside      the source pixel (qx >> 8, qy >> 8) is not in the source frame
+ * counts (or NULL) gets {valid, no preimage, outside}.  CSG_ERR_INVALID, nothing
+ * written: model or map NULL, a size outside 1..8192, a number that is not
+ * finite, a focal length that is not > 0.  No input yields undefined behaviour.
+ *
+ * csg_lens_remap: a stand-alone pass on device memory only, like
+ * csg_sensor_depth; the two frame sizes are the job's own and the result is
+ * defined to the bit.  W x H = the output's size, SW x SH = the source's.  Per
+ * output pixel (i, j) of frame f with (qx, qy) = map[j][i] (one map for every
+ * frame; it may be the caller's own, of any model):
+ *   cause  qx == INT32_MIN: 1 if qy == 1, else 2.  Otherwise 2 if the source
+ *          pixel (px, py) = (qx >> 8, qy >> 8) (arithmetic shifts) is not in
+ *          [0, SW) x [0, SH), else 0.  No map value yields an address outside
+ *          the arrays described.
+ *   cause 0:
+ *     lens_instance, lens_depth, lens_coords = instance, depth, obj_coords at
+ *       [f][py][px], bit for bit (a NaN depth included): a label and its depth
+ *       come from the same source pixel.  Depth stays the distance along the
+ *       optical axis, as OpenCV's model has it for distorted cameras.
+ *     lens_rgb, rgb_filter = CSG_LENS_FILTER_BILINEAR: tx = qx - 128,
+ *       x0 = tx >> 8, fx8 = tx & 255, and ty, y0, fy8 likewise; the taps
+ *       (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1), each coordinate
+ *       clamped into the source, have the weights (256 - fx8)(256 - fy8),
+ *       fx8 (256 - fy8), (256 - fx8) fy8, fx8 fy8; per channel
+ *       (sum of w * c + 32768) >> 16.  Colours blend across silhouettes, as in
+ *       the crops.  CSG_LENS_FILTER_NEAREST: rgb[f][py][px].
+ *     lens_valid = 0.
+ *   any other cause: RGB 0, id -1, depth +inf, coords 0, lens_valid = cause.
+ *   lens_stats[f][l] = pixels, minx, miny, maxx, maxy of label l in
+ *     lens_instance (as csg_outputs.inst_stats, a label without pixels gets 0,
+ *     0xFFFFFFFF, 0xFFFFFFFF, 0, 0); ids outside [0, n_labels) are counted nowhere.
+ *   lens_count[f] = the frame's pixels of cause 0, 1 and 2.
+ * Every element of every requested output is written; integer atomics only, so
+ * the result is a pure function of the inputs.
+ *
+ * Enqueues on `stream` (NULL = the context's stream) and returns; behind the
+ * render that wrote the sources on the same stream it needs no synchronisation.
+ * csg_synchronize waits for it under the rule for the crops.  The pass has no
+ * scratch and never touches the render's work buffers.
+ *
+ * Returns -1 for a NULL ctx.  CSG_ERR_INVALID, nothing enqueued or written: job
+ * NULL; n_frames == 0; a size outside 1..8192; an unknown rgb_filter; map NULL;
+ * no output at all; an output without its source (lens_rgb: rgb, lens_instance
+ * and lens_stats: instance, lens_depth: depth, lens_coords: obj_coords);
+ * lens_stats with n_labels == 0 (above CSG_SPAN_MAX_LABELS: CSG_ERR_LIMIT); an
+ * output that overlaps a source, the map or another output; a pointer that is
+ * not aligned: 8 bytes for map, 4 for instance, depth, lens_rgb, lens_instance,
+ * lens_depth, lens_coords, lens_stats and lens_count, 2 for obj_coords (rgb and
+ * lens_valid need none).
+ *
+ * csg_lens_points: the keypoints of the source render in the output camera, by
+ * the forward model in float32 (the model's numbers rounded to float32 first,
+ * every operation rounded once, '/' correctly rounded).  Per keypoint (u, v):
+ *   x = (u - scx) / sfx, y = (v - scy) / sfy
+ *   xx = x * x, yy = y * y, xy = x * y, r2 = xx + yy, r4 = r2 * r2, r6 = r4 * r2
+ *   N  = 1 + ((k1 * r2 + k2 * r4) + k3 * r6), D likewise with k4, k5, k6
+ *   Np = (k1 + (2 * k2) * r2) + (3 * k3) * r4, Dp likewise
+ *   R  = N / D, Rp = (Np * D - N * Dp) / (D * D)
+ *   xd = (x * R + (2 * p1) * xy) + p2 * (r2 + 2 * xx)
+ *   yd = (y * R + p1 * (r2 + 2 * yy)) + (2 * p2) * xy
+ *   a  = ((R + (2 * xx) * Rp) + (2 * p1) * y) + (6 * p2) * x
+ *   b  = ((2 * xy) * Rp + (2 * p1) * x) + (2 * p2) * y
+ *   d  = ((R + (2 * yy) * Rp) + (6 * p1) * y) + (2 * p2) * x
+ *   u' = fx * xd + cx, v' = fy * yd + cy
+ * If one of u', v', a, b, d is not finite: lens_uv = (0, 0), lens_vis = 0.
+ * Otherwise lens_uv = (u', v'), and lens_vis = 0 if the point is outside the
+ * output frame (not 0 <= u' < W and 0 <= v' < H) or beyond the fold (not both
+ * a * d - b * b > 0 and a + d > 0), else keypoints_vis.  It reads of the job
+ * `model` (host memory, read before the call returns; its sizes as csg_lens_map
+ * checks them), n_keypoints (1..65536), keypoints_uv, keypoints_vis, lens_uv and
+ * lens_vis (all needed, 4-byte aligned, no output over a source).  Stream rules
+ * as above. */
+typedef struct {
+  uint32_t width, height;          /* output camera: 1..8192 each */
+  uint32_t src_width, src_height;  /* source camera: 1..8192 each */
+  double fx, fy, cx, cy;           /* output camera, pixels */
+  double k1, k2, p1, p2, k3, k4, k5, k6;   /* OpenCV's order */
+  double sfx, sfy, scx, scy;       /* source camera, pixels */
+} csg_lens_model;                  /* 144 bytes */
+int csg_lens_map(const csg_lens_model* m, int32_t* map /* host [H][W][2] */, uint32_t* counts /* [3] or NULL */);
+
+#define CSG_LENS_FILTER_BILINEAR 0u
+#define CSG_LENS_FILTER_NEAREST 1u
+typedef struct {
+  uint32_t width, height;          /* W, H: of the output frames */
+  uint32_t src_width, src_height;  /* SW, SH: of the source frames */
+  uint32_t n_labels;               /* labels of lens_stats */
+  uint32_t rgb_filter;             /* CSG_LENS_FILTER_* */
+  const int32_t* map;              /* device [H][W][2] */
+  /* sources, device memory, layouts of csg_outputs at SW x SH; any may be NULL */
+  const uint8_t*  rgb;             /* [n][SH][SW][3] */
+  const int32_t*  instance;        /* [n][SH][SW] */
+  const float*    depth;           /* [n][SH][SW] */
+  const uint16_t* obj_coords;      /* [n][SH][SW][3] */
+  /* outputs, device memory; any may be NULL, not all */
+  uint8_t*  lens_rgb;              /* [n][H][W][3] */
+  int32_t*  lens_instance;         /* [n][H][W] */
+  float*    lens_depth;            /* [n][H][W] */
+  uint16_t* lens_coords;           /* [n][H][W][3] */
+  uint8_t*  lens_valid;            /* [n][H][W] 0 = valid, else the cause */
+  uint32_t* lens_stats;            /* [n][n_labels][5] */
+  uint32_t* lens_count;            /* [n][3] = valid, no preimage, outside */
+  /* csg_lens_points only */
+  const csg_lens_model* model;     /* host memory */
+  uint32_t n_keypoints;            /* K: 1..65536 */
+  uint32_t pad;
+  const float*   keypoints_uv;     /* [n][K][2] source pixels */
+  const int32_t* keypoints_vis;    /* [n][K] */
+  float*   lens_uv;                /* [n][K][2] output pixels */
+  int32_t* lens_vis;               /* [n][K] */
+} csg_lens_job;
+int csg_lens_remap(csg_ctx* ctx, const csg_lens_job* job, uint32_t n_frames, void* stream);
+int csg_lens_points(csg_ctx* ctx, const csg_lens_job* job, uint32_t n_frames, void* stream);
 
 /* Stand-alone 3D->2D projection (host buffers): uv [n][2], vis [n] without a
  * depth test (1 = in front and inside the image, 0 otherwise). */
